@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- bidirectional redistribution throughput (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, runs W warm-up steps, times K steps and prints one JSON line: `value` (Msamples/s), `ms_per_step`
+(one timed step), the pass's counters and kernel times, `roofline` and `solve_fp64` from those same timed passes.
+--dump-outputs DIR then also writes what the last timed step computed (dump_outputs).  --full adds everything below that
+takes runs of its own (box, clock_in_pass, sustained, regimes, pcie_inclusive, roofline.alone, configs, cpu_baseline,
+parity_checked; N > 1: ranks and config 5).
 
 One "step" = one redistribution pass over one frame's worth of synthetic AOV-sample visits that are
 already resident in HBM: clear accumulators -> scan/compact/direct-accumulate -> draw/splat ->
@@ -12,12 +18,12 @@ per second (Msamples/s; 1 sample = 1 visit record of 80+16K bytes, SURVEY.md sec
 Workload at N=1: the configuration the metric is quoted on -- double-gauss 50 mm polynomial optics,
 3840x2160, 9 visits/pixel (AA 3), 1024 redistribution draws per redistributed visit, beauty only,
 highlight fraction f_hi (default 2^-16, the scan-dominated regime of SURVEY.md section 8d; the
-highlight-heavy regime 1.6e-3 is reported beside it in "regimes").  N>1 is the metric's wording -- the SAME 4K
+highlight-heavy regime 1.6e-3 is reported beside it in "regimes", --full).  N>1 is the metric's wording -- the SAME 4K
 frame at 1/2/4/8 GPUs (strong scaling, the default): rank r owns a band of consecutive rows -- its visits and its
 tile of the output -- and sends what its draws touched outside the band to the owners over xGMI
 (lentil_hip_exchange_bands; pota_amd/distributed.py::frame_step_bands is the torch.distributed form of the same
 step).  At N>1 BASELINE config 5 (7680x4320, 2048 draws, tiled across the N GPUs) is timed the same way and
-reported under "configs"; --scaling weak keeps the per-GPU work fixed instead (the same camera at N times the pixels).
+reported under "configs" (--full); --scaling weak keeps the per-GPU work fixed instead (the same camera at N times the pixels).
 LENTIL_PARTITION=interleaved selects rows r mod N with one sum all-reduce of the whole frame instead.
 
 Launch: `python bench.py --gpus N` starts its own N ranks (a child `python -m torch.distributed.run ... bench.py`,
@@ -33,7 +39,7 @@ Set-up before the W warm-up steps (untimed, like generating the visits): two pas
 draw buffers (the first pass of a context waits for each chunk's scan and allocates); for N > 1 three calibration
 passes that re-cut the row bands from the ranks' pass times.
 
-The printed JSON line also carries
+The printed JSON line also carries (the parts that take runs of their own: with --full only)
   roofline     -- the HBM-bound scan kernel: algorithmic bytes (visits x 80 B) / its mean duration,
                   measured with HIP events on the library's stream -- the start / stop events of the launch itself
                   (hipExtLaunchKernelGGL) in a streamed pass: events recorded *around* the launch read ~90 us more than
@@ -63,10 +69,6 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-# A pass uses several HIP streams (scan, publishers, solve waves beside the scan); torch and RCCL bring theirs.
-# With the runtime's default of 4 hardware queues per process two of them end up sharing one.
-# Read when the HIP runtime initialises, so: before torch is imported.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 # dmabuf IPC for RCCL between the ranks of one node (the host driver here supports nothing else); also read early
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
@@ -87,6 +89,12 @@ def parse():
     ap.add_argument("--f-hi", type=float, default=2.0 ** -16)
     ap.add_argument("--aovs", type=int, default=0, help="extra (non-beauty) AOVs")
     ap.add_argument("--lens", default="double_gauss_50mm")
+    ap.add_argument("--full", action="store_true", help="also every measurement and check beside the headline figure (box probe, "
+                                                        "clock in the pass, sustained figure, second regime, PCIe, scan alone, "
+                                                        "configs, CPU baseline, parity check; N > 1: per-rank figures, config 5); "
+                                                        "the --no-* switches below leave parts of it out")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity-check", action="store_true", help="skip the oracle check of a sample of the workload")
     ap.add_argument("--no-scan-alone", action="store_true", help="skip the measurement of the scan kernel with the chip to itself")
@@ -125,6 +133,26 @@ def physical_cores():
         return len(seen) or None
     except OSError:
         return None
+
+
+def usable_cpus():
+    """CPUs this process may keep busy: the fewest of its affinity mask, its cgroup's CPU quota and OMP_NUM_THREADS
+    (os.cpu_count() is the whole box's; the oracle's samples are sized per thread, so too many threads only make them longer)."""
+    try:
+        n = len(os.sched_getaffinity(0))
+    except (AttributeError, OSError):
+        n = os.cpu_count() or 1
+    try:
+        with open("/sys/fs/cgroup/cpu.max") as f:
+            quota, period = f.read().split()[:2]
+        if quota != "max":
+            n = min(n, max(1, int(quota) // int(period)))
+    except (OSError, ValueError):
+        pass
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return max(1, n)
 
 
 def pcie_inclusive(b):
@@ -189,10 +217,7 @@ def cpu_baseline(args, p, table, M, tan_half_fov):
     lib = oracle_lib.load()
     W, H = args.width, args.height
     logical = os.cpu_count() or 1
-    try:
-        usable = len(os.sched_getaffinity(0))          # (a container may see fewer CPUs than the box has)
-    except (AttributeError, OSError):
-        usable = logical
+    usable = usable_cpus()          # (a container may have fewer CPUs than the box shows)
     threads = max(1, min(usable, 512))
 
     def timed(n_threads, budget_s, repeats):
@@ -250,7 +275,7 @@ def parity_check(W, H, M, samples, aovs, f_hi, p, table, tan_half_fov, device_in
     lib = oracle_lib.load()
     n_aovs = 1 + aovs
     # (one shared oracle frame whatever the thread count: orc_redistribute_threads)
-    threads = max(1, min(os.cpu_count() or 1, 64))
+    threads = max(1, min(usable_cpus(), 64))
     est_full = W * H * M * (0.1e-6 + f_hi * samples * 35e-6 * 1.1) * 1.5       # (shadow buffers, the draw log)
     row_step = max(1, int(round(est_full / (budget_s * threads))))
     rows = list(range(0, H, row_step))
@@ -569,6 +594,32 @@ def summarize(b, r, n_total, bytes_per_visit):
     return ms, launches, launch_ms, launch_bytes, achieved
 
 
+DUMP_BYTES = 60 * 10 ** 6       # --dump-outputs: all of a run's files together stay below 64 MB
+DUMP_SEED = 0xD0D0
+
+
+def dump_outputs(b, out_dir):
+    """--dump-outputs DIR: what the last timed step computed, as a caller of the pass receives it -- every AOV's resolved
+    image (lentil_hip_download_aov: RGBA fp32 per pixel) over the frame rows this rank owns -- as DIR/aov<a>.npy [n, 4] fp32,
+    with DIR/pixel_index.npy [n] fp64 saying which pixels (row-major over the frame).  A frame too large for DUMP_BYTES is
+    sampled: a fixed, seeded set of its pixels, the same whenever the arguments are.  N > 1: every rank writes its own files
+    (_rank<r>), each with 1/N of the bytes."""
+    import numpy as np
+    b.ctx.sync()
+    xres, yres = int(b.p.xres), int(b.p.yres)
+    lo, hi = b.band if b.band is not None else (0, yres)
+    n_aovs = 1 + b.aovs
+    count = (hi - lo) * xres
+    k = min(count, DUMP_BYTES // max(1, b.world) // (16 * n_aovs + 8))
+    idx = np.arange(count, dtype=np.int64) if k == count else np.sort(np.random.default_rng(DUMP_SEED).choice(count, k, replace=False))
+    idx += lo * xres
+    suffix = "_rank%d" % b.rank if b.world > 1 else ""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "pixel_index%s.npy" % suffix), idx.astype(np.float64))
+    for a in range(n_aovs):
+        np.save(os.path.join(out_dir, "aov%d%s.npy" % (a, suffix)), b.ctx.download_aov(a)[idx])
+
+
 def spawn_ranks(args):
     """`python bench.py --gpus N` without a launcher: start the N ranks as a child (the launcher the driver itself uses),
     BEFORE this process has imported torch or touched the GPU, pass its output on and leave with its exit code."""
@@ -734,11 +785,14 @@ def main():
         for _ in range(2):
             b.step()
         torch.cuda.synchronize()
+    full = args.full
     # what this box delivers, before and after the timed steps (rank 0's GPU; the probe's kernels run ~10 ms on the library's stream)
     box = None
-    if rank == 0:
+    if rank == 0 and full:
         box = checked(b.ctx.box_probe)
     r = b.run(args.steps, args.warmup)
+    if args.dump_outputs:
+        dump_outputs(b, args.dump_outputs)
     if rank == 0 and isinstance(box, dict) and "error" not in box:
         after = checked(b.ctx.box_probe)
         if isinstance(after, dict) and "error" not in after:
@@ -750,7 +804,7 @@ def main():
     # the clock those steps ran at: a short loop of its own with a one-wave sampler beside it (tools/clock_trace.py; never the
     # timed loop) -- box.shader_clock_mhz_under_fp64 is what the chip settles at after 15 ms of steady fp64 load, a 2-ms pass gets less
     clock_in_pass = None
-    if rank == 0 and world == 1 and not args.no_clock_trace:
+    if rank == 0 and world == 1 and full and not args.no_clock_trace:
         try:
             sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
             import clock_trace
@@ -764,7 +818,7 @@ def main():
     # see whichever regime the chip is in; this second figure, timed the same way, is reported beside it in roofline.sustained --
     # never as `value` -- with the clock in the pass for both.
     sustained = None
-    if rank == 0 and world == 1 and not args.no_sustained and not emulate:
+    if rank == 0 and world == 1 and full and not args.no_sustained and not emulate:
         try:
             for _ in range(350):
                 b.step()
@@ -842,7 +896,7 @@ def main():
         "solve_fp64": {"scan_dominated": b.solve_block(r)},
     }
 
-    if world > 1 and not emulate:
+    if world > 1 and not emulate and full:
         try:
             out["ranks"] = rank_details(b, dist, torch, dev)
         except Exception as e:      # the headline number must still be reported
@@ -874,7 +928,7 @@ def main():
             except Exception as e:
                 out.setdefault("configs", {})[name] = {"value": None, "error": repr(e)}
 
-    if rank == 0 and world == 1 and not emulate and not args.no_configs and os.environ.get("GPU_MAX_HW_QUEUES") != "4":
+    if rank == 0 and world == 1 and not emulate and full and not args.no_configs and os.environ.get("GPU_MAX_HW_QUEUES", "4") != "4":
         # The same headline pass in a process whose runtime keeps its default of four hardware queues (a renderer that loads the
         # plugin sets nothing): a child process, because the runtime reads the variable when it initialises.  lentil_hip_create
         # probes whether the pass's streams run side by side there; where they do not, the pass takes its chunked form.
@@ -893,7 +947,7 @@ def main():
         except Exception as e:      # noqa: BLE001
             out["runtime_default_hw_queues"] = {"ms_per_step": None, "error": repr(e)}
 
-    if not args.no_second_regime and world == 1:
+    if full and not args.no_second_regime and world == 1:
         f2 = 1.6e-3
         b.generate(f2)
         st = max(2, min(args.steps, 2))
@@ -906,7 +960,7 @@ def main():
             "passes": {"streamed": r2["streamed"], "chunks_redone_after_a_short_estimate": r2["redone"]}}}
         out["solve_fp64"]["highlight_heavy"] = b.solve_block(r2)
 
-    if rank == 0 and world == 1 and not args.no_pcie and not emulate:
+    if rank == 0 and world == 1 and full and not args.no_pcie and not emulate:
         try:
             b.generate(args.f_hi)
             out["pcie_inclusive"] = pcie_inclusive(b)
@@ -941,10 +995,10 @@ def main():
                 else:
                     os.environ[k] = v
 
-    if rank == 0 and world == 1 and not emulate and not args.no_scan_alone:
+    if rank == 0 and world == 1 and not emulate and full and not args.no_scan_alone:
         out["roofline"]["alone"] = scan_alone(W, H, args.lens, args.samples, args.aovs, args.bokeh_image, n_total, bytes_per_visit)
 
-    if not args.no_configs and world == 1 and not emulate:
+    if full and not args.no_configs and world == 1 and not emulate:
         # BASELINE.json's other single-GPU configurations, measured the same way (alternating streams)
         cfgs = {}
         for name, kw in (
@@ -988,13 +1042,13 @@ def main():
                 cfgs[name] = {"value": None, "error": repr(e)}
         out["configs"] = cfgs
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and full and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(*cpu_args)
         except Exception as e:      # the GPU number must still be reported
             out["cpu_baseline"] = {"value": None, "unit": "Msamples/s", "cores": 0, "kind": "port",
                                    "sample": "failed: %r" % (e,)}
-    if rank == 0 and world == 1 and not args.no_parity_check:
+    if rank == 0 and world == 1 and full and not args.no_parity_check:
         out["parity_checked"] = checked(parity_check, args.width, args.height, M, args.samples, args.aovs, args.f_hi, cpu_args[1],
                                         cpu_args[2], cpu_args[4], local_rank, torch, bokeh_tables=cpu_bokeh)
     from pota_amd import distributed

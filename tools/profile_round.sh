@@ -9,7 +9,7 @@ cd "$(dirname "$0")/.."
 TAG=${1:-rXX}
 O=gpurun_out/$TAG; mkdir -p $O/profiles
 export TMPDIR=/tmp
-# (the runtime reads it when the profiler's preloaded library initialises it -- before bench.py's own os.environ.setdefault runs)
+# (the runtime reads it when the profiler's preloaded library initialises it, before bench.py starts)
 export GPU_MAX_HW_QUEUES=8
 B="bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-second-regime --no-configs --no-pcie --no-parity-check --no-scan-alone"
 B4="$B --lens petzval_58mm --aovs 8"                       # BASELINE config 4
@@ -66,6 +66,6 @@ python3 $C5 2>/dev/null | tail -1 > $O/profiles/${TAG}_config5_one_gpu_streamed.
 LENTIL_STREAM=0 python3 $C5 2>/dev/null | tail -1 > $O/profiles/${TAG}_config5_one_gpu_chunked.json
 # 6. single bands of the multi-GPU frames, each alone on this GPU
 bash tools/emulate_bands.sh > $O/profiles/${TAG}_emulated_bands.txt 2>&1
-# 7. the bench line as the driver runs it
-python3 bench.py --steps 20 --warmup 3 > $O/profiles/${TAG}_bench_line.json 2> $O/bench.err
+# 7. the full bench line (--full: box probe, clock, configs, CPU baseline, parity check beside the headline)
+python3 bench.py --full --steps 20 --warmup 3 > $O/profiles/${TAG}_bench_line.json 2> $O/bench.err
 ls -la $O/profiles
