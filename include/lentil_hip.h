@@ -399,7 +399,11 @@ int lentil_hip_get_xor128_state(lentil_hip_ctx *ctx, uint32_t state[4]);
  * others zero, so the sum all-reduce of lentil_hip_accum_buffer completes the closest AOVs too.
  * Frame-wide visit ids: uniform streams derive them from pixel_y0 / pixel_row_stride (the id a single
  * process walking the whole frame would give the visit -- row bands and row-interleaved partitions alike);
- * ragged streams use visit_id_base + index. */
+ * ragged streams use visit_id_base + index.
+ * Candidates at depth 0 / NaN (order-dependent upstream, lentil_closest_replay.h): with the library's communicator
+ * (lentil_hip_comm_init) the pass leaves them to lentil_hip_allreduce / _exchange_bands, which replay their pixels over every
+ * rank's candidates; a caller that min-reduces the keys itself (deferred != 0, no communicator) gets the pass refused
+ * (LENTIL_ERR_UNSUPPORTED). */
 int lentil_hip_set_closest_exchange(lentil_hip_ctx *ctx, int deferred, uint32_t visit_id_base);
 int lentil_hip_zkey_buffer(lentil_hip_ctx *ctx, void **device_ptr, uint64_t *n_keys);
 int lentil_hip_closest_gather(lentil_hip_ctx *ctx);
@@ -459,12 +463,19 @@ int lentil_hip_stream(lentil_hip_ctx *ctx, void **hip_stream);
  *                  on every rank: closest-AOV winner keys are min-reduced and the winners gathered (requires
  *                  set_closest_exchange(deferred = 1) when the frame has closest AOVs), then one sum all-reduce
  *                  of accum_buffer.  lentil_hip_resolve afterwards gives every rank the whole image.
+ *                  Frames with closest AOVs start with a one-word all-gather (did any rank's pass meet a candidate at
+ *                  depth 0 / NaN?); if one did, the pixels such candidates reached are replayed in frame-wide visit order
+ *                  over every rank's candidates (all-gathered) before the gather: the same winner keys on every rank.
  * exchange_bands : tiled output.  Rank r's visits are rows [bounds[r], bounds[r+1]) (bounds == NULL: an even split
  *                  of visit_rows); its band of the frame is the same rows, the last band reaching to yres.
  *                  After lentil_hip_redistribute on every rank: the touched rows are all-gathered, what a
  *                  rank added to another's band travels point to point (sparse != 0: as pixel entries when
  *                  at most a quarter of the pixels hold anything, else as packed rows), the owner merges
  *                  the arrivals in rank order and resolves its band; band_lo / band_hi (may be NULL) return it.
+ *                  Frames with closest AOVs: the same one-word agreement first; if some rank met a candidate at depth
+ *                  0 / NaN, every rank's candidates at the flagged pixels go to the owner with their values, and the owner
+ *                  replays those pixels in visit order after its merges, before the resolve.  In both exchanges a rank
+ *                  whose pass kept no complete draw log runs it again with one first (lentil_hip_degenerate_stats).
  *                  Collective: every rank calls it with the same bounds / visit_rows / sparse. */
 int lentil_hip_comm_unique_id(uint8_t id[128]);
 int lentil_hip_comm_init(lentil_hip_ctx *ctx, const uint8_t id[128], int rank, int world);
@@ -480,6 +491,14 @@ int lentil_hip_exchange_stats(lentil_hip_ctx *ctx, uint64_t *bytes_sent, uint64_
  * (every message's size known to both ends beforehand, no host wait between compaction and merge) and directed pairs whose
  * entries did not fit their message and followed as whole rows; either pointer may be NULL.  Instrumentation. */
 int lentil_hip_exchange_counts(lentil_hip_ctx *ctx, uint64_t *fixed_form, uint64_t *pairs_overflowed);
+/* Closest-filtered candidates at depth (Z) 0 or NaN (src/lentil.h:832-845: their outcome depends on the order of the
+ * candidates at the pixel), for the last lentil_hip_redistribute and the exchange behind it: *degenerate = 1 when the pass
+ * met one in a frame with a closest-filtered AOV; the distinct pixels the ranks flagged for the replay across GPUs; the
+ * candidate nodes this rank sent to / received from other ranks; passes wiped and run again to get a draw log (one GPU: the
+ * pass itself; across GPUs: inside the exchange, on a rank that met no such candidate but holds draws at a flagged pixel).
+ * Any pointer may be NULL.  Instrumentation. */
+int lentil_hip_degenerate_stats(lentil_hip_ctx *ctx, uint32_t *degenerate, uint64_t *flagged_pixels, uint64_t *nodes_sent,
+                                uint64_t *nodes_received, uint64_t *passes_rerun);
 /* *concurrent = 1 when the four HIP streams a streamed pass keeps kernels resident on run them side by side (they were
  * chosen so at lentil_hip_create: streams that share one of the runtime's hardware queues serialise, and the pass then
  * takes about 1.5 x as long; 2: and a fifth one beside them, on which a pass with cryptomatte AOVs replays the own-pixel

@@ -33,7 +33,7 @@ EXPORTS = [
     "lentil_hip_host_alloc", "lentil_hip_host_free", "lentil_hip_visits_begin", "lentil_hip_visits_append",
     "lentil_hip_visits_wait", "lentil_hip_visits_end",
     "lentil_hip_comm_unique_id", "lentil_hip_comm_init", "lentil_hip_comm_destroy", "lentil_hip_allreduce",
-    "lentil_hip_exchange_bands", "lentil_hip_exchange_stats", "lentil_hip_exchange_counts", "lentil_hip_streams_concurrent",
+    "lentil_hip_exchange_bands", "lentil_hip_exchange_stats", "lentil_hip_exchange_counts", "lentil_hip_degenerate_stats", "lentil_hip_streams_concurrent",
     "lentil_hip_alloc_crypto", "lentil_hip_upload_crypto", "lentil_hip_bind_crypto", "lentil_hip_download_crypto",
     "lentil_hip_download_crypto_table", "lentil_hip_visits_begin_crypto", "lentil_hip_visits_append_crypto",
 ]
@@ -165,6 +165,7 @@ def load_library():
         "lentil_hip_exchange_bands": (i, [vp, vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
         "lentil_hip_exchange_stats": (i, [vp, C.POINTER(u64), C.POINTER(u64)]),
         "lentil_hip_exchange_counts": (i, [vp, C.POINTER(u64), C.POINTER(u64)]),
+        "lentil_hip_degenerate_stats": (i, [vp, C.POINTER(C.c_uint32), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
         "lentil_hip_streams_concurrent": (i, [vp, C.POINTER(C.c_int)]),
     }
     for name, (res, args) in sig.items():
@@ -470,6 +471,14 @@ class Context:
         a, b = C.c_uint64(), C.c_uint64()
         self._chk(self.lib.lentil_hip_exchange_counts(self.h, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
+
+    def degenerate_stats(self):
+        """(degenerate, flagged pixels, nodes sent, nodes received, passes run again) of the last pass and the exchange behind
+        it: closest-filtered candidates at depth 0 / NaN (lentil_hip_degenerate_stats)"""
+        d = C.c_uint32()
+        n = [C.c_uint64() for _ in range(4)]
+        self._chk(self.lib.lentil_hip_degenerate_stats(self.h, C.byref(d), *[C.byref(x) for x in n]))
+        return (int(d.value),) + tuple(int(x.value) for x in n)
 
     def touched_rows(self):
         lo, hi = C.c_int32(), C.c_int32()

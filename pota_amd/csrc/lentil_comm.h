@@ -198,6 +198,191 @@ LENTIL_API int lentil_hip_exchange_counts(lentil_hip_ctx *ctx, uint64_t *fixed_f
   return LENTIL_OK;
 }
 
+// ---- closest-filtered AOVs with candidates at depth 0 / NaN across GPUs (lentil_closest_replay.h) ------------------------
+// The outcome at such a pixel depends on the order of ALL its candidates, on every rank: a min-reduce or a min-merge of the
+// keys gets it wrong.  Scratch slots of this step lie behind the 12 per peer of the exchanges.
+static size_t deg_slot(const LentilComm *cm, size_t k) { return (size_t)cm->world * 12 + k; }
+
+// One word per rank -- did its pass meet such a candidate -- all-gathered at the start of the exchange, before anything from
+// another rank is merged.  When some rank did, every rank needs its pass's draw log: one that kept none (or an incomplete one)
+// runs the pass again with one, as on one GPU (its frame holds nothing but that pass yet).  *any: the replay step runs.
+static int degenerate_agree(lentil_hip_ctx *ctx, LentilComm *cm, bool *any) {
+  *any = false;
+  const int64_t word = ctx->degenerate_seen ? 1 : 0;
+  HIP_TRY(ctx, hipMemcpyAsync(cm->d_meta_mine, &word, sizeof word, hipMemcpyHostToDevice, ctx->stream));
+  RCCL_TRY(ctx, g_rccl.AllGather(cm->d_meta_mine, cm->d_meta_all, 1, kNcclInt64, cm->comm, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(cm->h_meta_all, cm->d_meta_all, (size_t)cm->world * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  for (int q = 0; q < cm->world; ++q)
+    if (cm->h_meta_all[q] & 1) *any = true;
+  if (!*any) return LENTIL_OK;
+  bool complete = false;
+  unsigned long long n_log = 0;
+  const int rc = closest_log_complete(ctx, &complete, &n_log);
+  if (rc || complete) return rc;
+  return closest_rerun_with_log(ctx, nullptr);
+}
+
+// Sized point-to-point exchange of byte blocks: out[q] (n_out[q] bytes) goes to rank q; what the others send to this rank lands
+// in scratch slot `slot` behind `front` bytes, in rank order (n_in[q] bytes from q).  The sizes travel first: one all-gather of
+// world words per rank.
+static int deg_alltoall(lentil_hip_ctx *ctx, LentilComm *cm, const std::vector<const uint8_t *> &out, const std::vector<uint64_t> &n_out,
+                        size_t slot, uint64_t front, uint8_t **in, std::vector<uint64_t> &n_in) {
+  const int world = cm->world, rank = cm->rank;
+  std::vector<int64_t> mine((size_t)world, 0);
+  for (int q = 0; q < world; ++q) mine[(size_t)q] = q == rank ? 0 : (int64_t)n_out[(size_t)q];
+  HIP_TRY(ctx, hipMemcpyAsync(cm->d_meta_mine, mine.data(), (size_t)world * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+  RCCL_TRY(ctx, g_rccl.AllGather(cm->d_meta_mine, cm->d_meta_all, (size_t)world, kNcclInt64, cm->comm, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(cm->h_meta_all, cm->d_meta_all, (size_t)world * world * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  n_in.assign((size_t)world, 0);
+  uint64_t total = front;
+  for (int q = 0; q < world; ++q) {
+    const int64_t n = q == rank ? 0 : cm->h_meta_all[(size_t)q * world + rank];
+    if (n < 0) return fail(ctx, LENTIL_ERR_HIP, "closest-AOV replay across GPUs: a peer announced a negative size");
+    n_in[(size_t)q] = (uint64_t)n;
+    total += (uint64_t)n;
+  }
+  void *p;
+  int rc;
+  if ((rc = comm_scratch(ctx, cm, slot, (size_t)total, &p))) return rc;
+  *in = (uint8_t *)p;
+  RCCL_TRY(ctx, g_rccl.GroupStart());
+  int g_err = 0;
+  uint64_t off = front;
+  for (int q = 0; q < world; ++q) {
+    if (q == rank) continue;
+    if (n_out[(size_t)q] && !g_err) g_err = g_rccl.Send(out[(size_t)q], (size_t)n_out[(size_t)q], kNcclUint8, q, cm->comm, ctx->stream);
+    if (n_in[(size_t)q] && !g_err) g_err = g_rccl.Recv(*in + off, (size_t)n_in[(size_t)q], kNcclUint8, q, cm->comm, ctx->stream);
+    off += n_in[(size_t)q];
+  }
+  const int r_end = g_rccl.GroupEnd();
+  if (g_err) return fail(ctx, LENTIL_ERR_HIP, std::string("ncclSend / ncclRecv: ") + g_rccl.GetErrorString(g_err));
+  if (r_end) return fail(ctx, LENTIL_ERR_HIP, std::string("ncclGroupEnd: ") + g_rccl.GetErrorString(r_end));
+  return LENTIL_OK;
+}
+
+// The replay over every rank's candidates, after a degenerate_agree that found some rank with a degenerate candidate.
+// Interleaved (bands == null): every rank sends its nodes to every other one and writes the same winner keys into the whole
+// frame -- call it after the min-reduces, before the gather, whose sum all-reduce then carries the values.  Tiled (`bands`:
+// rows [lo, hi) of every rank, 2 world words): a node goes to the owner of its pixel's band with the values its visit gives
+// the closest slots, and the owner writes keys and values in its rows [b_lo, b_hi) -- after the merges, before the resolve.
+static int degenerate_exchange(lentil_hip_ctx *ctx, LentilComm *cm, const int32_t *bands, int32_t b_lo, int32_t b_hi) {
+  const int world = cm->world, rank = cm->rank;
+  const uint64_t np = ctx->F.np;
+  int rc;
+  untrust_touched(ctx);              // (the closest slots of flagged pixels are written below)
+  ctx->resolved_valid = false;
+  bool complete = false;
+  unsigned long long n_log = 0;
+  if ((rc = closest_log_complete(ctx, &complete, &n_log))) return rc;
+  if (!complete) return fail(ctx, LENTIL_ERR_NOMEM, "closest-AOV replay across GPUs: the draw log did not hold the pass's accepted draws");
+  const int n_dest = bands ? world : 1;
+  const dim3 grid((unsigned)ctx->num_cu * 8), block(256);
+  void *p;
+  // control words: [0] flagged pixels, [1, 1 + n_dest) nodes per destination, then first node / nodes of every segment,
+  // then (tiled) the bands
+  const size_t ctl_words = 1 + 3 * (size_t)n_dest + 2 * (size_t)world;
+  if ((rc = comm_scratch(ctx, cm, deg_slot(cm, 0), ctl_words * 4, &p))) return rc;
+  unsigned int *ctl = (unsigned int *)p;
+  int32_t *d_bands = reinterpret_cast<int32_t *>(ctl + 1 + 3 * (size_t)n_dest);
+  if ((rc = comm_scratch(ctx, cm, deg_slot(cm, 1), (size_t)np, &p))) return rc;
+  uint8_t *flag = (uint8_t *)p;
+  HIP_TRY(ctx, hipMemsetAsync(ctl, 0, (1 + (size_t)n_dest) * 4, ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(flag, 0, (size_t)np, ctx->stream));
+  if (bands) HIP_TRY(ctx, hipMemcpyAsync(d_bands, bands, 2 * (size_t)world * 4, hipMemcpyHostToDevice, ctx->stream));
+  ReplayArgs a{};
+  a.P = ctx->P; a.lens_length = ctx->have_lens ? ctx->hlens.length : 0.0; a.V = ctx->V; a.F = ctx->F;
+  a.log = ctx->d_log; a.n_log = n_log; a.flag = flag;
+  // ---- 1. the pixels this rank's degenerate candidates reached, compacted; every rank's list to every rank
+  hipLaunchKernelGGL(replay_mark_visits_kernel, grid, block, 0, ctx->stream, a);
+  if (n_log) hipLaunchKernelGGL(replay_mark_log_kernel, grid, block, 0, ctx->stream, a);
+  if ((rc = comm_scratch(ctx, cm, deg_slot(cm, 2), 4096 * 4, &p))) return rc;
+  uint32_t cap = (uint32_t)(cm->scratch_bytes[deg_slot(cm, 2)] / 4 > 0xFFFFFFFFull ? 0xFFFFFFFFull : cm->scratch_bytes[deg_slot(cm, 2)] / 4);
+  hipLaunchKernelGGL(xflag_compact_kernel, grid, block, 0, ctx->stream, flag, np, (uint32_t *)p, cap, ctl);
+  HIP_TRY(ctx, hipGetLastError());
+  unsigned int n_own = 0;
+  HIP_TRY(ctx, hipMemcpyAsync(&n_own, ctl, 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (n_own > cap) {
+    if ((rc = comm_scratch(ctx, cm, deg_slot(cm, 2), (size_t)n_own * 4, &p))) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(ctl, 0, 4, ctx->stream));
+    hipLaunchKernelGGL(xflag_compact_kernel, grid, block, 0, ctx->stream, flag, np, (uint32_t *)p, n_own, ctl);
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  const uint8_t *own_list = (const uint8_t *)p;
+  std::vector<const uint8_t *> out((size_t)world, own_list);
+  std::vector<uint64_t> n_out((size_t)world, (uint64_t)n_own * 4), n_in;
+  uint8_t *got = nullptr;
+  if ((rc = deg_alltoall(ctx, cm, out, n_out, deg_slot(cm, 3), 0, &got, n_in))) return rc;
+  uint64_t n_got = 0;
+  for (uint64_t n : n_in) n_got += n / 4;
+  if (n_got) hipLaunchKernelGGL(xflag_set_kernel, grid, block, 0, ctx->stream, flag, np, (const uint32_t *)got, n_got);
+  // ---- 2. this rank's candidates at every flagged pixel: counted per destination, then filled into their segments
+  HIP_TRY(ctx, hipMemsetAsync(ctl, 0, (1 + (size_t)n_dest) * 4, ctx->stream));
+  hipLaunchKernelGGL(xflag_compact_kernel, grid, block, 0, ctx->stream, flag, np, nullptr, 0u, ctl);      // (the count: the stats)
+  XNodeArgs x{};
+  x.a = a;
+  x.words = kXNodeWords + (bands ? 4u * ctx->F.n_aovs : 0u);
+  x.n_dest = n_dest;
+  x.bands = bands ? d_bands : nullptr;
+  x.count = ctl + 1;
+  x.seg = ctl + 1 + n_dest;
+  x.out = nullptr;
+  hipLaunchKernelGGL(xnode_pack_kernel, grid, block, 0, ctx->stream, x);
+  HIP_TRY(ctx, hipGetLastError());
+  std::vector<unsigned int> cnt(1 + (size_t)n_dest);
+  HIP_TRY(ctx, hipMemcpyAsync(cnt.data(), ctl, cnt.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->deg_flagged = cnt[0];
+  std::vector<unsigned int> seg(2 * (size_t)n_dest);
+  uint64_t n_mine = 0;
+  for (int d = 0; d < n_dest; ++d) { seg[(size_t)d] = (unsigned int)n_mine; seg[(size_t)(n_dest + d)] = cnt[(size_t)(1 + d)]; n_mine += cnt[(size_t)(1 + d)]; }
+  if (n_mine > 0xFFFFFFFFull / 2) return fail(ctx, LENTIL_ERR_NOMEM, "closest-AOV replay across GPUs: too many candidates");
+  const uint64_t node_bytes = (uint64_t)x.words * 4;
+  if ((rc = comm_scratch(ctx, cm, deg_slot(cm, 4), (size_t)(n_mine * node_bytes), &p))) return rc;
+  x.out = (uint32_t *)p;
+  HIP_TRY(ctx, hipMemcpyAsync(ctl + 1 + n_dest, seg.data(), seg.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(ctl + 1, 0, (size_t)n_dest * 4, ctx->stream));
+  if (n_mine) hipLaunchKernelGGL(xnode_pack_kernel, grid, block, 0, ctx->stream, x);
+  HIP_TRY(ctx, hipGetLastError());
+  // ---- 3. the nodes travel: interleaved all of them to every rank, tiled each to the owner of its pixel
+  const uint8_t *mine_nodes = (const uint8_t *)x.out;
+  uint64_t n_keep = n_mine;
+  for (int q = 0; q < world; ++q) {
+    if (bands) { out[(size_t)q] = mine_nodes + (uint64_t)seg[(size_t)q] * node_bytes; n_out[(size_t)q] = (uint64_t)seg[(size_t)(n_dest + q)] * node_bytes; }
+    else { out[(size_t)q] = mine_nodes; n_out[(size_t)q] = n_mine * node_bytes; }
+  }
+  if (bands) n_keep = seg[(size_t)(n_dest + rank)];
+  uint8_t *all = nullptr;
+  if ((rc = deg_alltoall(ctx, cm, out, n_out, deg_slot(cm, 5), n_keep * node_bytes, &all, n_in))) return rc;
+  if (n_keep) HIP_TRY(ctx, hipMemcpyAsync(all, bands ? out[(size_t)rank] : mine_nodes, (size_t)(n_keep * node_bytes), hipMemcpyDeviceToDevice, ctx->stream));
+  uint64_t n_all = n_keep, sent = 0, received = 0;
+  for (int q = 0; q < world; ++q) {
+    if (q == rank) continue;
+    sent += n_out[(size_t)q] / node_bytes;
+    received += n_in[(size_t)q] / node_bytes;
+  }
+  n_all += received;
+  ctx->deg_nodes_sent = sent;
+  ctx->deg_nodes_received = received;
+  if (n_all > 0xFFFFFFF0ull) return fail(ctx, LENTIL_ERR_NOMEM, "closest-AOV replay across GPUs: too many candidates");
+  // ---- 4. the per-pixel lists over the union, resolved by the one-GPU rule
+  if ((rc = comm_scratch(ctx, cm, deg_slot(cm, 6), (size_t)np * 4, &p))) return rc;
+  uint32_t *head = (uint32_t *)p;
+  if ((rc = comm_scratch(ctx, cm, deg_slot(cm, 7), (size_t)n_all * sizeof(ReplayNode), &p))) return rc;
+  ReplayNode *rnodes = (ReplayNode *)p;
+  HIP_TRY(ctx, hipMemsetAsync(head, 0xFF, (size_t)np * 4, ctx->stream));
+  if (n_all) hipLaunchKernelGGL(xnode_list_kernel, grid, block, 0, ctx->stream, (const uint32_t *)all, x.words, (uint32_t)n_all, np, head, rnodes);
+  const uint64_t p_lo = bands ? (uint64_t)b_lo * ctx->P.xres : 0ull, p_hi = bands ? (uint64_t)b_hi * ctx->P.xres : np;
+  if (p_hi > p_lo)
+    hipLaunchKernelGGL(xnode_resolve_kernel, grid, block, 0, ctx->stream, ctx->F, (const uint8_t *)flag, p_lo, p_hi < np ? p_hi : np,
+                       (const uint32_t *)head, (const ReplayNode *)rnodes, (uint32_t)n_all, (const uint32_t *)all, x.words, bands != nullptr);
+  HIP_TRY(ctx, hipGetLastError());
+  ++ctx->n_degenerate_replays;
+  return LENTIL_OK;
+}
+
 // interleaved partition: every rank ends up with the whole frame's accumulators (distributed.frame_step)
 LENTIL_API int lentil_hip_allreduce(lentil_hip_ctx *ctx) {
   CHECK_CTX(ctx);
@@ -208,6 +393,8 @@ LENTIL_API int lentil_hip_allreduce(lentil_hip_ctx *ctx) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   int rc;
   if (ctx->crypto) return fail(ctx, LENTIL_ERR_UNSUPPORTED, "cryptomatte AOVs travel with the tiled exchange only (lentil_hip_exchange_bands)");
+  bool degenerate = false;         // some rank's pass met a closest candidate at depth 0 / NaN (a pass run again here has a log)
+  if ((ctx->F.zkey || ctx->F.zkey_dbg) && ctx->closest_deferred && (rc = degenerate_agree(ctx, cm, &degenerate))) return rc;
   if ((rc = fold_direct(ctx, 0, ctx->F.np, true))) return rc;        // what the scan kept apart joins the sum
   untrust_touched(ctx);
   if (ctx->F.zkey || ctx->F.zkey_dbg) {
@@ -217,6 +404,7 @@ LENTIL_API int lentil_hip_allreduce(lentil_hip_ctx *ctx) {
       RCCL_TRY(ctx, g_rccl.AllReduce(ctx->F.zkey, ctx->F.zkey, ctx->F.np, kNcclUint64, kNcclMin, cm->comm, ctx->stream));
     if (ctx->F.zkey_dbg)       // lentil_debug: a key plane of its own (src/lentil.h:838-845)
       RCCL_TRY(ctx, g_rccl.AllReduce(ctx->F.zkey_dbg, ctx->F.zkey_dbg, ctx->F.np, kNcclUint64, kNcclMin, cm->comm, ctx->stream));
+    if (degenerate && (rc = degenerate_exchange(ctx, cm, nullptr, 0, 0))) return rc;      // the same winner keys on every rank
     if ((rc = lentil_hip_closest_gather(ctx))) return rc;
   }
   RCCL_TRY(ctx, g_rccl.AllReduce(ctx->F.acc, ctx->F.acc, ctx->F.np * ctx->F.stride, kNcclFloat32, kNcclSum, cm->comm, ctx->stream));
@@ -238,7 +426,7 @@ LENTIL_API int lentil_hip_allreduce(lentil_hip_ctx *ctx) {
 // arrived.  The host looks at the headers once, at the end: they give the next capacities, and a pair whose entries did
 // not fit (count > capacity: nothing of it was merged) sends the rows of its region whole, as the sized form does.
 static int exchange_bands_fixed(lentil_hip_ctx *ctx, LentilComm *cm, const int32_t *bounds, int32_t visit_rows,
-                                int32_t b_lo, int32_t b_hi, int32_t lo, int32_t hi) {
+                                int32_t b_lo, int32_t b_hi, int32_t lo, int32_t hi, const int32_t *deg_bands) {
   const int world = cm->world, rank = cm->rank;
   const int32_t yres = (int32_t)ctx->P.yres;
   const uint32_t xres = ctx->P.xres;
@@ -324,7 +512,8 @@ static int exchange_bands_fixed(lentil_hip_ctx *ctx, LentilComm *cm, const int32
     if (i.cap && b_hi > b_lo)
       if ((rc = merge_sparse_impl(ctx, (uint32_t)b_lo, (uint32_t)(b_hi - b_lo), i.cap, i.idx + kHdrWords, i.vals, i.k, i.kd, i.idx))) return rc;
   }
-  if ((rc = lentil_hip_resolve_rows(ctx, (uint32_t)b_lo, (uint32_t)(b_hi - b_lo)))) return rc;
+  // (deg_bands: the closest slots of flagged pixels are replayed once every merge is done, the resolve follows that, below)
+  if (!deg_bands && (rc = lentil_hip_resolve_rows(ctx, (uint32_t)b_lo, (uint32_t)(b_hi - b_lo)))) return rc;
   // ---- the headers, once everything is on its way
   for (int q = 0; q < world; ++q) {
     if (q == rank) continue;
@@ -386,9 +575,13 @@ static int exchange_bands_fixed(lentil_hip_ctx *ctx, LentilComm *cm, const int32
         if ((rc = merge_rows_impl(ctx, (uint32_t)r.lo, (uint32_t)(r.hi - r.lo), r.packed, r.key_rows, r.dkey_rows, true))) return rc;
         merged = true;
       }
-    if (merged && (rc = lentil_hip_resolve_rows(ctx, (uint32_t)b_lo, (uint32_t)(b_hi - b_lo)))) return rc;
+    if (merged && !deg_bands && (rc = lentil_hip_resolve_rows(ctx, (uint32_t)b_lo, (uint32_t)(b_hi - b_lo)))) return rc;
   }
   cm->last_sent = sent; cm->last_received = received;
+  if (deg_bands) {
+    if ((rc = degenerate_exchange(ctx, cm, deg_bands, b_lo, b_hi))) return rc;
+    if ((rc = lentil_hip_resolve_rows(ctx, (uint32_t)b_lo, (uint32_t)(b_hi - b_lo)))) return rc;
+  }
   return LENTIL_OK;
 }
 
@@ -420,6 +613,20 @@ LENTIL_API int lentil_hip_exchange_bands(lentil_hip_ctx *ctx, const int32_t *bou
   const bool keys = ctx->F.zkey != nullptr, dkeys = ctx->F.zkey_dbg != nullptr;
   if ((keys || dkeys) && ctx->closest_deferred)
     return fail(ctx, LENTIL_ERR_INVALID, "tiled exchange: the pass must gather its own winners (set_closest_exchange(ctx, 0, ...))");
+  // closest candidates at depth 0 / NaN on some rank: agreed on before anything is compacted (a pass run again here changes
+  // the frame), replayed after the merges
+  std::vector<int32_t> deg_bands;
+  if (keys || dkeys) {
+    bool degenerate = false;
+    const uint64_t reruns = ctx->deg_passes_rerun;
+    rc = degenerate_agree(ctx, cm, &degenerate);
+    if (!rc && ctx->deg_passes_rerun != reruns) rc = lentil_hip_touched_rows(ctx, &lo, &hi);
+    if (rc) { if (sparse) cm->poisoned = true; return rc; }
+    if (degenerate) {
+      deg_bands.resize((size_t)(2 * world));
+      for (int q = 0; q < world; ++q) band_of(q, deg_bands[(size_t)(2 * q)], deg_bands[(size_t)(2 * q + 1)]);
+    }
+  }
 
   // (LENTIL_EXCHANGE_FIXED=0: the sized form below, whose sends carry exactly the entries found -- and whose host waits for
   // every count; sparse == 0, whole rows always, is that form too)
@@ -428,7 +635,7 @@ LENTIL_API int lentil_hip_exchange_bands(lentil_hip_ctx *ctx, const int32_t *bou
     if (cm->poisoned)
       return fail(ctx, LENTIL_ERR_INVALID, "tiled exchange: an earlier exchange on this communicator failed on this rank; its message "
                                            "sizes no longer agree with its peers' (lentil_hip_comm_destroy / _comm_init on every rank)");
-    rc = exchange_bands_fixed(ctx, cm, bounds, visit_rows, b_lo, b_hi, lo, hi);
+    rc = exchange_bands_fixed(ctx, cm, bounds, visit_rows, b_lo, b_hi, lo, hi, deg_bands.empty() ? nullptr : deg_bands.data());
     if (rc) cm->poisoned = true;
     return rc;
   }
@@ -563,5 +770,18 @@ LENTIL_API int lentil_hip_exchange_bands(lentil_hip_ctx *ctx, const int32_t *bou
       if ((rc = merge_rows_impl(ctx, (uint32_t)i.r_lo, (uint32_t)(i.r_hi - i.r_lo), i.packed, i.key_rows, i.dkey_rows, true))) return rc;
     }
   }
+  if (!deg_bands.empty() && (rc = degenerate_exchange(ctx, cm, deg_bands.data(), b_lo, b_hi))) return rc;
   return lentil_hip_resolve_rows(ctx, (uint32_t)b_lo, (uint32_t)(b_hi - b_lo));
+}
+
+// the last pass and the exchange behind it: see include/lentil_hip.h
+LENTIL_API int lentil_hip_degenerate_stats(lentil_hip_ctx *ctx, uint32_t *degenerate, uint64_t *flagged_pixels, uint64_t *nodes_sent,
+                                           uint64_t *nodes_received, uint64_t *passes_rerun) {
+  CHECK_CTX(ctx);
+  if (degenerate) *degenerate = ctx->degenerate_seen ? 1u : 0u;
+  if (flagged_pixels) *flagged_pixels = ctx->deg_flagged;
+  if (nodes_sent) *nodes_sent = ctx->deg_nodes_sent;
+  if (nodes_received) *nodes_received = ctx->deg_nodes_received;
+  if (passes_rerun) *passes_rerun = ctx->deg_passes_rerun;
+  return LENTIL_OK;
 }

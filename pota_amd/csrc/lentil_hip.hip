@@ -98,6 +98,9 @@ struct lentil_hip_ctx {
   bool closest_auto_log = false;
   uint64_t closest_auto_log_cap = 0;
   uint64_t n_degenerate_replays = 0;
+  // lentil_hip_degenerate_stats: the last pass and the exchange behind it (distinct pixels flagged on any rank, candidate nodes
+  // sent to / received from other ranks, passes wiped and run again to get a draw log)
+  uint64_t deg_flagged = 0, deg_nodes_sent = 0, deg_nodes_received = 0, deg_passes_rerun = 0;
   struct DirRegion {
     int32_t x0 = 0, y0 = 0; uint32_t row_stride = 0, ppr = 0; uint64_t npix = 0;
     bool operator==(const DirRegion &o) const { return x0 == o.x0 && y0 == o.y0 && row_stride == o.row_stride && ppr == o.ppr && npix == o.npix; }
@@ -3386,16 +3389,47 @@ static void account_pass(lentil_hip_ctx *ctx);
 
 // Closest-filtered AOVs after a pass that met candidates at depth 0 / NaN: lentil_closest_replay.h.  Returns LENTIL_OK with
 // *need_log set when the pass kept no (complete) draw log to replay from.
-static int closest_degenerate_replay(lentil_hip_ctx *ctx, bool *need_log) {
-  *need_log = false;
+// Did the last pass keep a draw log that holds every accepted draw?  *n_log: its records.
+static int closest_log_complete(lentil_hip_ctx *ctx, bool *complete, unsigned long long *n_log) {
   const int C = ctx->n_chunks;
-  unsigned long long n_log = 0;
+  *n_log = 0;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  HIP_TRY(ctx, hipMemcpy(&n_log, (char *)(ctx->d_ctr + C) + offsetof(DevCounters, log_count), sizeof n_log, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(n_log, (char *)(ctx->d_ctr + C) + offsetof(DevCounters, log_count), sizeof *n_log, hipMemcpyDeviceToHost));
   unsigned long long accepted = 0;
   for (const DevCounters &k : ctx->h_ctr) accepted += k.accepted;
-  if (!ctx->d_log || n_log > ctx->log_cap || (accepted && n_log < accepted)) { *need_log = true; return LENTIL_OK; }
+  *complete = !(!ctx->d_log || *n_log > ctx->log_cap || (accepted && *n_log < accepted));
+  return LENTIL_OK;
+}
+
+// No (complete) draw log to replay from, and the frame held nothing but this pass: a log sized from the pass's counters, the
+// frame wiped, the pass once more -- and a log from the start in every later pass of this context.  `xor_entry`: the xor128
+// state the first run started from (null: the pass draws no xor128 numbers).
+static int closest_rerun_with_log(lentil_hip_ctx *ctx, const uint32_t *xor_entry) {
+  unsigned long long accepted = 0;
+  for (const DevCounters &k : ctx->h_ctr) accepted += k.accepted;
+  ctx->closest_auto_log = true;
+  ctx->closest_auto_log_cap = accepted + accepted / 4 + (1ull << 20);
+  int rc;
+  if ((rc = lentil_hip_set_draw_log(ctx, ctx->closest_auto_log_cap))) return rc;
+  if ((rc = lentil_hip_clear_frame(ctx))) return rc;
+  ctx->degenerate_seen = false;
+  if (xor_entry) memcpy(ctx->xor_state, xor_entry, sizeof ctx->xor_state);      // (thin lens, abb_chromatic > 0: the same colour channels as the first run)
+  if ((rc = redistribute_impl(ctx))) return rc;
+  // (counters and timing describe the second run; that there were two is reported like any pass that was redone)
+  ++ctx->last_fallback;
+  ++ctx->deg_passes_rerun;
+  ctx->redo_note = "the pass was run twice: candidates at depth 0 / NaN compete for a closest-filtered AOV and the first run kept no draw log "
+                   "to replay their pixels from (lentil_closest_replay.h); later passes of this context keep one from the start";
+  return LENTIL_OK;
+}
+
+static int closest_degenerate_replay(lentil_hip_ctx *ctx, bool *need_log) {
+  *need_log = false;
+  unsigned long long n_log = 0;
+  bool complete = false;
+  if (const int rc0 = closest_log_complete(ctx, &complete, &n_log)) return rc0;
+  if (!complete) { *need_log = true; return LENTIL_OK; }
   ReplayArgs a{};
   a.P = ctx->P; a.lens_length = ctx->have_lens ? ctx->hlens.length : 0.0; a.V = ctx->V; a.F = ctx->F;
   a.log = ctx->d_log; a.n_log = n_log;
@@ -3455,6 +3489,7 @@ LENTIL_API int lentil_hip_redistribute(lentil_hip_ctx *ctx) {
 static int redistribute_top(lentil_hip_ctx *ctx) {
   ctx->stall_redo = false;
   ctx->degenerate_seen = false;
+  ctx->deg_flagged = ctx->deg_nodes_sent = ctx->deg_nodes_received = ctx->deg_passes_rerun = 0;
   const bool clean_entry = ctx->cleared_since_pass;
   // (a context whose frames have needed the replay before keeps a draw log from the start: no pass is run twice again)
   if (ctx->closest_auto_log && ctx->log_cap == 0 && (ctx->F.zkey || ctx->F.zkey_dbg)) {
@@ -3469,34 +3504,25 @@ static int redistribute_top(lentil_hip_ctx *ctx) {
   ht_mark(ctx, "}pass");
   if (rc || !ctx->degenerate_seen) return rc;
   // ---- candidates at depth 0 / NaN compete for a closest-filtered AOV: their pixels are replayed in visit order
-  if (ctx->comm || ctx->closest_deferred)
+  // (with the library's communicator: inside lentil_hip_allreduce / _exchange_bands, over every rank's candidates; a caller
+  // that min-reduces the keys itself has no such step)
+  if (!ctx->comm && ctx->closest_deferred)
     return fail(ctx, LENTIL_ERR_UNSUPPORTED, "a sample with depth (Z) 0 or NaN competes for a closest-filtered AOV: the reference's result there "
-                                             "depends on the order of the samples at the pixel (src/lentil.h:832-837), which the exchange "
-                                             "between GPUs does not keep; the pass is refused");
+                                             "depends on the order of the samples at the pixel (src/lentil.h:832-837), which a min-reduce "
+                                             "of the keys between GPUs does not keep; the pass is refused (the library's own exchange, "
+                                             "lentil_hip_comm_init, replays such pixels)");
   // The replay walks ONE pass's candidates -- the bound visits and this pass's draw log -- in visit order: a frame that already
   // held an earlier pass's candidates (no clear in between) cannot be replayed from them, with or without a log.
   if (!clean_entry)
     return fail(ctx, LENTIL_ERR_UNSUPPORTED, "a sample with depth (Z) 0 or NaN competes for a closest-filtered AOV in a frame that was not cleared "
                                              "before this pass: the reference's result depends on the order of ALL candidates at the pixel "
                                              "(src/lentil.h:832-837), and an earlier pass's are gone; clear the frame before the pass");
+  if (ctx->comm) return LENTIL_OK;      // (the exchange replays these pixels over every rank's candidates: lentil_comm.h)
   bool need_log = false;
   if ((rc = closest_degenerate_replay(ctx, &need_log))) return rc;
   if (!need_log) return LENTIL_OK;
-  // no (complete) draw log to replay from.  The frame held nothing before this pass: a log sized from the pass's counters,
-  // the frame wiped, the pass once more -- and a log from the start in every later pass of this context.
-  unsigned long long accepted = 0;
-  for (const DevCounters &k : ctx->h_ctr) accepted += k.accepted;
-  ctx->closest_auto_log = true;
-  ctx->closest_auto_log_cap = accepted + accepted / 4 + (1ull << 20);
-  if ((rc = lentil_hip_set_draw_log(ctx, ctx->closest_auto_log_cap))) return rc;
-  if ((rc = lentil_hip_clear_frame(ctx))) return rc;
-  ctx->degenerate_seen = false;
-  memcpy(ctx->xor_state, xor_entry, sizeof xor_entry);       // (thin lens, abb_chromatic > 0: the same colour channels as the first run)
-  if ((rc = redistribute_impl(ctx))) return rc;
-  // (counters and timing describe the second run; that there were two is reported like any pass that was redone)
-  ++ctx->last_fallback;
-  ctx->redo_note = "the pass was run twice: candidates at depth 0 / NaN compete for a closest-filtered AOV and the first run kept no draw log "
-                   "to replay their pixels from (lentil_closest_replay.h); later passes of this context keep one from the start";
+  // no (complete) draw log to replay from: the pass once more, with one
+  if ((rc = closest_rerun_with_log(ctx, xor_entry))) return rc;
   if (!ctx->degenerate_seen) return LENTIL_OK;
   if ((rc = closest_degenerate_replay(ctx, &need_log))) return rc;
   if (need_log) return fail(ctx, LENTIL_ERR_NOMEM, "closest-AOV replay: the draw log did not hold the pass's accepted draws");

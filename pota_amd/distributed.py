@@ -149,6 +149,10 @@ class HipEngine:
     def redistribute(self):
         self.ctx.redistribute()
 
+    def degenerate(self):
+        """did the last pass meet a closest-filtered candidate at depth 0 / NaN (see degenerate_gate)"""
+        return self.ctx.degenerate_stats()[0] != 0
+
     def fold_direct(self):
         self.ctx.accum_buffer()      # what the scan keeps apart for the resolve goes into the block the collective sums
 
@@ -179,6 +183,45 @@ def exchange_closest(zkey, dist):
     zkey.bitwise_xor_(_SIGN)
 
 
+def _redistribute(engine):
+    """engine.redistribute(); -> the LentilError of a pass the library refuses (ERR_UNSUPPORTED), for degenerate_gate"""
+    from . import capi
+    try:
+        engine.redistribute()
+    except capi.LentilError as e:
+        if e.code != capi._abi.ERR_UNSUPPORTED:
+            raise
+        return e
+    return None
+
+
+def degenerate_gate(engine, dist, refused=None):
+    """Closest-filtered candidates at depth 0 / NaN make the outcome at their pixels depend on the order of ALL candidates
+    there (src/lentil.h:832-845).  The library replays such pixels on one GPU and inside its own exchange (frame_step_native,
+    frame_step_bands_native); the keys these torch forms min-reduce / min-merge cannot.  So before any collective that moves
+    frame data every rank contributes one flag -- its pass met such a candidate, or was refused (`refused`) -- to a SUM
+    all-reduce, and if any rank's is set every rank raises: none is left waiting in a collective, none returns a frame that
+    differs from the single-GPU one.  Engines without the bookkeeping (the oracle of the CPU tests) are not asked."""
+    seen = getattr(engine, "degenerate", None)
+    if seen is None:
+        if refused is not None:
+            raise refused
+        return
+    import torch
+    from . import capi
+    flag = torch.tensor([1 if (refused is not None or seen()) else 0], dtype=torch.int64, device=engine.device)
+    dist.all_reduce(flag, op=dist.ReduceOp.SUM)
+    n = int(flag.item())
+    if refused is not None:
+        raise refused
+    if n:
+        raise capi.LentilError(capi._abi.ERR_UNSUPPORTED,
+                               "%d rank(s) met a sample with depth (Z) 0 or NaN competing for a closest-filtered AOV: its outcome depends "
+                               "on the order of every rank's samples at the pixel (src/lentil.h:832-845), which this exchange does not "
+                               "keep; the frame is refused on every rank (the library's own exchange replays such pixels: "
+                               "frame_step_native / frame_step_bands_native)" % n)
+
+
 def frame_step(engine, dist=None):
     """One redistribution pass over the rank's visits incl. the cross-rank merge and the resolve."""
     collective = dist is not None and dist.is_initialized() and (dist.get_world_size() > 1 or FORCE_COLLECTIVE)
@@ -186,8 +229,10 @@ def frame_step(engine, dist=None):
     if zkey is not None:
         engine.set_deferred_closest(collective)
     engine.clear()
-    engine.redistribute()
-    if collective:
+    if not collective:
+        engine.redistribute()
+    else:
+        degenerate_gate(engine, dist, _redistribute(engine))
         if hasattr(engine, "fold_direct"):
             engine.fold_direct()
         engine.finish_local()
@@ -327,7 +372,7 @@ def frame_step_bands(engine, dist, visit_rows, frame_rows, bounds=None):
         engine.set_deferred_closest(False)        # local winners are gathered by the pass; keys travel with the rows
     ph = _Phase()
     engine.clear()
-    engine.redistribute()
+    degenerate_gate(engine, dist, _redistribute(engine))
     ph.mark("enqueue pass")
     engine.finish_local()
     ph.mark("pass done")
