@@ -387,9 +387,25 @@ int lentil_hip_download_records(lentil_hip_ctx *ctx, float *host_records, uint64
  * order is the single-threaded one (visits in stream order, attempts in order) and the state is explicit:
  * it starts at the generator's initial constants, every lentil_hip_redistribute continues from where the
  * previous one stopped, and a host that wants another starting point (or to mirror draws it made itself)
- * reads / writes the four words x, y, z, w.  One GPU only. */
+ * reads / writes the four words x, y, z, w.
+ * Across GPUs (a communicator from lentil_hip_comm_init, either partition, world size 1 included) the order is the same
+ * one over the whole frame: items in frame-wide visit-id order, whichever rank holds them.  lentil_hip_redistribute is
+ * then a collective step -- every rank calls it, with visits of its own or none -- after which every rank's draws and
+ * channels are those a single context of the whole frame makes, and every rank's state is the WHOLE frame's last one, so
+ * the next pass continues as one GPU would.  Give every rank the same starting state.  Visit ids must be frame-wide and
+ * distinct: the two partitions derive them from pixel_y0 / pixel_row_stride; a ragged stream numbers its visits from
+ * visit_id_base (lentil_hip_set_closest_exchange), so give each rank the range its visits hold in the frame's order.  Items
+ * of two ranks with one id make every rank refuse the pass (LENTIL_ERR_INVALID).  As with the exchanges, an error a rank
+ * meets on its own before the ranks' lists are exchanged (work-list overflow, out of device memory) returns on that rank
+ * only and leaves the others waiting in the exchange: treat it as fatal to the communicator.  Without the library's
+ * communicator (lentil_hip_set_closest_exchange(ctx, 1, ...) alone) such a pass is refused.
+ * lentil_hip_tl_chroma_stats: for the last such pass, the frame's items (redistributed visits; without a communicator
+ * this context's), those whose generator use depends on the channels drawn (dependent_items: walked in order, the others
+ * in parallel; 0 without a communicator, where one block walks every item in order), and the payload bytes this rank
+ * received from the others.  Any pointer may be NULL.  Instrumentation. */
 int lentil_hip_set_xor128_state(lentil_hip_ctx *ctx, const uint32_t state[4]);
 int lentil_hip_get_xor128_state(lentil_hip_ctx *ctx, uint32_t state[4]);
+int lentil_hip_tl_chroma_stats(lentil_hip_ctx *ctx, uint64_t *items, uint64_t *dependent_items, uint64_t *gathered_bytes);
 
 /* Closest-filtered AOVs across GPUs (the reference's single z-buffer, src/lentil.h:832-837).
  * deferred != 0: lentil_hip_redistribute leaves the per-pixel winner keys -- (bits of |Z|) << 32 |
@@ -658,6 +674,9 @@ int lentil_hip_test_trace_bw_po(lentil_hip_ctx *ctx, uint64_t n, const double *t
                                 double *sensor_xy, int32_t *ok);
 int lentil_hip_test_aperture_sample(lentil_hip_ctx *ctx, uint64_t n, const uint32_t *a,
                                     const uint32_t *b, double *xy);
+/* Test hook: xor128 (src/global.h:22-27) advanced by k outputs with the jump-ahead the parallel thin-lens walk uses
+ * (products with T^(2^j), the generator's step matrix over GF(2)^128), run by one wave on the current device. */
+int lentil_hip_test_xor128_jump(const uint32_t in[4], uint64_t k, uint32_t out[4]);
 /* Test hook, needs no GPU.  The scan decides `get_coc_thinlens(z) < 0.4` (src/lentil.h:674-692,
  * src/lentil_filter.cpp:185-190) from the camera-space depth alone wherever that is certain; this returns the
  * intervals it would use for `params`: out[0..1] / out[2..3] lower / upper ends of the (at most two) closed depth

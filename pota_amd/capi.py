@@ -29,7 +29,7 @@ EXPORTS = [
     "lentil_hip_test_trace_bw_po", "lentil_hip_test_aperture_sample", "lentil_hip_debug_scan_bands",
     "lentil_hip_lens_is_compiled", "lentil_hip_set_lens_mode",
     "lentil_hip_focus_search", "lentil_hip_test_y0_intersection",
-    "lentil_hip_set_xor128_state", "lentil_hip_get_xor128_state",
+    "lentil_hip_set_xor128_state", "lentil_hip_get_xor128_state", "lentil_hip_tl_chroma_stats", "lentil_hip_test_xor128_jump",
     "lentil_hip_host_alloc", "lentil_hip_host_free", "lentil_hip_visits_begin", "lentil_hip_visits_append",
     "lentil_hip_visits_wait", "lentil_hip_visits_end",
     "lentil_hip_comm_unique_id", "lentil_hip_comm_init", "lentil_hip_comm_destroy", "lentil_hip_allreduce",
@@ -151,6 +151,8 @@ def load_library():
         "lentil_hip_focus_search": (i, [vp, C.c_double, C.c_double, C.POINTER(C.c_double)]),
         "lentil_hip_set_xor128_state": (i, [vp, C.POINTER(C.c_uint32)]),
         "lentil_hip_get_xor128_state": (i, [vp, C.POINTER(C.c_uint32)]),
+        "lentil_hip_tl_chroma_stats": (i, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
+        "lentil_hip_test_xor128_jump": (i, [C.POINTER(C.c_uint32), u64, C.POINTER(C.c_uint32)]),
         "lentil_hip_test_y0_intersection": (i, [vp, u64, vp, C.c_double, vp, vp, vp]),
         "lentil_hip_host_alloc": (i, [C.POINTER(vp), u64]),
         "lentil_hip_host_free": (i, [vp]),
@@ -385,6 +387,19 @@ class Context:
         st = (C.c_uint32 * 4)()
         self._chk(self.lib.lentil_hip_get_xor128_state(self.h, st))
         return list(st)
+
+    def tl_chroma_stats(self):
+        """(items, dependent items, bytes received from other ranks) of the last thin-lens abb_chromatic > 0 pass
+        (lentil_hip_tl_chroma_stats)"""
+        n = [C.c_uint64() for _ in range(3)]
+        self._chk(self.lib.lentil_hip_tl_chroma_stats(self.h, *[C.byref(x) for x in n]))
+        return tuple(int(x.value) for x in n)
+
+    def test_xor128_jump(self, state, k):
+        """xor128 state advanced by k outputs, by the device jump-ahead (lentil_hip_test_xor128_jump)"""
+        out = (C.c_uint32 * 4)()
+        self._chk(self.lib.lentil_hip_test_xor128_jump((C.c_uint32 * 4)(*[int(x) for x in state]), int(k), out))
+        return list(out)
 
     def focus_search(self, focal_distance, lam):
         best = C.c_double()

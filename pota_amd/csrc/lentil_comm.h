@@ -383,6 +383,157 @@ static int degenerate_exchange(lentil_hip_ctx *ctx, LentilComm *cm, const int32_
   return LENTIL_OK;
 }
 
+// ---- thin lens with abb_chromatic > 0 across GPUs (lentil_tl_chroma_mgpu.h) ----------------------------------------------
+// Called inside lentil_hip_redistribute on every rank -- the pass is the collective step here, not the exchange behind it.
+// Every rank's items in frame-wide visit order go to every rank as (visit id, D | kTlcDependent) pairs, then the dependent
+// items' signatures; every rank merges the lists and runs the same chain over them (the same anchors everywhere), walks its
+// own items from them and ends at the whole frame's last generator state.  Scratch slots behind those of the closest-AOV
+// replay.
+static size_t tlc_slot(const LentilComm *cm, size_t k) { return deg_slot(cm, 8 + k); }
+
+static int tl_chroma_across_ranks(lentil_hip_ctx *ctx, TlChromaArgs &ta, const std::vector<uint32_t> &gids) {
+  LentilComm *cm = ctx->comm;
+  const int world = cm->world, rank = cm->rank;
+  const uint32_t n = ta.n_items;
+  int rc;
+  void *p;
+  TlChromaPar q{};
+  q.jump = ctx->d_xor_jump;
+  q.val = ctx->d_tlc_val;
+  const dim3 grid(tl_chroma_item_blocks(ctx, n)), block(256);
+  if (n) hipLaunchKernelGGL(tl_chroma_count_kernel, grid, block, 0, ctx->stream, ta, q);
+  HIP_TRY(ctx, hipGetLastError());
+  std::vector<uint64_t> val(n);
+  if (n) HIP_TRY(ctx, hipMemcpyAsync(val.data(), ctx->d_tlc_val, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  auto sig_words = [](uint64_t v) -> uint64_t { return ((v & 0xFFFFFFFFull) + 7) / 8; };
+  // ---- 1. this rank's list to every rank (own first, then the others' in rank order)
+  const uint64_t list_bytes = (uint64_t)n * 16;
+  std::vector<uint64_t> mine(2 * (size_t)n);
+  std::vector<uint64_t> sig_off(n, kTlcNoSig);
+  uint64_t my_words = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    mine[2 * (size_t)i] = gids[i];
+    mine[2 * (size_t)i + 1] = val[i];
+    if (val[i] & kTlcDependent) { sig_off[i] = my_words; my_words += sig_words(val[i]); }
+  }
+  if ((rc = comm_scratch(ctx, cm, tlc_slot(cm, 0), (size_t)list_bytes + 16, &p))) return rc;
+  const uint8_t *d_mine = (const uint8_t *)p;
+  if (n) HIP_TRY(ctx, hipMemcpyAsync(p, mine.data(), (size_t)list_bytes, hipMemcpyHostToDevice, ctx->stream));
+  std::vector<const uint8_t *> out((size_t)world, d_mine);
+  std::vector<uint64_t> n_out((size_t)world, list_bytes), n_in;
+  uint8_t *got = nullptr;
+  if ((rc = deg_alltoall(ctx, cm, out, n_out, tlc_slot(cm, 1), list_bytes, &got, n_in))) return rc;
+  if (n) HIP_TRY(ctx, hipMemcpyAsync(got, d_mine, (size_t)list_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  uint64_t total_bytes = list_bytes, received = 0;
+  for (int r = 0; r < world; ++r) { if (n_in[(size_t)r] % 16) return fail(ctx, LENTIL_ERR_HIP, "thin-lens abb_chromatic > 0 across GPUs: a torn list"); total_bytes += n_in[(size_t)r]; received += n_in[(size_t)r]; }
+  std::vector<uint64_t> all_lists(total_bytes / 8);
+  if (total_bytes) HIP_TRY(ctx, hipMemcpyAsync(all_lists.data(), got, (size_t)total_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  // ---- 2. the merged list: every entry's rank, index there, and (dependent) the word of its signature in the gathered block,
+  // which holds this rank's signatures first, then the others' in rank order
+  struct Entry { uint32_t gid; int rank; uint32_t local; uint64_t val, sig; };
+  std::vector<Entry> all;
+  all.reserve(total_bytes / 16);
+  uint64_t pos = 0, sig_base = 0, n_dep = 0;
+  for (int k = 0; k < world; ++k) {
+    const int r = k == 0 ? rank : (k <= rank ? k - 1 : k);      // (rank order of the blocks behind this rank's own)
+    const uint64_t cnt = (r == rank ? list_bytes : n_in[(size_t)r]) / 16;
+    for (uint64_t i = 0; i < cnt; ++i, ++pos) {
+      const uint64_t v = all_lists[2 * pos + 1];
+      Entry e{(uint32_t)all_lists[2 * pos], r, (uint32_t)i, v, kTlcNoSig};
+      if (v & kTlcDependent) { e.sig = sig_base; sig_base += sig_words(v); ++n_dep; }
+      all.push_back(e);
+    }
+  }
+  std::stable_sort(all.begin(), all.end(), [](const Entry &a, const Entry &b) { return a.gid < b.gid; });
+  // The order is the visit ids' own: two items with one id have none (and this rank's block comes first in its own merge, so
+  // the ranks would break the tie differently).  Every rank holds the same merged list and refuses it alike -- before any
+  // other collective of the pass.
+  for (size_t i = 1; i < all.size(); ++i)
+    if (all[i].gid == all[i - 1].gid)
+      return fail(ctx, LENTIL_ERR_INVALID, "thin-lens abb_chromatic > 0 across GPUs: items of two ranks carry the same frame-wide visit id "
+                                           "(a ragged stream numbers its visits from visit_id_base: give every rank its own range, "
+                                           "lentil_hip_set_closest_exchange)");
+  if (n_dep > 0xFFFFFFF0ull) return fail(ctx, LENTIL_ERR_NOMEM, "thin-lens abb_chromatic > 0 across GPUs: too many dependent items");
+  // ---- 3. the dependent items' signatures to every rank (no step at all when no rank has one: every rank knows that now)
+  uint32_t *d_sig_all = nullptr;
+  if (n_dep) {
+    if ((rc = comm_scratch(ctx, cm, tlc_slot(cm, 2), (size_t)n * 8 + 8, &p))) return rc;
+    q.sig_off = (const uint64_t *)p;
+    if (n) HIP_TRY(ctx, hipMemcpyAsync(p, sig_off.data(), (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = comm_scratch(ctx, cm, tlc_slot(cm, 3), (size_t)my_words * 4 + 4, &p))) return rc;
+    q.sig = (uint32_t *)p;
+    if (my_words) hipLaunchKernelGGL(tl_chroma_sig_kernel, grid, block, 0, ctx->stream, ta, q);
+    HIP_TRY(ctx, hipGetLastError());
+    std::vector<const uint8_t *> sout((size_t)world, (const uint8_t *)q.sig);
+    std::vector<uint64_t> sn_out((size_t)world, my_words * 4), sn_in;
+    uint8_t *sgot = nullptr;
+    if ((rc = deg_alltoall(ctx, cm, sout, sn_out, tlc_slot(cm, 4), my_words * 4, &sgot, sn_in))) return rc;
+    if (my_words) HIP_TRY(ctx, hipMemcpyAsync(sgot, q.sig, (size_t)my_words * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    uint64_t s_total = my_words * 4;
+    for (uint64_t b : sn_in) { s_total += b; received += b; }
+    if (s_total != sig_base * 4) return fail(ctx, LENTIL_ERR_HIP, "thin-lens abb_chromatic > 0 across GPUs: signatures and lists disagree");
+    d_sig_all = (uint32_t *)sgot;
+  }
+  // ---- 4. the chain's inputs, and every own item's anchor and offset
+  std::vector<uint64_t> skip, dsig;
+  std::vector<uint32_t> dslots, base_idx(n);
+  std::vector<uint64_t> offset(n);
+  skip.reserve(n_dep + 1); dsig.reserve(n_dep); dslots.reserve(n_dep);
+  uint32_t cur_anchor = 0;
+  uint64_t cur_off = 0;
+  for (const Entry &e : all) {
+    if (e.rank == rank) { base_idx[e.local] = cur_anchor; offset[e.local] = cur_off; }
+    if (e.val & kTlcDependent) {
+      skip.push_back(cur_off); dsig.push_back(e.sig); dslots.push_back((uint32_t)(e.val & 0xFFFFFFFFull));
+      ++cur_anchor;
+      cur_off = 0;
+    } else {
+      cur_off += e.val;
+    }
+  }
+  skip.push_back(cur_off);
+  // one block: anchors [n_dep + 1] uint4, skip [n_dep + 1], signature offsets [n_dep], slots [n_dep], own items' anchors / offsets
+  const size_t b_anchor = 0, b_skip = b_anchor + (n_dep + 1) * 16, b_dsig = b_skip + (n_dep + 1) * 8, b_base = b_dsig + n_dep * 8,
+               b_offset = b_base + ((size_t)n * 8 + 8), b_slots = b_offset + (size_t)n * 8, b_end = b_slots + n_dep * 4 + 4;
+  if ((rc = comm_scratch(ctx, cm, tlc_slot(cm, 5), b_end, &p))) return rc;
+  uint8_t *blk = (uint8_t *)p;
+  std::vector<uint8_t> h(b_end, 0);
+  memcpy(h.data() + b_anchor, ctx->xor_state, 16);
+  memcpy(h.data() + b_skip, skip.data(), skip.size() * 8);
+  if (n_dep) memcpy(h.data() + b_dsig, dsig.data(), n_dep * 8);
+  if (n) { memcpy(h.data() + b_base, base_idx.data(), (size_t)n * 4); memcpy(h.data() + b_offset, offset.data(), (size_t)n * 8); }
+  if (n_dep) memcpy(h.data() + b_slots, dslots.data(), n_dep * 4);
+  HIP_TRY(ctx, hipMemcpyAsync(blk, h.data(), b_end, hipMemcpyHostToDevice, ctx->stream));
+  TlChainArgs c{};
+  c.jump = ctx->d_xor_jump;
+  c.anchor = (uint4 *)(blk + b_anchor);
+  c.n_dep = (uint32_t)n_dep;
+  c.skip = (const uint64_t *)(blk + b_skip);
+  c.sig_off = (const uint64_t *)(blk + b_dsig);
+  c.slots = (const uint32_t *)(blk + b_slots);
+  c.sig = d_sig_all;
+  c.final_state = ctx->d_xor;
+  hipLaunchKernelGGL(tl_chroma_chain_kernel, dim3(1), dim3(64), 0, ctx->stream, c);
+  HIP_TRY(ctx, hipGetLastError());
+  // ---- 5. this rank's items, in parallel, from their anchors; the frame's last state for the next pass
+  if (n) {
+    q.base = c.anchor;
+    q.base_idx = (const uint32_t *)(blk + b_base);
+    q.offset = (const uint64_t *)(blk + b_offset);
+    q.entry_out = ctx->d_tlc_entry;
+    hipLaunchKernelGGL(tl_chroma_walk_par_kernel, grid, block, 0, ctx->stream, ta, q);
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->xor_state, ctx->d_xor, sizeof ctx->xor_state, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      // (h and the vectors above are the copies' sources)
+  ctx->tlc_items = all.size();
+  ctx->tlc_dependent = n_dep;
+  ctx->tlc_gathered = received;
+  return LENTIL_OK;
+}
+
 // interleaved partition: every rank ends up with the whole frame's accumulators (distributed.frame_step)
 LENTIL_API int lentil_hip_allreduce(lentil_hip_ctx *ctx) {
   CHECK_CTX(ctx);

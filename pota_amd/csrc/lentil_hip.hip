@@ -17,6 +17,7 @@
 
 #include "lentil_kernels.h"
 #include "lentil_closest_replay.h"
+#include "lentil_tl_chroma_mgpu.h"
 #include "lentil_lens_jit.h"
 #include "generated/embedded_sources.inc"
 
@@ -278,6 +279,15 @@ struct lentil_hip_ctx {
   uint64_t *d_tlc_off = nullptr;
   uint2 *d_tlc_tasks = nullptr;
   uint64_t tlc_res_cap = 0, tlc_off_cap = 0, tlc_tasks_cap = 0;
+  // ... with a communicator (lentil_tl_chroma_mgpu.h): the jump tables, every item's D, and the entry state each item of the
+  // last pass walked from -- with the frame-wide visit ids of those items, in walk order -- so that a rank can re-run that
+  // pass on its own (closest_rerun_with_log) without another collective
+  uint4 *d_xor_jump = nullptr, *d_tlc_entry = nullptr;
+  uint64_t *d_tlc_val = nullptr;
+  uint64_t tlc_entry_cap = 0, tlc_val_cap = 0;
+  std::vector<uint32_t> tlc_gids;
+  bool tlc_have_entries = false, tlc_rewalk = false;
+  uint64_t tlc_items = 0, tlc_dependent = 0, tlc_gathered = 0;     // lentil_hip_tl_chroma_stats
   double lens_housing_radius = 0.0;  // lens_aperture_housing_radius of the current table (focus search)
   float4 *d_dummy = nullptr;          // ScanArgs::dummy
   float *d_cam_keys = nullptr;        // lentil_hip_set_camera_motion
@@ -831,6 +841,7 @@ LENTIL_API int lentil_hip_destroy(lentil_hip_ctx *ctx) {
   (void)hipFree(ctx->d_bm_land); (void)hipFree(ctx->d_bm_box); (void)hipFree(ctx->d_bm_npass);
   (void)hipFree(ctx->d_ext_q);
   (void)hipFree(ctx->d_xor); (void)hipFree(ctx->d_tlc_res); (void)hipFree(ctx->d_tlc_off); (void)hipFree(ctx->d_tlc_tasks);
+  (void)hipFree(ctx->d_xor_jump); (void)hipFree(ctx->d_tlc_entry); (void)hipFree(ctx->d_tlc_val);
   (void)hipFree(ctx->d_log);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);       // (ctx->ev[]: one of the slots' sets, destroyed with them above)
   delete ctx;
@@ -3291,30 +3302,81 @@ static int redistribute_streamed(lentil_hip_ctx *ctx, bool *streamed, bool *defe
   return streamed_finish(ctx, t, ctx->h_ctr_pinned, true, streamed);
 }
 
+// Frame-wide visit id on the host: visit_gid (lentil_kernels.h) for the work list's order across ranks.
+static uint32_t host_visit_gid(const VisitsDev &V, uint32_t v) {
+  if (V.visits_per_pixel == 0 || V.pixel_y0 < 0) return V.id_base + v;
+  const uint32_t row_visits = V.pixels_per_row * V.visits_per_pixel;
+  const uint32_t ly = v / row_visits;
+  return ((uint32_t)V.pixel_y0 + ly * V.pixel_row_stride) * row_visits + (v - ly * row_visits);
+}
+
+// The jump tables on the context's device (lentil_tl_chroma_mgpu.h), uploaded once.
+static int ensure_xor_jump(lentil_hip_ctx *ctx) {
+  if (ctx->d_xor_jump) return LENTIL_OK;
+  HIP_TRY(ctx, hipMalloc(&ctx->d_xor_jump, kXorJumpBytes));
+  HIP_TRY(ctx, hipMemcpy(ctx->d_xor_jump, xor128_jump_rows().data(), kXorJumpBytes, hipMemcpyHostToDevice));
+  return LENTIL_OK;
+}
+
+static unsigned tl_chroma_item_blocks(const lentil_hip_ctx *ctx, uint32_t n_items) {      // (one wave per item, four per block)
+  uint64_t blocks = ((uint64_t)n_items + 3) / 4;
+  const uint64_t max_blocks = (uint64_t)ctx->num_cu * 8;
+  if (blocks > max_blocks) blocks = max_blocks;
+  return (unsigned)(blocks ? blocks : 1);
+}
+
+static int tl_chroma_across_ranks(lentil_hip_ctx *ctx, TlChromaArgs &ta, const std::vector<uint32_t> &gids);      // lentil_comm.h
+
 // Thin lens with abb_chromatic > 0 (kernels: tl_chroma_*): scan, the work list put into visit order on the host, every
-// possible attempt's channel-independent part solved in parallel, then one block walks the items in order.
+// possible attempt's channel-independent part solved in parallel, then the walk in visit order.  Without a communicator one
+// block walks the items one after the other.  With one (lentil_tl_chroma_mgpu.h) the items are ordered by frame-wide visit
+// id, and every rank walks its own in parallel from the states the whole frame's order gives them: a collective step on
+// every rank, with or without visits of its own (tl_chroma_across_ranks).  A rank that re-runs the pass on its own
+// (closest_rerun_with_log: tlc_rewalk) walks its items again from the entry states the first run kept.
 static int redistribute_tl_chroma(lentil_hip_ctx *ctx) {
-  if (ctx->comm || ctx->closest_deferred)
-    return fail(ctx, LENTIL_ERR_UNSUPPORTED, "thin-lens abb_chromatic > 0: the order of the xor128 draws is defined for one GPU only");
-  ScanPlan plan;
-  int rc = plan_scan(ctx, plan);
-  if (rc) return rc;
-  lentil_hip_ctx::Chunk &ch = ctx->chunks[0];
-  ch.tile_begin = 0; ch.tile_end = plan.n_tiles;
-  ch.v_begin = 0; ch.v_end = ctx->V.n;
-  if ((rc = launch_scan(ctx, plan, ch, ctx->d_ctr, nullptr))) return rc;
-  ++ctx->last_scan_launches;
-  HIP_TRY(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-  HIP_TRY(ctx, hipEventRecord(ctx->scans_done, ctx->stream));
-  DevCounters c0;
-  HIP_TRY(ctx, hipMemcpyAsync(&c0, ctx->d_ctr, sizeof(c0), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  if (c0.work_count > ctx->V.n) return fail(ctx, LENTIL_ERR_NOMEM, "work list overflow");
-  const uint32_t n_items = (uint32_t)c0.work_count;
-  if (!n_items) return LENTIL_OK;
+  if (!ctx->comm && ctx->closest_deferred && ctx->V.n)
+    return fail(ctx, LENTIL_ERR_UNSUPPORTED, "thin-lens abb_chromatic > 0: the order of the xor128 draws across GPUs is kept by the "
+                                             "library's communicator only (lentil_hip_comm_init)");
+  const bool rewalk = ctx->tlc_rewalk;
+  if (!rewalk) ctx->tlc_items = ctx->tlc_dependent = ctx->tlc_gathered = 0;
+  int rc;
+  uint32_t n_items = 0;
+  if (ctx->V.n) {
+    ScanPlan plan;
+    if ((rc = plan_scan(ctx, plan))) return rc;
+    lentil_hip_ctx::Chunk &ch = ctx->chunks[0];
+    ch.tile_begin = 0; ch.tile_end = plan.n_tiles;
+    ch.v_begin = 0; ch.v_end = ctx->V.n;
+    if ((rc = launch_scan(ctx, plan, ch, ctx->d_ctr, nullptr))) return rc;
+    ++ctx->last_scan_launches;
+    HIP_TRY(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->scans_done, ctx->stream));
+    DevCounters c0;
+    HIP_TRY(ctx, hipMemcpyAsync(&c0, ctx->d_ctr, sizeof(c0), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (c0.work_count > ctx->V.n) return fail(ctx, LENTIL_ERR_NOMEM, "work list overflow");
+    n_items = (uint32_t)c0.work_count;
+  } else {
+    HIP_TRY(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->scans_done, ctx->stream));
+  }
+  if (!ctx->comm) ctx->tlc_items = n_items;
+  if (!n_items && (!ctx->comm || rewalk)) return LENTIL_OK;
   std::vector<uint2> work(n_items);
-  HIP_TRY(ctx, hipMemcpy(work.data(), ctx->d_work, (size_t)n_items * sizeof(uint2), hipMemcpyDeviceToHost));
-  std::sort(work.begin(), work.end(), [](const uint2 &a, const uint2 &b) { return a.x < b.x; });      // iterator order
+  std::vector<uint32_t> gids;
+  if (n_items) HIP_TRY(ctx, hipMemcpy(work.data(), ctx->d_work, (size_t)n_items * sizeof(uint2), hipMemcpyDeviceToHost));
+  if (ctx->comm) {
+    // frame-wide visit order: the order the ranks agree on
+    std::vector<std::pair<uint32_t, uint2>> keyed(n_items);
+    for (uint32_t i = 0; i < n_items; ++i) keyed[i] = {host_visit_gid(ctx->V, work[i].x), work[i]};
+    std::sort(keyed.begin(), keyed.end(), [](const std::pair<uint32_t, uint2> &a, const std::pair<uint32_t, uint2> &b) { return a.first < b.first; });
+    gids.resize(n_items);
+    for (uint32_t i = 0; i < n_items; ++i) { gids[i] = keyed[i].first; work[i] = keyed[i].second; }
+  } else {
+    std::sort(work.begin(), work.end(), [](const uint2 &a, const uint2 &b) { return a.x < b.x; });      // iterator order
+  }
+  if (rewalk && (!ctx->tlc_have_entries || gids != ctx->tlc_gids))
+    return fail(ctx, LENTIL_ERR_INVALID, "thin-lens abb_chromatic > 0: the pass run again found other items than its first run");
   std::vector<uint64_t> off((size_t)n_items + 1);
   std::vector<uint2> tasks;
   uint64_t slots = 0;
@@ -3338,10 +3400,17 @@ static int redistribute_tl_chroma(lentil_hip_ctx *ctx) {
   if ((rc = grow_to(&ctx->d_tlc_res, ctx->tlc_res_cap, slots * 3ull + 4ull))) return rc;
   if ((rc = grow_to(&ctx->d_tlc_off, ctx->tlc_off_cap, (uint64_t)n_items + 1))) return rc;
   if ((rc = grow_to(&ctx->d_tlc_tasks, ctx->tlc_tasks_cap, (uint64_t)tasks.size() + 1))) return rc;
+  if (ctx->comm) {
+    if ((rc = grow_to(&ctx->d_tlc_val, ctx->tlc_val_cap, (uint64_t)n_items + 1))) return rc;
+    if ((rc = grow_to(&ctx->d_tlc_entry, ctx->tlc_entry_cap, (uint64_t)n_items + 1))) return rc;
+    if ((rc = ensure_xor_jump(ctx))) return rc;
+  }
   if (!ctx->d_xor) HIP_TRY(ctx, hipMalloc(&ctx->d_xor, 4 * sizeof(uint32_t)));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_work, work.data(), (size_t)n_items * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tlc_off, off.data(), off.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tlc_tasks, tasks.data(), tasks.size() * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream));
+  if (n_items) {
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_work, work.data(), (size_t)n_items * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tlc_off, off.data(), off.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tlc_tasks, tasks.data(), tasks.size() * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream));
+  }
   HIP_TRY(ctx, hipMemcpyAsync(ctx->d_xor, ctx->xor_state, sizeof ctx->xor_state, hipMemcpyHostToDevice, ctx->stream));
   TlChromaArgs ta{};
   ta.P = ctx->P; ta.bokeh = ctx->bokeh; ta.V = ctx->V; ta.F = ctx->F;
@@ -3351,16 +3420,57 @@ static int redistribute_tl_chroma(lentil_hip_ctx *ctx) {
   ta.xor_state = ctx->d_xor;
   ta.ctr = ctx->d_ctr;
   ta.log = ctx->d_log; ta.log_cap = ctx->log_cap; ta.log_count = &ctx->d_ctr[ctx->n_chunks].log_count;
-  uint64_t blocks = tasks.size();
-  const uint64_t max_blocks = (uint64_t)ctx->num_cu * 8;
-  if (blocks > max_blocks) blocks = max_blocks;
-  hipLaunchKernelGGL(tl_chroma_solve_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, ta);
-  HIP_TRY(ctx, hipGetLastError());
-  hipLaunchKernelGGL(tl_chroma_walk_kernel, dim3(1), dim3(256), 0, ctx->stream, ta);
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->xor_state, ctx->d_xor, sizeof ctx->xor_state, hipMemcpyDeviceToHost, ctx->stream));
+  if (n_items) {
+    uint64_t blocks = tasks.size();
+    const uint64_t max_blocks = (uint64_t)ctx->num_cu * 8;
+    if (blocks > max_blocks) blocks = max_blocks;
+    hipLaunchKernelGGL(tl_chroma_solve_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, ta);
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  if (!ctx->comm) {
+    hipLaunchKernelGGL(tl_chroma_walk_kernel, dim3(1), dim3(256), 0, ctx->stream, ta);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->xor_state, ctx->d_xor, sizeof ctx->xor_state, hipMemcpyDeviceToHost, ctx->stream));
+  } else if (rewalk) {
+    // (ctx->xor_state stays the frame's last state, as the first run left it)
+    TlChromaPar q{};
+    q.jump = ctx->d_xor_jump; q.base = ctx->d_tlc_entry;
+    hipLaunchKernelGGL(tl_chroma_walk_par_kernel, dim3(tl_chroma_item_blocks(ctx, n_items)), dim3(256), 0, ctx->stream, ta, q);
+    HIP_TRY(ctx, hipGetLastError());
+  } else {
+    ctx->tlc_have_entries = false;
+    if ((rc = tl_chroma_across_ranks(ctx, ta, gids))) return rc;
+    ctx->tlc_gids.swap(gids);
+    ctx->tlc_have_entries = true;
+  }
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      // (the host vectors above are the copies' sources)
   ctx->last_rounds = 1;
+  return LENTIL_OK;
+}
+
+LENTIL_API int lentil_hip_tl_chroma_stats(lentil_hip_ctx *ctx, uint64_t *items, uint64_t *dependent_items, uint64_t *gathered_bytes) {
+  CHECK_CTX(ctx);
+  if (items) *items = ctx->tlc_items;
+  if (dependent_items) *dependent_items = ctx->tlc_dependent;
+  if (gathered_bytes) *gathered_bytes = ctx->tlc_gathered;
+  return LENTIL_OK;
+}
+
+// xor128_jump on the current device, one wave: `in` advanced by k outputs.
+LENTIL_API int lentil_hip_test_xor128_jump(const uint32_t in[4], uint64_t k, uint32_t out[4]) {
+  if (!in || !out) return fail(nullptr, LENTIL_ERR_INVALID, "state is null");
+  uint4 *tab = nullptr, *st = nullptr;
+  hipError_t e = hipMalloc(&tab, kXorJumpBytes);
+  if (e == hipSuccess) e = hipMalloc(&st, sizeof(uint4));
+  if (e == hipSuccess) e = hipMemcpy(tab, xor128_jump_rows().data(), kXorJumpBytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(st, in, sizeof(uint4), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(xor128_jump_test_kernel, dim3(1), dim3(64), 0, 0, (const uint4 *)tab, st, k);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(out, st, sizeof(uint4), hipMemcpyDeviceToHost);
+  (void)hipFree(tab); (void)hipFree(st);
+  if (e != hipSuccess) return fail(nullptr, LENTIL_ERR_HIP, std::string("test_xor128_jump: ") + hipGetErrorString(e));
   return LENTIL_OK;
 }
 
@@ -3415,7 +3525,12 @@ static int closest_rerun_with_log(lentil_hip_ctx *ctx, const uint32_t *xor_entry
   if ((rc = lentil_hip_clear_frame(ctx))) return rc;
   ctx->degenerate_seen = false;
   if (xor_entry) memcpy(ctx->xor_state, xor_entry, sizeof ctx->xor_state);      // (thin lens, abb_chromatic > 0: the same colour channels as the first run)
-  if ((rc = redistribute_impl(ctx))) return rc;
+  // (with a communicator the run is this rank's alone: thin lens, abb_chromatic > 0 walks its items again from the entry
+  // states the first run kept, and starts no collective -- the other ranks are not running the pass)
+  ctx->tlc_rewalk = ctx->comm != nullptr;
+  rc = redistribute_impl(ctx);
+  ctx->tlc_rewalk = false;
+  if (rc) return rc;
   // (counters and timing describe the second run; that there were two is reported like any pass that was redone)
   ++ctx->last_fallback;
   ++ctx->deg_passes_rerun;
@@ -3755,8 +3870,7 @@ static int redistribute_pass(lentil_hip_ctx *ctx) {
   const bool tl_chroma = P.cameraType == LENTIL_THINLENS && P.abb_chromatic > 0.0f;
   if (tl_chroma) {
     { const int rc = join_clear(ctx); if (rc) return rc; }
-    if (ctx->V.n) { const int rc = redistribute_tl_chroma(ctx); if (rc) return rc; }
-    else { HIP_TRY(ctx, hipEventRecord(ctx->ev[1], ctx->stream)); HIP_TRY(ctx, hipEventRecord(ctx->scans_done, ctx->stream)); }
+    { const int rc = redistribute_tl_chroma(ctx); if (rc) return rc; }      // (with a communicator: on every rank, visits or not)
     streamed = true;          // (nothing of the chunked form below runs)
   } else {
     const int rc = redistribute_streamed(ctx, &streamed, &deferred);

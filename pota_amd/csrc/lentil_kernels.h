@@ -4412,7 +4412,14 @@ __global__ __launch_bounds__(256) void probe_apply_kernel(DrawArgs a, ProbeArgs 
 //                            make (n < 5 * samples): vignetted?, and the outcome for each of the three channels.
 //   tl_chroma_walk_kernel  : ONE block walks the items in visit order, 256 attempts per step: prefix count of the
 //                            survivors = each attempt's index into the generator's output, channel, outcome, ordered
-//                            acceptance, splat.  Sequential in the items by construction (~15 us per item).
+//                            acceptance, splat.  Sequential in the items by construction (DESIGN.md 4.2 has the
+//                            measured cost per item).  A context without a communicator walks this way.
+// With a communicator the items are walked in parallel instead, from entry states the generator's linearity gives
+// (lentil_tl_chroma_mgpu.h).  Both walks share the per-attempt pieces below (tl_chroma_channel, tl_chroma_accept_wave).
+// The step's bookkeeping -- each attempt's index into the generator's outputs, ordered acceptance up to `samples`, the
+// state after the outputs the made attempts consumed -- exists twice: block-wide (256 attempts) here, wave-wide (64) in
+// tl_chroma_wave_step.  A change to one is a change to the other; test_native_exchange_tl_chroma.py compares the two walks
+// draw for draw (and tl_chroma_walk_kernel is pinned to the oracle by test_thinlens_chromatic_aberration).
 // ---------------------------------------------------------------------------------------
 struct TlChromaArgs {
   lentil_params P;
@@ -4464,6 +4471,83 @@ LD_DEV uint32_t xor128_next(uint32_t &x, uint32_t &y, uint32_t &z, uint32_t &w) 
   return w = (w ^ (w >> 19) ^ t ^ (t >> 8));
 }
 
+// the colour channel an xor128 output picks: -1 / 0 / +1 (src/lentil_filter.cpp:397)
+LD_DEV int tl_chroma_channel(uint32_t x) { return (int)floor(((double)x / 4294967296.0) * 3.0) - 1; }
+
+// Orders a wave's own LDS accesses (the walks' per-wave pixel lists): the lanes of one wave, nothing else waited for.
+LD_DEV void wave_sync_lds() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// What an accepted draw of the item adds (gaussian AOVs: (value + add_energy) * w per component, then the weight itself):
+// the thread t < 4 n_aovs of the caller writes float t of the list, t == 0 the weight.  Returns the list's length U.
+LD_DEV uint32_t tl_chroma_item_values(const TlChromaArgs &a, const ItemVisit &h, uint32_t t, float *s_val, uint32_t *s_off) {
+  const float ae = h.I.add_energy, w = h.w;
+  uint32_t U = 1;
+  for (uint32_t k = 0; k < a.F.n_aovs; ++k) if (!(a.F.closest_mask & (1u << k))) U += 4;
+  if (t < a.F.n_aovs * 4u) {
+    const uint32_t k = t >> 2, c = t & 3u;
+    if (!(a.F.closest_mask & (1u << k))) {
+      uint32_t slot = 0;
+      for (uint32_t j = 0; j < k; ++j) if (!(a.F.closest_mask & (1u << j))) slot += 4;
+      const float4 v = k == 0 ? h.rgba : a.V.extra[k - 1][h.visit];
+      const float vc = c == 0 ? v.x : (c == 1 ? v.y : (c == 2 ? v.z : v.w));
+      s_val[slot + c] = (vc + ae) * w;
+      s_off[slot + c] = 4u * k + c;
+    }
+  }
+  if (t == 0) { s_val[U - 1] = w; s_off[U - 1] = 4u * a.F.n_aovs; }
+  return U;
+}
+
+// The accepted draws of one wave's 64 attempts (take: this lane's attempt my_n is accepted, on `pix`, with `channel`): row
+// range, touched flags, closest keys, draw-log records (the channel in the attempt's top bits), then the splat -- draws of
+// the same pixel and channel as one atomic of count x value; channel c feeds colour component c only, three-fold, alpha
+// and weight as they are.  s_pix .. s_key: this wave's own 64 entries.  Called by the whole wave.
+LD_DEV void tl_chroma_accept_wave(const TlChromaArgs &a, uint32_t visit, unsigned long long zk, bool take, uint32_t pix, int channel,
+                                  uint32_t my_n, uint32_t lane, uint32_t *s_pix, uint32_t *s_same, uint32_t *s_ch, uint32_t *s_key,
+                                  const float *s_val, const uint32_t *s_off, uint32_t U, uint32_t &rmin, uint32_t &rmax_p1) {
+  const unsigned long long lt_mask = (1ull << lane) - 1ull;
+  const unsigned long long tm = __ballot(take);
+  const uint32_t T = (uint32_t)__builtin_popcountll(tm);
+  wave_sync_lds();                 // (the wave's previous step has read its lists)
+  if (take) {
+    const uint32_t row = pix / a.P.xres;
+    rmin = row < rmin ? row : rmin;
+    rmax_p1 = row + 1u > rmax_p1 ? row + 1u : rmax_p1;
+    const uint32_t slot = (uint32_t)__builtin_popcountll(tm & lt_mask);
+    s_pix[slot] = pix;
+    s_ch[slot] = (uint32_t)(channel + 1);
+    s_key[slot] = (pix << 2) | (uint32_t)(channel + 1);       // (frames of up to 2^30 pixels)
+    if (a.F.touched) { a.F.touched[pix >> 6] = 1; a.F.touched_px[pix] = 1; }
+    if (a.F.zkey) atomicMin(a.F.zkey + pix, zk);
+    if (a.F.zkey_dbg) atomicMin(a.F.zkey_dbg + pix, zk);
+    if (a.log_cap) {
+      const unsigned long long li = wave_log_slots(a.log_count, tm, lane);
+      if (li < a.log_cap) { a.log[li].visit = visit; a.log[li].attempt = my_n | ((uint32_t)(channel + 1) << 30); a.log[li].pixel = pix; }
+    }
+  }
+  wave_sync_lds();
+  count_same_pixel(s_key, s_same, T, lane);
+  wave_sync_lds();
+  for (uint32_t q = lane; q < T * U; q += 64u) {
+    const uint32_t d = q / U, ch = q - d * U;
+    const uint32_t same = s_same[d];
+    if (!same) continue;
+    float val = s_val[ch];
+    if (ch != U - 1u) {
+      const uint32_t comp = s_off[ch] & 3u;
+      if (comp < 3u) {
+        if (comp != s_ch[d]) continue;          // rgb_weight is 0 there
+        val = val * 3.0f;
+      }
+    }
+    atomicAdd(a.F.acc + (size_t)s_pix[d] * a.F.stride + s_off[ch], (float)same * val);
+  }
+}
+
 __global__ __launch_bounds__(256) void tl_chroma_walk_kernel(TlChromaArgs a) {
   __shared__ uint32_t s_x[256];            // the step's generator outputs, in order
   __shared__ uint32_t s_state[256][4];     // generator state after each of them
@@ -4480,25 +4564,10 @@ __global__ __launch_bounds__(256) void tl_chroma_walk_kernel(TlChromaArgs a) {
   for (uint32_t item = 0; item < a.n_items; ++item) {
     const ItemVisit h = load_work_visit(a.P, a.V, a.work[item], 0.0);
     const uint32_t S = h.samples, max_total = S * 5u;
-    const float ae = h.I.add_energy, w = h.w;
     const unsigned long long zk = (a.F.zkey || a.F.zkey_dbg) ? closest_key_of(a.ctr, h.I.depth, visit_gid(a.V, h.visit)) : 0ull;
     const uint32_t *res = a.res + a.att_off[item] * 3ull;
-    // what an accepted draw adds (gaussian AOVs: (value + add_energy) * w per component, then the weight itself)
-    uint32_t U = 1;
-    for (uint32_t k = 0; k < a.F.n_aovs; ++k) if (!(a.F.closest_mask & (1u << k))) U += 4;
     __syncthreads();
-    if (threadIdx.x < a.F.n_aovs * 4u) {
-      const uint32_t k = threadIdx.x >> 2, c = threadIdx.x & 3u;
-      if (!(a.F.closest_mask & (1u << k))) {
-        uint32_t slot = 0;
-        for (uint32_t j = 0; j < k; ++j) if (!(a.F.closest_mask & (1u << j))) slot += 4;
-        const float4 v = k == 0 ? h.rgba : a.V.extra[k - 1][h.visit];
-        const float vc = c == 0 ? v.x : (c == 1 ? v.y : (c == 2 ? v.z : v.w));
-        s_val[slot + c] = (vc + ae) * w;
-        s_off[slot + c] = 4u * k + c;
-      }
-    }
-    if (threadIdx.x == 0) { s_val[U - 1] = w; s_off[U - 1] = 4u * a.F.n_aovs; }
+    const uint32_t U = tl_chroma_item_values(a, h, threadIdx.x, s_val, s_off);
     __syncthreads();
     uint32_t n = 0, acc = 0, last_n = 0;
     bool done = false;
@@ -4526,7 +4595,7 @@ __global__ __launch_bounds__(256) void tl_chroma_walk_kernel(TlChromaArgs a) {
       int channel = 0;
       uint32_t my_code = kCodeFail;
       if (survives) {
-        channel = (int)floor(((double)s_x[xi] / 4294967296.0) * 3.0) - 1;      // :397
+        channel = tl_chroma_channel(s_x[xi]);
         my_code = code[channel + 1];
       }
       const bool succ = survives && my_code < kCodeOut;
@@ -4553,44 +4622,8 @@ __global__ __launch_bounds__(256) void tl_chroma_walk_kernel(TlChromaArgs a) {
       if (lane == 0) s_cnt2[wave] = (uint32_t)__builtin_popcountll(cm);
       __syncthreads();
       const uint32_t consumed = s_cnt2[0] + s_cnt2[1] + s_cnt2[2] + s_cnt2[3];
-      // splat the accepted draws: channel c feeds colour component c only, three-fold; alpha and weight as they are
-      const unsigned long long tm = __ballot(take);
-      const uint32_t T = (uint32_t)__builtin_popcountll(tm);
-      if (take) {
-        const uint32_t pix = my_code;
-        const uint32_t row = pix / a.P.xres;
-        rmin = row < rmin ? row : rmin;
-        rmax_p1 = row + 1u > rmax_p1 ? row + 1u : rmax_p1;
-        const uint32_t slot = (uint32_t)__builtin_popcountll(tm & lt_mask);
-        s_pix[wave][slot] = pix;
-        s_ch[wave][slot] = (uint32_t)(channel + 1);
-        s_key[wave][slot] = (pix << 2) | (uint32_t)(channel + 1);       // (frames of up to 2^30 pixels)
-        if (a.F.touched) { a.F.touched[pix >> 6] = 1; a.F.touched_px[pix] = 1; }
-        if (a.F.zkey) atomicMin(a.F.zkey + pix, zk);
-        if (a.F.zkey_dbg) atomicMin(a.F.zkey_dbg + pix, zk);
-        if (a.log_cap) {
-          const unsigned long long li = wave_log_slots(a.log_count, tm, lane);
-          if (li < a.log_cap) { a.log[li].visit = h.visit; a.log[li].attempt = my_n | ((uint32_t)(channel + 1) << 30); a.log[li].pixel = pix; }
-        }
-      }
-      __syncthreads();
-      // draws of the step with the same pixel and channel: one atomic of count x value (accept_item does the same)
-      count_same_pixel(s_key[wave], s_same[wave], T, lane);
-      __syncthreads();
-      for (uint32_t q = lane; q < T * U; q += 64u) {
-        const uint32_t d = q / U, ch = q - d * U;
-        const uint32_t same = s_same[wave][d];
-        if (!same) continue;
-        float val = s_val[ch];
-        if (ch != U - 1u) {
-          const uint32_t comp = s_off[ch] & 3u;
-          if (comp < 3u) {
-            if (comp != s_ch[wave][d]) continue;          // rgb_weight is 0 there
-            val = val * 3.0f;
-          }
-        }
-        atomicAdd(a.F.acc + (size_t)s_pix[wave][d] * a.F.stride + s_off[ch], (float)same * val);
-      }
+      tl_chroma_accept_wave(a, h.visit, zk, take, my_code, channel, my_n, lane, s_pix[wave], s_same[wave], s_ch[wave], s_key[wave],
+                            s_val, s_off, U, rmin, rmax_p1);
       uint32_t taken = stotal < S - acc ? stotal : S - acc;
       acc += taken;
       n += executed;
