@@ -39,7 +39,7 @@ static int host_trace_passes() { static const int n = getenv("LENTIL_HOST_TRACE"
 struct StreamTail {
   hipStream_t tail = nullptr;         // the stream the pass's last kernels and its counter read-back are on
   std::chrono::steady_clock::time_point pass_t0;
-  bool calibrates_now = false, predicted = false, lean = false, extend = false, live = false, inject = false;
+  bool calibrates_now = false, predicted = false, lean = false, live = false, inject = false;
   int blind_rounds = 2;
   DrawArgs da{};
   SlowRec *slow_base = nullptr;
@@ -154,19 +154,14 @@ struct lentil_hip_ctx {
  uint64_t slow_below = 8ull << 20;          // LENTIL_SLOW_BELOW: ... in chunks whose draw sum is below this
  int slow_from_round = 0;                   // LENTIL_SLOW_FROM_ROUND
   int slow_max_lanes = 4;                    // LENTIL_SLOW_MAX_LANES
-  int slow_prio = 0;                         // LENTIL_SLOW_PRIO: instruction priority of the straggler kernel's waves (0-3)
   int slow_waves_per_cu = 0;                 // LENTIL_SLOW_WAVES_PER_CU: straggler waves per CU of a streamed pass (0: one)
   int slow_nap_max = 0;                      // LENTIL_SLOW_NAP_MAX: DrawArgs::slow_nap_max
-  bool blind = true;                         // LENTIL_BLIND=0: always wait for a chunk's scan before sizing its draw rounds
   uint32_t extra_num = 0, extra_const = 16;  // LENTIL_EXTRA_256THS / LENTIL_EXTRA_CONST: first-batch over-provisioning (16 spare attempts: what a decoupled first accept's guess about its unknown attempts may be off by, accept_item<1>)
   uint64_t extra_below = 8ull << 20;         // LENTIL_EXTRA_BELOW: ... while a chunk's draw sum is below this
   int solve_cap_blocks = 1;                  // LENTIL_EARLY_CAP_BLOCKS: solve blocks per CU while later chunks are scanned
   int accept_max_blocks = 4;                 // LENTIL_ACCEPT_BLOCKS: accept blocks per CU at most
   int accept_stream_blocks = 2;              // ... in a streamed pass, whose accepts share the CUs with the next round's solves
-  bool extend = false;                       // LENTIL_EXTEND=1: a streamed pass's first round appends the batches its items still need itself
-                                             // (ItemLive, lentil_kernels.h).  Built, correct, and measured slower: 2.30 against 2.00 ms, see there
-  bool lean_tail = true;                     // LENTIL_LEAN_TAIL=0: ... and its second round's kernels are always in flight
-  bool lean_ok = true;                       // the last streamed pass with extension left its first accept nothing to schedule
+  bool lean_ok = true;                       // false once a modelled pass fell short with the model's margin at its cap (streamed_finish): no lean tail until the camera set-up changes
   uint64_t n_lean_lost = 0;                  // passes whose lean tail had to run the second round after all
   // First batches from the lens and the frame (lentil_batch_model.h): the calibration table, what it was built for, and how
   // the bets on it went.  LENTIL_PREDICT=0: every item starts with samples + retries + spare, as before round 5.
@@ -192,10 +187,6 @@ struct lentil_hip_ctx {
   uint32_t bm_margin16 = 0;                  // sixteenths the model's margin has been widened by (a lost bet adds one, at most 4)
   uint32_t bm_since_loss = 0;
   uint64_t n_bm_built = 0, n_lean = 0;       // calibrations run / passes that ran with the lean tail
-  ItemLive *d_live = nullptr;                // ... one record per item of chunk 0
-  uint64_t live_cap = 0;
-  Task *d_ext_q = nullptr;                   // ... the queue of the batches it appends
-  uint64_t ext_q_cap = 0;
   int solve_max_blocks = 4;                  // LENTIL_SOLVE_BLOCKS: solve blocks per CU at most
   // Streamed pass (polynomial optics, from the second pass of a context on): one scan launch that publishes its items
   // and their first-batch tasks itself, persistent solve waves that follow the task queue while the scan runs.
@@ -225,29 +216,22 @@ struct lentil_hip_ctx {
   int32_t dirty_lo = 0, dirty_hi = 0;
   bool dirty_known = false;
   hipEvent_t scans_done = nullptr;   // after the last chunk's scan of a pass
-  bool overlap_rounds = true;        // LENTIL_OVERLAP_ROUNDS=0: a streamed pass's second round starts after its first accept has ended
-  bool slow_live = true;             // LENTIL_SLOW_LIVE=0: stragglers of a streamed pass wait for their round's solve kernel to end
-  int crowd_stays_first = 0, crowd_stays_later = 0;    // LENTIL_CROWD_STAYS=ab (two digits): DrawArgs::slow_crowd_stays of a streamed pass's first / later rounds
-  bool solve_b = false;              // LENTIL_SOLVE_B=1: the second solve launch behind the scan (its blocks only find room when the first launch's leave: measured idle)
   uint32_t margin_low_rate = 10;      // LENTIL_BATCH_MARGIN_LOW_RATE (sixteenths, 0..16): DrawArgs::margin_low_rate
   uint32_t batch_margin16 = 4;        // LENTIL_BATCH_MARGIN (sixteenths, 0..16): DrawArgs::batch_margin16
   uint32_t unknown_credit = 7;        // LENTIL_UNKNOWN_CREDIT (0..8): DrawArgs::unknown_credit
-  bool chain_streams = true;          // LENTIL_CHAIN_STREAMS=0: a decoupled pass keeps its accepts on the main stream
   hipEvent_t ev_solve = nullptr, ev_slow1 = nullptr;
   hipStream_t aux_stream = nullptr;     // a fifth stream that runs beside the four (more than four hardware queues to be had), or null
   hipEvent_t ev_crypto = nullptr;       // the cryptomatte own-pixel adds a streamed pass has put on aux_stream
   bool crypto_direct_enqueued = false;
   bool streams_concurrent = false;      // pick_concurrent_streams: the streamed pass's four streams run their kernels side by side
   hipStream_t slow1_stream = nullptr;   // a decoupled pass's second-round straggler kernel (beside the first round's, which is still at work)
-  bool decouple = true;              // LENTIL_DECOUPLE=0: a streamed pass's first accept waits for the first round's stragglers
   hipEvent_t ev_slow = nullptr, ev_round = nullptr;
   // A streamed pass resolves the frame while its second round is still solving (the chip's HBM is idle then) and, at the
   // end, once more the 64-pixel groups that received draws: lentil_hip_resolve then finds its work done.
-  bool early_resolve = true;         // LENTIL_EARLY_RESOLVE=0: lentil_hip_resolve does all of it
   bool early_resolve_pending = false;    // the early half of this pass is enqueued (ev_res marks its end)
   bool late_resolve_done = false;    // ... and so is the second half, behind the last accept
   bool resolved_valid = false;       // d_resolved holds the frame as it is
-  hipEvent_t ev_acc1 = nullptr, ev_res = nullptr, ev_b = nullptr;
+  hipEvent_t ev_acc1 = nullptr, ev_res = nullptr;
   hipStream_t pub_stream = nullptr;  // streamed pass: publish_kernel, then the live straggler kernel
   hipEvent_t pub_done = nullptr;
   bool pass_pending = false;         // a redistribute ran whose rows have not been asked for yet
@@ -255,12 +239,6 @@ struct lentil_hip_ctx {
   uint32_t visit_id_base = 0;
   DevCounters *d_ctr = nullptr;
   std::vector<DevCounters> h_ctr;    // the chunks' counters as read back at the end of the last (blind) pass
-  DevCounters *d_ctr_host = nullptr;     // the pinned staging block as the device addresses it (report_counters_kernel)
-  uint32_t *h_seq = nullptr;             // ... the sequence number behind its records: the pass whose counters they are
-  uint32_t seq = 0;
-  bool spin_readback = false;            // LENTIL_SPIN_READBACK=1: the counters by a kernel into pinned memory, the host polls a sequence
-                                         // number (measured: 1.992 against 1.993 ms, four runs each on one box -- hipStreamSynchronize
-                                         // already spins; off)
   DevCounters *h_ctr_pinned = nullptr;   // staging for that read-back (pinned: an asynchronous copy at the end of each chunk's stream)
   bool h_ctr_valid = false;
   lentil_draw_record *d_log = nullptr;
@@ -305,32 +283,15 @@ struct lentil_hip_ctx {
   // counters are still read (estimates for the next pass, lentil_hip_pass_totals), but work it still needed is not done -- nobody can
   // see that frame any more; pass_totals.abandoned_incomplete counts such passes.  At most two passes are in flight unobserved.
   bool async_end = true;
-  // clear_frame's wipe of the splatted groups off the main stream (round 6; LENTIL_CLEAR_OFFSTREAM=0: on it, as before): a streamed
+  // clear_frame's wipe of the splatted groups off the main stream (round 6): a streamed
   // pass's scan neither reads nor writes the splat accumulators -- the pixels' own sums go to FrameDev::dir --, so the wipe (20-25 us
   // of HBM writes for a 4K frame) runs on the stream of the pass's solve and accept kernels, beside the scan; the first accept
   // follows it in stream order, the early resolve waits for ev_clear, and every other consumer of the frame joins it first
   // (join_clear: CHECK_CTX, lentil_hip_resolve, every pass that is not the streamed one).
-  bool clear_offstream = true;
   bool clear_pending = false;
   hipEvent_t ev_pre_clear = nullptr, ev_clear = nullptr;
-  // accept_kernel<3> (lentil_kernels.h) as the lean tail's first accept: LENTIL_READY_ACCEPT=0 restores round 5's pair, LENTIL_READY_ACCEPT_BLOCKS
-  // its blocks per CU; LENTIL_RESOLVE_AFTER_SCAN=0 / 1 decides where the whole-frame resolve runs whatever the accept (-1: with accept_kernel<3>)
-  bool ready_accept = true;
+  // accept_kernel<3> (lentil_kernels.h) as the lean tail's first accept: LENTIL_READY_ACCEPT_BLOCKS its blocks per CU
   int ready_blocks = 2;              // (2 / 3 / 4 per CU: 2.011 / 2.013 / 2.013 ms, eight interleaved 60-step runs each on one box: gpurun_out/r06s05)
-  // ... and that accept BESIDE the first round's solves (accept_kernel<4>, DrawArgs::early_accept): LENTIL_EARLY_ACCEPT=0 keeps it behind
-  // them (accept_kernel<3>); LENTIL_EARLY_ACCEPT_BLOCKS its blocks per CU (1: a wave per SIMD beside two solve waves)
-  // MEASURED AND OFF BY DEFAULT (LENTIL_EARLY_ACCEPT=1 switches it on): frames bit-identical (tests pass with it on), and the pass
-  // 2.33 ms against 2.01 on one box (gpurun_out/r06s07: six interleaved 60-step runs each).  The accept's 160 us do move under the
-  // solve kernel -- and cost more than they were: the solve kernel runs 1.62-1.65 ms where it took 1.47-1.51 (its results go out as
-  // write-through atomics and every flush waits for them and for a returning atomic per item; the accept's waves take issue slots and
-  // memory-side atomic bandwidth from it), the straggler waves -- 152 registers -- find no room on a SIMD that holds two solve waves
-  // AND an accept wave, so the parked solves start when the solve waves leave and end 210-270 us behind them (170 without), and the
-  // accept behind the stragglers gets the items that met them: 95 us where it took 33.
-  bool early_accept = false;
-  int early_blocks = 1;
-  uint64_t *d_ready = nullptr;       // the queue of completed items (tagged slots, one per item)
-  uint64_t ready_cap = 0;
-  int resolve_after_scan = -1;
   struct Slot {                       // what a pass needs of its own while another pass is being enqueued: events, the counters' landing block
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_scan_k[2] = {nullptr, nullptr};
@@ -455,7 +416,7 @@ static int resolve_range(lentil_hip_ctx *ctx, uint64_t p_begin, uint64_t p_end);
     }                                                                      \
   } while (0)
 
-// the context's stream behind a wipe that clear_frame put on another stream (lentil_hip_ctx::clear_offstream)
+// the context's stream behind a wipe that clear_frame put on another stream (lentil_hip_ctx::clear_pending)
 static int join_clear(lentil_hip_ctx *ctx) {
   if (!ctx->clear_pending) return LENTIL_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -594,21 +555,12 @@ LENTIL_API int lentil_hip_create(int device, lentil_hip_ctx **out_ctx) {
   if (ctx->n_chunks > 16) ctx->n_chunks = 16;
   // one DevCounters per chunk + one shared (draw-log cursor)
   HIP_TRY(ctx, hipMalloc(&ctx->d_ctr, sizeof(DevCounters) * (ctx->n_chunks + 1)));
-  // (+ one record's room behind them for the sequence number of report_counters_kernel)
-  HIP_TRY(ctx, hipHostMalloc((void **)&ctx->h_ctr_pinned, sizeof(DevCounters) * (ctx->n_chunks + 1), hipHostMallocDefault));
-  memset(ctx->h_ctr_pinned, 0, sizeof(DevCounters) * (ctx->n_chunks + 1));
-  ctx->h_seq = reinterpret_cast<uint32_t *>(ctx->h_ctr_pinned + ctx->n_chunks);
-  if (hipHostGetDevicePointer((void **)&ctx->d_ctr_host, ctx->h_ctr_pinned, 0) != hipSuccess) { ctx->d_ctr_host = nullptr; (void)hipGetLastError(); }
-  if (const char *e = getenv("LENTIL_SPIN_READBACK")) ctx->spin_readback = atoi(e) != 0;
+  HIP_TRY(ctx, hipHostMalloc((void **)&ctx->h_ctr_pinned, sizeof(DevCounters) * ctx->n_chunks, hipHostMallocDefault));
+  memset(ctx->h_ctr_pinned, 0, sizeof(DevCounters) * ctx->n_chunks);
   if (const char *e = getenv("LENTIL_ASYNC_END")) ctx->async_end = e[0] != '0';
-  if (const char *e = getenv("LENTIL_CLEAR_OFFSTREAM")) ctx->clear_offstream = e[0] != '0';
   HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_pre_clear, hipEventDisableTiming));
   HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_clear, hipEventDisableTiming));
-  if (const char *e = getenv("LENTIL_READY_ACCEPT")) ctx->ready_accept = e[0] != '0';
   if (const char *e = getenv("LENTIL_READY_ACCEPT_BLOCKS")) { ctx->ready_blocks = atoi(e); if (ctx->ready_blocks < 1) ctx->ready_blocks = 1; if (ctx->ready_blocks > 6) ctx->ready_blocks = 6; }
-  if (const char *e = getenv("LENTIL_RESOLVE_AFTER_SCAN")) ctx->resolve_after_scan = e[0] == '1' ? 1 : 0;
-  if (const char *e = getenv("LENTIL_EARLY_ACCEPT")) ctx->early_accept = e[0] != '0';
-  if (const char *e = getenv("LENTIL_EARLY_ACCEPT_BLOCKS")) { ctx->early_blocks = atoi(e); if (ctx->early_blocks < 1) ctx->early_blocks = 1; if (ctx->early_blocks > 4) ctx->early_blocks = 4; }
   HIP_TRY(ctx, hipEventCreate(&ctx->ev_scan_k[0]));
   HIP_TRY(ctx, hipEventCreate(&ctx->ev_scan_k[1]));
   // the slots of the asynchronous end (lentil_hip_ctx::Slot): slot 0 holds what has just been created, 1 and 2 their own
@@ -622,8 +574,8 @@ LENTIL_API int lentil_hip_create(int device, lentil_hip_ctx **out_ctx) {
       for (int i = 0; i < 5; ++i) HIP_TRY(ctx, hipEventCreate(&sl.ev[i]));
       HIP_TRY(ctx, hipEventCreate(&sl.ev_scan_k[0]));
       HIP_TRY(ctx, hipEventCreate(&sl.ev_scan_k[1]));
-      HIP_TRY(ctx, hipHostMalloc((void **)&sl.h_ctr_pinned, sizeof(DevCounters) * (ctx->n_chunks + 1), hipHostMallocDefault));
-      memset(sl.h_ctr_pinned, 0, sizeof(DevCounters) * (ctx->n_chunks + 1));
+      HIP_TRY(ctx, hipHostMalloc((void **)&sl.h_ctr_pinned, sizeof(DevCounters) * ctx->n_chunks, hipHostMallocDefault));
+      memset(sl.h_ctr_pinned, 0, sizeof(DevCounters) * ctx->n_chunks);
     }
     HIP_TRY(ctx, hipEventCreateWithFlags(&sl.ev_tail, hipEventDisableTiming));
   }
@@ -641,14 +593,12 @@ LENTIL_API int lentil_hip_create(int device, lentil_hip_ctx **out_ctx) {
   HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_round, hipEventDisableTiming));
   HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->pub_done, hipEventDisableTiming));
   HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_acc1, hipEventDisableTiming));
-  HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_b, hipEventDisableTiming));
   HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_res, hipEventDisableTiming));
   HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_solve, hipEventDisableTiming));
   HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_slow1, hipEventDisableTiming));
   HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->slow1_stream, hipStreamNonBlocking));
   HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_crypto, hipEventDisableTiming));
   { const int rc = pick_concurrent_streams(ctx); if (rc) return rc; }
-  if (const char *e = getenv("LENTIL_EARLY_RESOLVE")) ctx->early_resolve = atoi(e) != 0;
   if (const char *e = getenv("LENTIL_INJECT_STALL")) ctx->inject_stall_at = atoi(e);
   if (const char *ft = getenv("LENTIL_FORCE_TABLES")) ctx->use_generated = !(ft[0] == '1');
   if (const char *fc = getenv("LENTIL_FIRST_CHUNK_FRAC")) {
@@ -662,10 +612,8 @@ LENTIL_API int lentil_hip_create(int device, lentil_hip_ctx **out_ctx) {
   if (const char *e = getenv("LENTIL_SLOW_BELOW")) ctx->slow_below = strtoull(e, nullptr, 10);
   if (const char *e = getenv("LENTIL_SLOW_FROM_ROUND")) ctx->slow_from_round = atoi(e);
   if (const char *e = getenv("LENTIL_SLOW_MAX_LANES")) ctx->slow_max_lanes = atoi(e);
-  if (const char *e = getenv("LENTIL_SLOW_PRIO")) ctx->slow_prio = atoi(e);
   if (const char *e = getenv("LENTIL_SLOW_WAVES_PER_CU")) ctx->slow_waves_per_cu = atoi(e);
   if (const char *e = getenv("LENTIL_SLOW_NAP_MAX")) ctx->slow_nap_max = atoi(e);
-  if (const char *e = getenv("LENTIL_BLIND")) ctx->blind = !(e[0] == '0');
   if (const char *e = getenv("LENTIL_EXTRA_256THS")) ctx->extra_num = (uint32_t)strtoul(e, nullptr, 10);
   if (const char *e = getenv("LENTIL_EXTRA_CONST")) ctx->extra_const = (uint32_t)strtoul(e, nullptr, 10);
   if (const char *e = getenv("LENTIL_EXTRA_BELOW")) ctx->extra_below = strtoull(e, nullptr, 10);
@@ -674,8 +622,6 @@ LENTIL_API int lentil_hip_create(int device, lentil_hip_ctx **out_ctx) {
   if (const char *e = getenv("LENTIL_EARLY_CAP_BLOCKS")) ctx->solve_cap_blocks = atoi(e);
   if (ctx->solve_cap_blocks < 1) ctx->solve_cap_blocks = 1;
   if (const char *e = getenv("LENTIL_ACCEPT_BLOCKS")) ctx->accept_max_blocks = ctx->accept_stream_blocks = atoi(e);
-  if (const char *e = getenv("LENTIL_EXTEND")) ctx->extend = e[0] != '0';
-  if (const char *e = getenv("LENTIL_LEAN_TAIL")) ctx->lean_tail = e[0] != '0';
   if (const char *e = getenv("LENTIL_PREDICT")) ctx->predict = e[0] != '0';
   if (const char *e = getenv("LENTIL_PREDICT_MAX_DRAWS")) ctx->predict_max_draws = strtoull(e, nullptr, 10);
   if (const char *e = getenv("LENTIL_LENS_JIT")) ctx->jit_enabled = e[0] != '0';
@@ -690,16 +636,10 @@ LENTIL_API int lentil_hip_create(int device, lentil_hip_ctx **out_ctx) {
   if (ctx->solve_max_blocks < 1) ctx->solve_max_blocks = 1;
   if (const char *e = getenv("LENTIL_STREAM")) ctx->stream_mode = !(e[0] == '0');
   if (const char *e = getenv("LENTIL_SCAN_DMA")) ctx->scan_dma = !(e[0] == '0');
-  if (const char *e = getenv("LENTIL_SLOW_LIVE")) ctx->slow_live = !(e[0] == '0');
   if (const char *e = getenv("LENTIL_PARK_DRY_ONLY")) ctx->park_dry_only = atoi(e);
-  if (const char *e = getenv("LENTIL_OVERLAP_ROUNDS")) ctx->overlap_rounds = !(e[0] == '0');
-  if (const char *e = getenv("LENTIL_DECOUPLE")) ctx->decouple = !(e[0] == '0');
-  if (const char *e = getenv("LENTIL_CHAIN_STREAMS")) ctx->chain_streams = !(e[0] == '0');
   if (const char *e = getenv("LENTIL_BATCH_MARGIN_LOW_RATE")) { const int v = atoi(e); ctx->margin_low_rate = (uint32_t)(v < 0 ? 0 : (v > 16 ? 16 : v)); }
   if (const char *e = getenv("LENTIL_BATCH_MARGIN")) { const int v = atoi(e); ctx->batch_margin16 = (uint32_t)(v < 0 ? 0 : (v > 16 ? 16 : v)); }
   if (const char *e = getenv("LENTIL_UNKNOWN_CREDIT")) { const int v = atoi(e); ctx->unknown_credit = (uint32_t)(v < 0 ? 0 : (v > 8 ? 8 : v)); }
-  if (const char *e = getenv("LENTIL_CROWD_STAYS")) { ctx->crowd_stays_first = e[0] == '1'; ctx->crowd_stays_later = e[0] && e[1] == '1'; }
-  if (const char *e = getenv("LENTIL_SOLVE_B")) ctx->solve_b = e[0] == '1';
   if (const char *e = getenv("LENTIL_STREAM_BELOW")) { ctx->stream_below = strtoull(e, nullptr, 10); ctx->stream_below_set = true; }
   if (const char *e = getenv("LENTIL_STREAM_BLOCKS")) ctx->stream_blocks = atoi(e);
   if (ctx->stream_blocks < 1) ctx->stream_blocks = 1;
@@ -728,7 +668,6 @@ LENTIL_API int lentil_hip_create(int device, lentil_hip_ctx **out_ctx) {
       hipLaunchKernelGGL(accept_kernel<1>, dim3(wg), dim3(256), 0, st, w);
       hipLaunchKernelGGL(accept_kernel<2>, dim3(wg), dim3(256), 0, st, w);
       hipLaunchKernelGGL(accept_kernel<3>, dim3(wg), dim3(256), 0, st, w);
-      hipLaunchKernelGGL(accept_kernel<4>, dim3(wg), dim3(256), 0, st, w);
       HIP_TRY(ctx, hipGetLastError());
       HIP_TRY(ctx, hipStreamSynchronize(st));
     }
@@ -822,7 +761,6 @@ LENTIL_API int lentil_hip_destroy(lentil_hip_ctx *ctx) {
     if (sl.h_ctr_pinned) (void)hipHostFree(sl.h_ctr_pinned);
   }
   if (ctx->ev_acc1) (void)hipEventDestroy(ctx->ev_acc1);
-  if (ctx->ev_b) (void)hipEventDestroy(ctx->ev_b);
   if (ctx->ev_res) (void)hipEventDestroy(ctx->ev_res);
   if (ctx->ev_solve) (void)hipEventDestroy(ctx->ev_solve);
   if (ctx->ev_slow1) (void)hipEventDestroy(ctx->ev_slow1);
@@ -831,15 +769,12 @@ LENTIL_API int lentil_hip_destroy(lentil_hip_ctx *ctx) {
   if (ctx->ev_crypto) (void)hipEventDestroy(ctx->ev_crypto);
   (void)hipFree(ctx->d_ctr);
   (void)hipFree(ctx->d_ranges);
-  (void)hipFree(ctx->d_ready);
   (void)hipFree(ctx->d_c2w_keys); (void)hipFree(ctx->d_probe_seg); (void)hipFree(ctx->d_probe_idx); (void)hipFree(ctx->d_probe_occ);
   (void)hipFree(ctx->d_probe_count);
   if (ctx->h_probe_seg) (void)hipHostFree(ctx->h_probe_seg);
   if (ctx->h_probe_occ) (void)hipHostFree(ctx->h_probe_occ);
-  (void)hipFree(ctx->d_live);
   if (ctx->jit_module) (void)hipModuleUnload(ctx->jit_module);
   (void)hipFree(ctx->d_bm_land); (void)hipFree(ctx->d_bm_box); (void)hipFree(ctx->d_bm_npass);
-  (void)hipFree(ctx->d_ext_q);
   (void)hipFree(ctx->d_xor); (void)hipFree(ctx->d_tlc_res); (void)hipFree(ctx->d_tlc_off); (void)hipFree(ctx->d_tlc_tasks);
   (void)hipFree(ctx->d_xor_jump); (void)hipFree(ctx->d_tlc_entry); (void)hipFree(ctx->d_tlc_val);
   (void)hipFree(ctx->d_log);
@@ -1583,7 +1518,7 @@ LENTIL_API int lentil_hip_clear_frame(lentil_hip_ctx *ctx) {
     const uint64_t max_blocks = (uint64_t)ctx->num_cu * 4;
     if (blocks > max_blocks) blocks = max_blocks;
     hipStream_t cs = ctx->stream;
-    const bool off = ctx->clear_offstream && ctx->streams_concurrent && ctx->stream_mode && !ctx->chunks.empty() && ctx->chunks[0].stream && !ctx->clear_pending;
+    const bool off = ctx->streams_concurrent && ctx->stream_mode && !ctx->chunks.empty() && ctx->chunks[0].stream && !ctx->clear_pending;
     if (off) {
       // behind everything the main stream holds so far (the last pass's tail is on this very stream already), beside what it gets next
       cs = ctx->chunks[0].stream;
@@ -1632,13 +1567,13 @@ static int grow(lentil_hip_ctx *ctx, T **p, uint64_t need) {
 }
 
 template <bool kStream>
-static void launch_solve_po(lentil_hip_ctx *ctx, const DrawArgs &da, hipStream_t st, unsigned blocks, unsigned threads = 256) {
+static void launch_solve_po(lentil_hip_ctx *ctx, const DrawArgs &da, hipStream_t st, unsigned blocks) {
   const bool chroma = da.n_channels == 3;       // chromatic aberration: three wavelength channels per attempt
   bool launched = false;
 #define LENTIL_LAUNCH_GEN(NAME)                                                                          \
   if (!launched && ctx->use_generated && ctx->lens_hash == gen::Lens_##NAME::kTableHash) {                \
-    if (chroma) hipLaunchKernelGGL((solve_po_kernel<GenLens<gen::Lens_##NAME>, false, true, kStream>), dim3(blocks), dim3(threads), 0, st, da); \
-    else hipLaunchKernelGGL((solve_po_kernel<GenLens<gen::Lens_##NAME>, false, false, kStream>), dim3(blocks), dim3(threads), 0, st, da); \
+    if (chroma) hipLaunchKernelGGL((solve_po_kernel<GenLens<gen::Lens_##NAME>, false, true, kStream>), dim3(blocks), dim3(256), 0, st, da); \
+    else hipLaunchKernelGGL((solve_po_kernel<GenLens<gen::Lens_##NAME>, false, false, kStream>), dim3(blocks), dim3(256), 0, st, da); \
     launched = true;                                                                                     \
   }
   LENTIL_GENERATED_LENSES(LENTIL_LAUNCH_GEN)
@@ -1648,12 +1583,12 @@ static void launch_solve_po(lentil_hip_ctx *ctx, const DrawArgs &da, hipStream_t
     if (hipFunction_t fn = jit_function(ctx, chroma, kStream)) {
       DrawArgs args = da;
       void *params[] = {&args};
-      launched = hipModuleLaunchKernel(fn, blocks, 1, 1, threads, 1, 1, 0, st, params, nullptr) == hipSuccess;
+      launched = hipModuleLaunchKernel(fn, blocks, 1, 1, 256, 1, 1, 0, st, params, nullptr) == hipSuccess;
     }
   }
   if (!launched) {
-    if (chroma) hipLaunchKernelGGL((solve_po_kernel<LdsLens, true, true, kStream>), dim3(blocks), dim3(threads), 0, st, da);
-    else hipLaunchKernelGGL((solve_po_kernel<LdsLens, true, false, kStream>), dim3(blocks), dim3(threads), 0, st, da);
+    if (chroma) hipLaunchKernelGGL((solve_po_kernel<LdsLens, true, true, kStream>), dim3(blocks), dim3(256), 0, st, da);
+    else hipLaunchKernelGGL((solve_po_kernel<LdsLens, true, false, kStream>), dim3(blocks), dim3(256), 0, st, da);
   }
 }
 
@@ -1831,7 +1766,7 @@ static uint64_t chunk_units(const lentil_params &P, uint64_t nch, uint64_t sum_s
 static int enqueue_chunk_draws_blind(lentil_hip_ctx *ctx, int ci, DrawArgs &da, int blind_rounds, bool *done) {
   lentil_hip_ctx::Chunk &ch = ctx->chunks[ci];
   *done = false;
-  if (!ctx->blind || !ch.have_est) return LENTIL_OK;
+  if (!ch.have_est) return LENTIL_OK;
   const uint64_t cap = ch.v_end - ch.v_begin;
   uint64_t items = ch.est_items + ch.est_items / 4 + 1024;
   if (items > cap) items = cap;
@@ -1951,10 +1886,6 @@ static void init_draw_args(lentil_hip_ctx *ctx, DrawArgs &da) {
   da.slow_at = ctx->slow_at;
   da.batch_margin16 = ctx->batch_margin16;
   da.margin_low_rate = ctx->margin_low_rate;
-  {
-    static const bool narrow = getenv("LENTIL_ACCEPT_WIDE") && getenv("LENTIL_ACCEPT_WIDE")[0] == '0';
-    da.accept_narrow = narrow ? 1 : 0;
-  }
   if (ctx->slow_at > 0 && ctx->mean_iters > 0.0) {
     const int adaptive = (int)(1.3 * ctx->mean_iters + 0.5);
     if (adaptive > da.slow_at) da.slow_at = adaptive < 90 ? adaptive : 90;
@@ -1962,7 +1893,6 @@ static void init_draw_args(lentil_hip_ctx *ctx, DrawArgs &da) {
   da.slow_below = ctx->slow_below;
   da.slow_from_round = ctx->slow_from_round;
   da.slow_max_lanes = ctx->slow_max_lanes;
-  da.slow_prio = ctx->slow_prio;
   da.slow_nap_max = ctx->slow_nap_max;
   { const char *e = getenv("LENTIL_DISPATCH_PROBE"); da.dispatch_probe = (e && e[0] == '1') ? 1 : 0; }
   da.extra_num = ctx->extra_num; da.extra_const = ctx->extra_const; da.extra_below = ctx->extra_below;
@@ -2262,9 +2192,8 @@ static int launch_scan(lentil_hip_ctx *ctx, const ScanPlan &pl, const lentil_hip
   const uint64_t max_blocks = (uint64_t)ctx->num_cu * 8;
   uint64_t blocks;
   unsigned multi_skipped = 0;
-  // (a streamed pass's single launch: timed by its own dispatch, lentil_hip_last_timing; LENTIL_SCAN_EVENTS=0: by the events around it)
-  static const bool scan_events = !(getenv("LENTIL_SCAN_EVENTS") && getenv("LENTIL_SCAN_EVENTS")[0] == '0');
-  const bool own_events = streamed_pass && scan_events && (pl.dma || pl.dma_multi);
+  // (a streamed pass's single launch: timed by its own dispatch, lentil_hip_last_timing)
+  const bool own_events = streamed_pass && (pl.dma || pl.dma_multi);
   ctx->scan_kernel_timed = own_events;
   if (pl.dma) {
     // persistent, every wave draws four tiles at a time
@@ -2391,7 +2320,7 @@ static int streamed_finish(lentil_hip_ctx *ctx, StreamTail &t, const DevCounters
   const int C = ctx->n_chunks;
   lentil_hip_ctx::Chunk &ch = ctx->chunks[0];
   DrawArgs &da = t.da;
-  const bool predicted = t.predicted, lean = t.lean, extend = t.extend, live = t.live;
+  const bool predicted = t.predicted, lean = t.lean, live = t.live;
   const int blind_rounds = t.blind_rounds;
   SlowRec *const slow_base = t.slow_base;
   const uint32_t slow_cap_all = t.slow_cap_all;
@@ -2528,7 +2457,6 @@ static int streamed_finish(lentil_hip_ctx *ctx, StreamTail &t, const DevCounters
     ch.have_est = true; ch.est_items = n_items; ch.est_sum = c.sum_samples; ch.est_rounds = (int)c.rounds_used;
     if (c.tries) { ctx->mean_iters = (double)c.newton_iters / (double)c.tries; ctx->parked_frac = (double)c.slow_solves / (double)c.tries; }
     int rounds = blind_rounds;
-    if (extend) ctx->lean_ok = c.n_tasks[1] == 0u;       // (what the next pass may count on)
     if (lean) ++ctx->n_lean;
     // A pass whose first batches came from the model and left an item short all the same: the model's margin widens for the
     // passes that follow (the item is served by further rounds as ever); with the margin at its cap the context stops
@@ -2556,7 +2484,7 @@ static int streamed_finish(lentil_hip_ctx *ctx, StreamTail &t, const DevCounters
     if (lean && n_items && c.n_tasks[1] != 0u) {
       // The lean tail's bet was lost: the first accept scheduled tasks, the accept behind it did nothing.  The round the
       // ordinary way -- its solves (the queue is complete), their stragglers, the accept that was held back -- then whatever
-      // rounds follow.  (Rare: an item whose estimate in the solve kernel was too kind; ~0.3 ms.)
+      // rounds follow.  (Rare: an item whose first batch the model sized too small; ~0.3 ms.)
       ctx->h_ctr_valid = false;
       ctx->late_resolve_done = false;
       da.parity = 1; da.round = 1;
@@ -2617,8 +2545,6 @@ static int redistribute_streamed(lentil_hip_ctx *ctx, bool *streamed, bool *defe
   // frame: 114 ms against 135 ms; 15 M draws: 16.6 against 18.4 ms -- solve waves placed while the scan's are
   // resident keep running slower long after those have left, see launch_chunk_rounds), and so it is with extra
   // AOVs, whose scan kernel leaves the solve waves less room (config 4: 10.8 against 11.5 ms).
-  // (LENTIL_STREAM_EXTRA=0: frames with extra AOVs take the chunked pass whatever their scan kernel)
-  static const bool stream_extra = !(getenv("LENTIL_STREAM_EXTRA") && getenv("LENTIL_STREAM_EXTRA")[0] == '0');
   // (Round 3: ... or below one draw per 24 visits, whichever is more -- what streaming buys is the scan running beside the
   // solves, and a frame whose scan is long against its draws gains most: BASELINE config 5, 8K with 9.3 M draws, 12.9 ms
   // streamed against 16.3 chunked; 4K with 3.1 M draws 4.3 against 4.8 ms, with 6-48 M draws within +-5 % either way.)
@@ -2626,7 +2552,7 @@ static int redistribute_streamed(lentil_hip_ctx *ctx, bool *streamed, bool *defe
     const uint64_t by_visits = ctx->stream_below_set ? 0ull : ctx->V.n / 24ull;
     if (ctx->est_sum_total >= (ctx->stream_below > by_visits ? ctx->stream_below : by_visits)) return LENTIL_OK;
   }
-  if (ctx->V.n_extra && !(stream_extra && dma_multi_applies(ctx))) return LENTIL_OK;
+  if (ctx->V.n_extra && !dma_multi_applies(ctx)) return LENTIL_OK;
   lentil_hip_ctx::Chunk &ch = ctx->chunks[0];
   // One streamed pass per device at a time: the resident kernels of two of them could keep each other's scan off the chip.
   // A context that finds another one's streamed pass in flight does not wait for it: its pass runs in the chunked form,
@@ -2651,7 +2577,7 @@ static int redistribute_streamed(lentil_hip_ctx *ctx, bool *streamed, bool *defe
   ScanPlan plan;
   if ((rc = plan_scan(ctx, plan))) return rc;
   da.F = ctx->F;                // (plan_scan decides where the direct sums go and whether splats are flagged)
-  // the wipe clear_frame left on the chunk stream (clear_offstream) rides beside the scan only where the scan leaves the splat
+  // the wipe clear_frame left on the chunk stream (clear_pending) rides beside the scan only where the scan leaves the splat
   // accumulators alone: own sums to FrameDev::dir, splats flagged
   if (ctx->clear_pending && !(ctx->F.dir && ctx->F.touched) && (rc = join_clear(ctx))) return rc;
   ch.tile_begin = 0; ch.tile_end = plan.n_tiles;
@@ -2667,9 +2593,7 @@ static int redistribute_streamed(lentil_hip_ctx *ctx, bool *streamed, bool *defe
     HIP_TRY(ctx, hipMemsetAsync(ch.tasks[0], 0, ch.task_cap * sizeof(Task), ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(ch.tasks[1], 0, ch.task_cap * sizeof(Task), ctx->stream));
     if (ctx->d_ranges) HIP_TRY(ctx, hipMemsetAsync(ctx->d_ranges, 0, ctx->range_cap * sizeof(uint64_t), ctx->stream));
-    if (ctx->d_ready) HIP_TRY(ctx, hipMemsetAsync(ctx->d_ready, 0, ctx->ready_cap * sizeof(uint64_t), ctx->stream));
     if (ch.slow) HIP_TRY(ctx, hipMemsetAsync(ch.slow, 0, ch.slow_cap * sizeof(SlowRec), ctx->stream));
-    if (ctx->d_ext_q) HIP_TRY(ctx, hipMemsetAsync(ctx->d_ext_q, 0, ctx->ext_q_cap * sizeof(Task), ctx->stream));
   }
   const uint32_t retries = (uint32_t)(P.vignetting_retries < 0 ? 0 : P.vignetting_retries);
   const bool few = ctx->est_sum_total < ctx->slow_below;
@@ -2746,17 +2670,9 @@ static int redistribute_streamed(lentil_hip_ctx *ctx, bool *streamed, bool *defe
   const bool calibrates_now = ctx->predict && !ctx->bm_valid;       // (this pass's host time holds the calibration kernel's)
   // the first-batch model's calibration, should the camera set-up have changed: on the main stream, ahead of the event the
   // publishers (who read the table) wait for
-  if (ctx->predict && !ctx->extend && nch == 1 && (rc = ensure_batch_model(ctx))) return rc;
+  if (ctx->predict && nch == 1 && (rc = ensure_batch_model(ctx))) return rc;
   // (the scan's start for lentil_hip_last_timing: the host work since the pass began -- sizing, the plan -- is not the kernel's)
   HIP_TRY(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-  {
-    static const bool a_first = getenv("LENTIL_A_FIRST") && getenv("LENTIL_A_FIRST")[0] == '1';
-    if (a_first && ctx->streams_concurrent && ctx->slow_live) {
-      hipLaunchKernelGGL(wait_waves_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->d_ctr,
-                         (uint32_t)ctx->num_cu * (uint32_t)ctx->stream_blocks * 4u, (uint64_t)30000);      // (0.3 ms at most)
-      HIP_TRY(ctx, hipGetLastError());
-    }
-  }
   if ((rc = launch_scan(ctx, plan, ch, ctx->d_ctr, &scan_blocks, true))) return rc;
   ctx->last_scan_launches = 1;
   HIP_TRY(ctx, hipEventRecord(ch.scanned, ctx->stream));
@@ -2793,9 +2709,8 @@ static int redistribute_streamed(lentil_hip_ctx *ctx, bool *streamed, bool *defe
   // Live straggler queue: solve_slow_kernel is launched behind the publishers (who end with the scan) and takes the parked
   // solves as they come, one wave per CU.  (Round 3, from the timeline: its waves are placed as the first solve waves
   // leave -- the idle ones do at once when the publishers' end markers arrive --, not in the registers the scan gives
-  // back: a wave's registers are one contiguous range.  The second instance B, three waves per block so that a SIMD per
-  // CU kept room for a straggler wave, never got a task and is off: LENTIL_SOLVE_B.)
-  const bool live = ctx->slow_live && da.slow != nullptr && P.cameraType == LENTIL_POLYNOMIAL_OPTICS;
+  // back: a wave's registers are one contiguous range.)
+  const bool live = da.slow != nullptr && P.cameraType == LENTIL_POLYNOMIAL_OPTICS;
   int blind_rounds = ctx->est_rounds_total < 2 ? 2 : (ctx->est_rounds_total > 6 ? 6 : ctx->est_rounds_total);
   if (const char *e = getenv("LENTIL_BLIND_ROUNDS")) { blind_rounds = atoi(e); if (blind_rounds < 1) blind_rounds = 1; if (blind_rounds > 8) blind_rounds = 8; }
   // Second round beside the first accept: the accept kernel hands out the next round's tasks as it goes (tagged slots,
@@ -2804,20 +2719,18 @@ static int redistribute_streamed(lentil_hip_ctx *ctx, bool *streamed, bool *defe
   // serialises kernels runs them in an order that completes.
   // (Round 4: also in passes that park nothing -- more draws than LENTIL_SLOW_BELOW, BASELINE config 5 on one GPU: 4 560 items
   // x 2 048 draws --, whose first accept takes 0.65 ms and whose second round used to wait for all of it: 11.7 -> see DESIGN
-  // section 5.  No straggler kernels there, just the accept feeding the resident second-round solves.  LENTIL_OVERLAP_HEAVY=0: off.)
-  static const bool overlap_heavy_ok = !(getenv("LENTIL_OVERLAP_HEAVY") && getenv("LENTIL_OVERLAP_HEAVY")[0] == '0');
-  const bool overlap_plain = !live && overlap_heavy_ok && da.slow == nullptr && nch == 1 && P.cameraType == LENTIL_POLYNOMIAL_OPTICS;
-  const bool overlap = (live || overlap_plain) && ctx->overlap_rounds && blind_rounds >= 2;
+  // section 5.  No straggler kernels there, just the accept feeding the resident second-round solves.)
+  const bool overlap_plain = da.slow == nullptr && nch == 1 && P.cameraType == LENTIL_POLYNOMIAL_OPTICS;
+  const bool overlap = (live || overlap_plain) && blind_rounds >= 2;
   // ... and the first accept does not wait for the first round's stragglers either (accept_item<1> / <2>): one
   // straggler queue and one solve_slow_kernel launch for both rounds, closed by the second round's solve kernel.
-  const bool decoupled = live && overlap && ctx->decouple && nch == 1;
+  const bool decoupled = live && overlap && nch == 1;
   // (A queue and a solve_slow_kernel launch per round, as ever: ONE kernel for both rounds would wait for end markers from
   // kernels submitted after it -- the first accept, the second round's solves -- and where two of the pass's streams share
   // a hardware queue, the default with the runtime's 4, those sit behind it in that queue: 250 ms, then the chunked redo.
   // The second round parks into the upper half of the record buffer, its kernel follows the first round's on their stream.)
   SlowRec *const slow_base = da.slow;
   const uint32_t slow_cap_all = da.slow_cap;
-  da.slow_crowd_stays = ctx->crowd_stays_first;
   da.unknown_credit = ctx->unknown_credit;
   // (one straggler wave per CU; LENTIL_SLOW_WAVES_PER_CU, up to 4 -- measured on config 4, whose rounds end in hundreds
   // of parked solves at once: 9.15 / 9.18 / 9.35 / 9.46 ms with 1 / 2 / 3 / 4, the waves take from the solve kernel)
@@ -2832,21 +2745,17 @@ static int redistribute_streamed(lentil_hip_ctx *ctx, bool *streamed, bool *defe
   const uint32_t slow_default = (nch == 1 && ctx->V.n_extra == 0 && !dry_only) ? 4u : 1u;
   const uint32_t slow_waves_all = (uint32_t)ctx->num_cu * (slow_per_cu >= 1 && slow_per_cu <= 4 ? (uint32_t)slow_per_cu : slow_default);
   if (decoupled) { da.slow_indirect = 1; da.slow_cap = slow_cap_all / 2u > slow_waves_all ? slow_cap_all / 2u - slow_waves_all : 0u; }      // (its end markers stay below the upper half)
-  static const int b_threads_env = getenv("LENTIL_SOLVE_B_THREADS") ? atoi(getenv("LENTIL_SOLVE_B_THREADS")) : 0;
-  const unsigned b_threads = (b_threads_env == 64 || b_threads_env == 128 || b_threads_env == 192 || b_threads_env == 256) ? (unsigned)b_threads_env
-                                                                                                                         : (live ? 192u : 256u);
-  unsigned b_blocks;
-  {
-    int b_per_cu = live ? 3 - ctx->stream_blocks : ctx->solve_max_blocks - ctx->stream_blocks;
+  // B: a second solve launch behind the scan, in passes without a live queue.  (Measured, round 3: with the straggler
+  // kernel's wave on one of a CU's SIMDs the blocks of this launch are not placed before the first launch's blocks leave --
+  // zero iterations in every pass looked at: a pass with a live queue has none.)
+  unsigned b_blocks = 0;
+  if (!live) {
+    int b_per_cu = ctx->solve_max_blocks - ctx->stream_blocks;
     if (b_per_cu < 1) b_per_cu = 1;
     const uint64_t want = (nch * (ctx->est_sum_total / 64 + ctx->est_items_total) + 3) / 4;
     uint64_t b = (uint64_t)ctx->num_cu * (uint64_t)b_per_cu;
     if (want < b) b = want < 1 ? 1 : want;
     b_blocks = (unsigned)b;
-    // (Measured, round 3: with the straggler kernel's wave on one of a CU's SIMDs the three-wave blocks of this launch are
-    // not placed before the first launch's blocks leave -- zero iterations in every pass looked at; the launch then only
-    // stands between the first launch's end and the accept.)
-    if (live && !ctx->solve_b) b_blocks = 0;
   }
   da.slow_live = live ? 1 : 0;
   // A live queue takes every solve that reaches slow_at iterations -- outliers, by the measure of the previous pass.  With
@@ -2854,96 +2763,36 @@ static int redistribute_streamed(lentil_hip_ctx *ctx, bool *streamed, bool *defe
   // of the straggler kernel: 12 ms a frame against 10 chunked) only waves running dry park, and only their last lanes.
   // (It stays that way for the lens: a pass that parks dry waves' lanes only says nothing about what a live queue would get.)
   da.slow_dry_only = dry_only ? 1 : 0;
-  {
-    // (LENTIL_PARK_AFTER_SCAN=0: the first round parks from the start of the pass; 2 486 parked solves per headline pass
-    // instead of 1 070, 2.33 against 2.31 ms)
-    const char *e = getenv("LENTIL_PARK_AFTER_SCAN");
-    da.slow_after_producers = (e ? e[0] != '0' : true) ? 1 : 0;
-  }
+  // (the first round parks only once the scan has ended: 1 070 parked solves per headline pass instead of 2 486)
+  da.slow_after_producers = 1;
   da.slow_waves = live ? slow_waves_all : 0u;
   da.producers_done = &ctx->d_ctr->publishers_done;
   da.producers_total = (uint32_t)ctx->publish_waves;
-  pa.end_tasks = a_blocks * 4u + b_blocks * (b_threads / 64u);       // every first-round solve wave may hold one ticket past the last task
-  // Extension (ItemLive, lentil_kernels.h): the first round's solve kernel appends the batches its items still need
-  const bool extend = ctx->extend && decoupled && nch == 1 && ctx->chain_streams;
+  pa.end_tasks = (a_blocks + b_blocks) * 4u;       // every first-round solve wave may hold one ticket past the last task
   // First batches from the lens and the frame (lentil_batch_model.h): every item is published with the traces it is expected
   // to need, so that the first accept finds nothing to schedule and the pass can do without a second round (lean tail, below)
   // (Not for items with very many draws each -- BASELINE config 5's 2 048: their first accept is long, 0.3-0.65 ms, and the
   // second round that runs beside it is all but free, while its traces inside the first round are throughput; the bands of
   // that frame, each alone on one GPU, took 5-19 % longer with the lean tail: profiles/r05_emulated_bands.txt.)
   const bool few_draws_per_item = ctx->est_items_total == 0 || ctx->est_sum_total / ctx->est_items_total <= ctx->predict_max_draws;
-  const bool predict = ctx->predict && !extend && decoupled && nch == 1 && ctx->chain_streams && few_draws_per_item;
+  const bool predict = ctx->predict && decoupled && few_draws_per_item;
   if (predict && ctx->bm_valid) pub.model = batch_model_dev(ctx);        // (calibrated ahead of the scan, above)
   const bool predicted = predict && pub.model.land != nullptr;
-  if (extend) {
-    if (ch.item_cap > ctx->live_cap) {
-      if ((rc = grow(ctx, &ctx->d_live, ch.item_cap))) return rc;
-      ctx->live_cap = ch.item_cap;
-    }
-    if (ch.task_cap > ctx->ext_q_cap) {
-      if ((rc = grow(ctx, &ctx->d_ext_q, ch.task_cap))) return rc;
-      ctx->ext_q_cap = ch.task_cap;
-      HIP_TRY(ctx, hipMemsetAsync(ctx->d_ext_q, 0, ch.task_cap * sizeof(Task), ctx->stream));       // (slots are told by their tag)
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    const unsigned keepers = a_blocks < (unsigned)ctx->num_cu ? a_blocks : (unsigned)ctx->num_cu;       // one block per CU stays
-    pub.live = ctx->d_live;
-    pub.ext_q = ctx->d_ext_q;
-    pub.ext_keepers = keepers * 4u;
-    da.live = ctx->d_live;
-    da.ext_q = ctx->d_ext_q;
-    da.ext_keeper_blocks = keepers;
-    da.ext_end_tasks = keepers * 4u;
-    da.ext_slack = 4u;
-  }
   // The lean tail (below): known before anything is launched -- the solve and straggler kernels count parked solves per item for
   // accept_kernel<3> (DrawArgs::item_ready) in such a pass.
   // (LENTIL_INJECT_STALL stalls the second round's resident solve waves: that pass keeps its second round in flight)
-  const bool lean_pass = decoupled && ctx->chain_streams && (extend || predicted) && ctx->lean_tail && ctx->lean_ok && blind_rounds <= 2 &&
-                         !da.inject_stall;
+  const bool lean_pass = decoupled && predicted && ctx->lean_ok && blind_rounds <= 2 && !da.inject_stall;
   // Round 6: the first accept takes the items whose parked solves are through, whole, and leaves the others to the accept behind
-  // the stragglers (accept_kernel<3>; LENTIL_READY_ACCEPT=0: round 5's pair of accepts, the first splatting what is certain of
-  // every item, the second replaying nearly every item).  For frames the wide walk serves: <= 64 retries, records of <= 64 floats.
-  bool ready_accept = false;
-  {
-    const bool off = !ctx->ready_accept;
-    uint32_t add_floats = 1;
-    for (uint32_t k = 0; k < ctx->F.n_aovs; ++k) if (!(ctx->F.closest_mask & (1u << k))) add_floats += 4;
-    ready_accept = lean_pass && !off && live && retries <= kAcceptWinRetries && !da.accept_narrow && add_floats <= 64u && nch == 1;
-  }
+  // the stragglers (accept_kernel<3>).  For frames the wide walk serves: <= 64 retries, records of <= 64 floats.
+  uint32_t add_floats = 1;
+  for (uint32_t k = 0; k < ctx->F.n_aovs; ++k) if (!(ctx->F.closest_mask & (1u << k))) add_floats += 4;
+  const bool ready_accept = lean_pass && retries <= kAcceptWinRetries && add_floats <= 64u;
   da.item_ready = ready_accept ? 1 : 0;
-  // ... and beside the solves (accept_kernel<4>): the queue of completed items, a slot per item
-  const bool early = ready_accept && ctx->early_accept && ctx->slow1_stream != nullptr && !b_blocks;
-  if (early) {
-    if (ch.item_cap > ctx->ready_cap) {
-      if ((rc = grow(ctx, &ctx->d_ready, ch.item_cap))) return rc;
-      ctx->ready_cap = ch.item_cap;
-      HIP_TRY(ctx, hipMemsetAsync(ctx->d_ready, 0, ch.item_cap * sizeof(uint64_t), ctx->stream));       // (slots are told by their tag)
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    da.early_accept = 1;
-    da.ready_q = ctx->d_ready;
-    da.ready_cap = (uint32_t)(ctx->ready_cap < 0xFFFFFFF0ull ? ctx->ready_cap : 0xFFFFFFF0ull);
-  }
   HIP_TRY(ctx, hipStreamWaitEvent(ctx->pub_stream, ctx->ev[0], 0));
   hipLaunchKernelGGL(publish_kernel, dim3((unsigned)ctx->publish_waves), dim3(64), 0, ctx->pub_stream, pa);
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipEventRecord(ctx->pub_done, ctx->pub_stream));
-  if (live && early) {
-    // the stragglers on a stream of their own, the first accept behind the publishers on theirs: both start when the scan's
-    // registers and LDS are free, the accept takes the completed items as the solve kernel (launched below) delivers them
-    HIP_TRY(ctx, hipStreamWaitEvent(ctx->slow1_stream, ctx->pub_done, 0));
-    hipLaunchKernelGGL(solve_slow_kernel, dim3(da.slow_waves), dim3(64), coop_lds_bytes(ctx->hlens.n_terms), ctx->slow1_stream, da);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_slow, ctx->slow1_stream));
-    if (ctx->clear_pending) HIP_TRY(ctx, hipStreamWaitEvent(ctx->pub_stream, ctx->ev_clear, 0));      // (it splats into what clear_frame is wiping)
-    DrawArgs d0 = da;
-    d0.emit_live = 0; d0.lean_defer = 1;
-    d0.end_tasks = (uint32_t)ctx->num_cu * 4u;
-    hipLaunchKernelGGL(accept_kernel<4>, dim3((unsigned)ctx->num_cu * (unsigned)ctx->early_blocks), dim3(256), 0, ctx->pub_stream, d0);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_acc1, ctx->pub_stream));
-  } else if (live) {
+  if (live) {
     // (behind the publishers on their stream: they end with the scan, whose registers this kernel's waves need)
     hipLaunchKernelGGL(solve_slow_kernel, dim3(da.slow_waves), dim3(64), coop_lds_bytes(ctx->hlens.n_terms), ctx->pub_stream, da);
     HIP_TRY(ctx, hipGetLastError());
@@ -2960,7 +2809,7 @@ static int redistribute_streamed(lentil_hip_ctx *ctx, bool *streamed, bool *defe
   const unsigned accept_blocks = (unsigned)(acc_want > acc_max ? acc_max : acc_want);
   hipStream_t tail = ctx->stream;       // the stream the pass's last kernels and its counter read-back are on
   bool lean = false;                    // lean tail (below): no second round in flight
-  if (decoupled && ctx->chain_streams) {
+  if (decoupled) {
     // ---- the decoupled pass with its chain of kernels laid along streams: a dependency that crosses streams costs
     // 40-90 us (event, barrier packet, a queue waking up) where a kernel behind its predecessor on ONE stream costs ~2:
     //   chunk stream : A -> first accept                      (the accept starts as the last first-round solve ends)
@@ -2973,17 +2822,6 @@ static int redistribute_streamed(lentil_hip_ctx *ctx, bool *streamed, bool *defe
     // accept, the first round's stragglers -- has ended before that kernel does, so those waits find their events fired.
     // On the publishers' stream the accept came ~60 us after the stragglers' end: three cross-stream waits in a row.)
     hipStream_t ps = ctx->slow1_stream;
-    if (b_blocks) {
-      // LENTIL_SOLVE_B=1: a third solve block per CU (three waves: one SIMD stays the straggler wave's) behind the scan on its
-      // stream -- it starts when the scan's waves have left, finds the queue complete and never waits; the first accept waits
-      // for it as for A
-      DrawArgs db = da;
-      db.instance = 1;
-      launch_solve_po<true>(ctx, db, ctx->stream, b_blocks, b_threads);
-      HIP_TRY(ctx, hipGetLastError());
-      HIP_TRY(ctx, hipEventRecord(ctx->ev_b, ctx->stream));
-      HIP_TRY(ctx, hipStreamWaitEvent(ch.stream, ctx->ev_b, 0));
-    }
     HIP_TRY(ctx, hipStreamWaitEvent(ch.stream, ctx->pub_done, 0));       // (both long past when A ends)
     HIP_TRY(ctx, hipStreamWaitEvent(ch.stream, ctx->scans_done, 0));
     HIP_TRY(ctx, hipEventRecord(ctx->ev_round, ch.stream));
@@ -2994,37 +2832,21 @@ static int redistribute_streamed(lentil_hip_ctx *ctx, bool *streamed, bool *defe
       // a block per item where that many fit (4 per CU: 4 x 20.7 KB of LDS beside a straggler wave's 10, 16 waves of <= 96 registers)
       const uint64_t m = (uint64_t)ctx->num_cu * (uint64_t)ctx->ready_blocks;
       accept1_blocks = (unsigned)(acc_want > m ? m : acc_want);
-    } else if (lean_pass) {
-      // (measured, same box, headline: 2 / 4 / 5 blocks per CU -> 2.00 / 2.00-2.24 / 2.08-2.30 ms: with more blocks than the
-      // stragglers' LDS leaves room for, every third run sits in a mode 0.25 ms slower.  The knob stays; the default is round 4's.)
-      static const int lean_blocks = getenv("LENTIL_ACCEPT_LEAN_BLOCKS") ? atoi(getenv("LENTIL_ACCEPT_LEAN_BLOCKS")) : 0;
-      if (lean_blocks >= 1) {
-        const uint64_t m = (uint64_t)ctx->num_cu * (uint64_t)(lean_blocks > 6 ? 6 : lean_blocks);
-        const unsigned b = (unsigned)(acc_want > m ? m : acc_want);
-        if (b > accept1_blocks) accept1_blocks = b;
-      }
     }
-    const bool resolves_early = ctx->early_resolve && ctx->F.dir && ctx->F.touched && ctx->n_chunks >= 2 && !ctx->comm && !ctx->closest_deferred;
-    // Lean tail, an option: the frame's resolve does not wait for the first accept.  The whole frame is resolved behind the scan
+    const bool resolves_early = ctx->F.dir && ctx->F.touched && ctx->n_chunks >= 2 && !ctx->comm && !ctx->closest_deferred;
+    // With accept_kernel<3> the frame's resolve does not wait for the first accept.  The whole frame is resolved behind the scan
     // -- the pixels' own sums are complete then, the HBM is idle and the solve waves do not need it --, the groups of pixels
     // the first accept's draws land in are resolved again behind it (about half of a headline frame's groups: 86 us where
-    // the whole frame takes 130), the few groups of the last accept once more at the end.
-    // (LENTIL_RESOLVE_AFTER_SCAN=1; off by default: measured on the headline, same box, 2.00-2.01 ms with it and 1.98-2.00
-    // without -- the resolve is not what the pass ends on, the stragglers and the accept behind them are)
-    // (Round 6, with accept_kernel<3>: on -- the accept behind the stragglers now has a few items where it had nearly all of them,
-    // so the whole-frame resolve would be what the pass ends on; behind the scan it is under the solves, and behind the first
-    // accept only the groups its draws reached are left.  LENTIL_RESOLVE_AFTER_SCAN=0 / 1 decides whatever the accept.)
-    const bool resolve_after_scan = lean_pass && resolves_early && (ctx->resolve_after_scan >= 0 ? ctx->resolve_after_scan == 1 : ready_accept);
+    // the whole frame takes 130), the few groups of the last accept once more at the end.  (The accept behind the stragglers
+    // has a few items, so the whole-frame resolve behind the first accept would be what the pass ends on.)
+    const bool resolve_after_scan = resolves_early && ready_accept;
     if (resolve_after_scan) {
       hipStream_t rs = ctx->chunks[1].stream;
       if (ctx->clear_pending) HIP_TRY(ctx, hipStreamWaitEvent(rs, ctx->ev_clear, 0));      // (it reads the accumulators clear_frame is wiping on the chunk stream)
       HIP_TRY(ctx, hipStreamWaitEvent(rs, ctx->scans_done, 0));
       if ((rc = launch_resolve_half(ctx, rs, 0u))) return rc;
     }
-    if (early) {
-      // (the first accept is at work beside the solve kernel already -- accept_kernel<4>, above; what follows on this stream follows it)
-      HIP_TRY(ctx, hipStreamWaitEvent(ch.stream, ctx->ev_acc1, 0));
-    } else {
+    {
       DrawArgs d0 = da;
       d0.emit_live = lean_pass ? 0 : 1;       // (lean tail: nobody is waiting for tasks)
       d0.lean_defer = lean_pass ? 1 : 0;
@@ -3041,10 +2863,10 @@ static int redistribute_streamed(lentil_hip_ctx *ctx, bool *streamed, bool *defe
       HIP_TRY(ctx, hipEventRecord(ctx->ev_res, rs));
       ctx->early_resolve_pending = true;
     }
-    // Lean tail (extension, ItemLive): the first round's solve kernel has appended what its items needed, so the first accept
-    // is expected to schedule nothing -- no second round's solve and straggler kernels, no waiting for them: the accept of the
-    // items that met parked solves follows the first accept on its stream, behind the first round's stragglers.  Should the
-    // first accept have scheduled tasks after all, that accept does nothing (DrawArgs::lean_gate) and the round is run below.
+    // Lean tail (first batches from the model): the first accept is expected to schedule nothing -- no second round's solve and
+    // straggler kernels, no waiting for them: the accept of the items that met parked solves follows the first accept on its
+    // stream, behind the first round's stragglers.  Should the first accept have scheduled tasks after all, that accept does
+    // nothing (DrawArgs::lean_gate) and the round is run by streamed_finish.
     lean = lean_pass;
     if (lean) {
       hipStream_t ls = ch.stream;
@@ -3054,13 +2876,11 @@ static int redistribute_streamed(lentil_hip_ctx *ctx, bool *streamed, bool *defe
       {
         DrawArgs d2 = da;
         d2.lean_gate = 1;
-        d2.early_accept = 0;          // (every kernel that wrote its results has ended: plain loads)
         d2.slow_indirect = 0; d2.slow_cap = slow_cap_all; d2.slow_live = 0;
         hipLaunchKernelGGL(accept_kernel<2>, dim3(accept_blocks), dim3(256), 0, ls, d2);
       }
       HIP_TRY(ctx, hipGetLastError());
       da.slow_indirect = 0; da.slow_cap = slow_cap_all; da.slow_live = 0;
-      da.early_accept = 0;          // (whatever the host launches behind this pass's kernels reads results they have finished writing)
       if (ctx->early_resolve_pending) {
         HIP_TRY(ctx, hipStreamWaitEvent(ls, ctx->ev_res, 0));
         if ((rc = launch_resolve_half(ctx, ls, 2u))) return rc;
@@ -3074,7 +2894,6 @@ static int redistribute_streamed(lentil_hip_ctx *ctx, bool *streamed, bool *defe
       da.parity = round & 1; da.round = round;
       DrawArgs d1 = da;
       d1.slow_after_producers = 0;      // (its straggler kernel runs beside it from the start)
-      d1.slow_crowd_stays = ctx->crowd_stays_later;
       d1.slow_indirect = 0;
       if (round == 1) {
         d1.no_reset = 1;
@@ -3141,25 +2960,24 @@ static int redistribute_streamed(lentil_hip_ctx *ctx, bool *streamed, bool *defe
   if ((rc = join_clear(ctx))) return rc;       // (this form's accepts are on the main stream)
   // B: the rest of the CUs' room, once the scan's waves have left
   da.instance = 1;
-  if (b_blocks) launch_solve_po<true>(ctx, da, ctx->stream, b_blocks, b_threads);
+  if (b_blocks) launch_solve_po<true>(ctx, da, ctx->stream, b_blocks);
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ch.done, 0));
   HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->pub_done, 0));
-  if (live && !decoupled) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_slow, 0));
-  else if (!live) launch_slow(ctx, da, ctx->stream);
+  if (live) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_slow, 0));
+  else launch_slow(ctx, da, ctx->stream);
   {
     DrawArgs d0 = da;
     d0.emit_live = overlap ? 1 : 0;
     d0.end_tasks = (uint32_t)ctx->num_cu * 4u;
     if (overlap) HIP_TRY(ctx, hipEventRecord(ctx->ev_round, ctx->stream));      // everything the first accept waits for
-    if (decoupled) hipLaunchKernelGGL(accept_kernel<1>, dim3(accept_blocks), dim3(256), 0, ctx->stream, d0);
-    else hipLaunchKernelGGL(accept_kernel<0>, dim3(accept_blocks), dim3(256), 0, ctx->stream, d0);
+    hipLaunchKernelGGL(accept_kernel<0>, dim3(accept_blocks), dim3(256), 0, ctx->stream, d0);
     HIP_TRY(ctx, hipGetLastError());
   }
   // The frame's resolve, first half: behind the first accept, beside the second round's solves (one block per CU, no
   // HBM traffic to speak of) on the otherwise idle second chunk stream.  What later accepts add lands in groups of
   // pixels whose `touched` flag is set by then: lentil_hip_redistribute resolves those once more at its end.
-  if (ctx->early_resolve && ctx->F.dir && ctx->F.touched && ctx->n_chunks >= 2 && !ctx->comm && !ctx->closest_deferred) {
+  if (ctx->F.dir && ctx->F.touched && ctx->n_chunks >= 2 && !ctx->comm && !ctx->closest_deferred) {
     hipStream_t rs = ctx->chunks[1].stream;
     HIP_TRY(ctx, hipEventRecord(ctx->ev_acc1, ctx->stream));
     HIP_TRY(ctx, hipStreamWaitEvent(rs, ctx->ev_acc1, 0));
@@ -3179,8 +2997,6 @@ static int redistribute_streamed(lentil_hip_ctx *ctx, bool *streamed, bool *defe
         d1.no_reset = 1;
         d1.producers_done = &ctx->d_ctr->accept_final[0];      // (set behind the queue's end markers)
         d1.producers_total = 1u;
-        d1.slow_crowd_stays = ctx->crowd_stays_later;
-        if (decoupled) { d1.slow_indirect = 0; d1.slow = slow_base + slow_cap_all / 2u; d1.slow_cap = slow_cap_all - slow_cap_all / 2u - d1.slow_waves; }
         HIP_TRY(ctx, hipStreamWaitEvent(ch.stream, ctx->ev_round, 0));
         launch_solve_po<true>(ctx, d1, ch.stream, (unsigned)ctx->num_cu);
         HIP_TRY(ctx, hipGetLastError());
@@ -3189,10 +3005,10 @@ static int redistribute_streamed(lentil_hip_ctx *ctx, bool *streamed, bool *defe
         hipLaunchKernelGGL(solve_slow_kernel, dim3(d1.slow_waves), dim3(64), coop_lds_bytes(ctx->hlens.n_terms), ctx->pub_stream, d1);
         HIP_TRY(ctx, hipEventRecord(ctx->ev_slow, ctx->pub_stream));
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ch.done, 0));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_slow, 0));      // (decoupled: behind the first round's straggler kernel too)
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_slow, 0));
         // (the first accept and this round's solves are done: the first round's queues can go back to empty for what
         // the accept below schedules)
-        hipLaunchKernelGGL(reset_round_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->d_ctr, 0u, decoupled ? 1u : 0u);
+        hipLaunchKernelGGL(reset_round_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->d_ctr, 0u, 0u);
       } else {
         da.producers_done = nullptr; da.producers_total = 0;
         HIP_TRY(ctx, hipEventRecord(ctx->ev_round, ctx->stream));
@@ -3219,12 +3035,9 @@ static int redistribute_streamed(lentil_hip_ctx *ctx, bool *streamed, bool *defe
     } else {
       launch_solve(ctx, da, ctx->stream, (unsigned)ctx->num_cu);
     }
-    if (decoupled && round == 1) hipLaunchKernelGGL(accept_kernel<2>, dim3(accept_blocks), dim3(256), 0, ctx->stream, da);
-    else hipLaunchKernelGGL(accept_kernel<0>, dim3(accept_blocks), dim3(256), 0, ctx->stream, da);
+    hipLaunchKernelGGL(accept_kernel<0>, dim3(accept_blocks), dim3(256), 0, ctx->stream, da);
     HIP_TRY(ctx, hipGetLastError());
-    if (decoupled && round == 1) { da.slow_indirect = 0; da.slow_cap = slow_cap_all; }
   }
-  da.slow_indirect = 0; da.slow_cap = slow_cap_all;
   da.slow_live = 0;       // (rounds the host adds one by one, below, park and finish their stragglers the plain way)
   if (ctx->early_resolve_pending) {
     // the resolve's second half behind the last accept enqueued blind (should the host have to add rounds, or redo
@@ -3238,35 +3051,16 @@ static int redistribute_streamed(lentil_hip_ctx *ctx, bool *streamed, bool *defe
   ht_mark(ctx, "all_launched");
   ctx->clear_pending = false;       // (every stream of the pass is behind the wipe by now, and the main stream will be behind the pass)
   StreamTail t;
-  t.tail = tail; t.pass_t0 = pass_t0; t.calibrates_now = calibrates_now; t.predicted = predicted; t.lean = lean; t.extend = extend;
+  t.tail = tail; t.pass_t0 = pass_t0; t.calibrates_now = calibrates_now; t.predicted = predicted; t.lean = lean;
   t.live = live; t.inject = da.inject_stall != 0; t.blind_rounds = blind_rounds; t.da = da; t.slow_base = slow_base;
   t.slow_cap_all = slow_cap_all; t.accept_blocks = accept_blocks; t.item_cap = pub.item_cap; t.task_cap = pub.task_cap;
   t.range_cap = plan.sa.range_cap; t.pool_cap = pub.pool_cap; t.stuck_ticks = stuck_ticks;
-  bool have_counters = false;
-  if (ctx->spin_readback && ctx->d_ctr_host) {
-    // The counters by a kernel into the host's copy and a sequence number behind them; the host polls that number.  (A copy
-    // command's completion reaches the waiting thread ~40 us after the device is through: signal, interrupt, wake-up.)
-    const uint32_t seq = ++ctx->seq ? ctx->seq : ++ctx->seq;
-    hipLaunchKernelGGL(report_counters_kernel, dim3(1), dim3(256), 0, tail, reinterpret_cast<const uint32_t *>(ctx->d_ctr),
-                       reinterpret_cast<uint32_t *>(ctx->d_ctr_host), (uint32_t)(sizeof(DevCounters) * C / sizeof(uint32_t)),
-                       reinterpret_cast<uint32_t *>(ctx->d_ctr_host + C), seq);
-    HIP_TRY(ctx, hipGetLastError());
-    const auto spin_t0 = std::chrono::steady_clock::now();
-    uint32_t spins = 0;
-    while (true) {
-      if (__atomic_load_n(ctx->h_seq, __ATOMIC_ACQUIRE) == seq) { have_counters = true; break; }
-      __builtin_ia32_pause();
-      if ((++spins & 0xFFFu) == 0u &&
-          std::chrono::duration<double>(std::chrono::steady_clock::now() - spin_t0).count() > 2.0) break;      // (then the plain way)
-    }
-  }
-  if (!have_counters)
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_ctr_pinned, ctx->d_ctr, sizeof(DevCounters) * C, hipMemcpyDeviceToHost, tail));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->h_ctr_pinned, ctx->d_ctr, sizeof(DevCounters) * C, hipMemcpyDeviceToHost, tail));
   // The asynchronous end (lentil_hip_ctx::async_end): the lean tail is the pass that expects to have nothing left to do, and the
   // frame takes nothing but gaussian splats (closest-filtered AOVs, lentil_debug and cryptomatte have host steps behind the pass).
   // Everything of the pass is behind `tail` by now (the lean tail's accepts wait for the scan, the publishers, the stragglers
   // and the early resolve); the context's own stream waits for it in turn, so whatever the caller enqueues next follows the pass.
-  const bool defer = ctx->async_end && lean && !have_counters && !ctx->spin_readback && !ctx->crypto && !ctx->F.zkey && !ctx->F.zkey_dbg &&
+  const bool defer = ctx->async_end && lean && !ctx->crypto && !ctx->F.zkey && !ctx->F.zkey_dbg &&
                      !ctx->comm && !ctx->closest_deferred && !da.inject_stall && !host_trace_passes() && ctx->inflight.size() < 2;
   if (defer) {
     lentil_hip_ctx::Slot &sl = ctx->slots[ctx->slot];
@@ -3283,7 +3077,7 @@ static int redistribute_streamed(lentil_hip_ctx *ctx, bool *streamed, bool *defe
     *streamed = true;
     return LENTIL_OK;
   }
-  if (!have_counters) HIP_TRY(ctx, hipStreamSynchronize(tail));
+  HIP_TRY(ctx, hipStreamSynchronize(tail));
   ht_mark(ctx, "tail_synced");
   if (tail != ctx->stream) {
     // everything the pass enqueued anywhere is behind the read-back that has just arrived; what the caller enqueues on
@@ -3754,12 +3548,6 @@ static void harvest_ready(lentil_hip_ctx *ctx) {
 static int begin_slot(lentil_hip_ctx *ctx) {
   lentil_hip_ctx::Slot &cur = ctx->slots[ctx->slot];
   cur.timed_draw = ctx->timed_draw; cur.timed_resolve = ctx->timed_resolve; cur.scan_kernel_timed = ctx->scan_kernel_timed;
-  if (ctx->spin_readback) {        // (LENTIL_SPIN_READBACK: one block, addressed by the device -- no rotation, no asynchronous end)
-    flush_timing(ctx, ctx->slot, true);
-    ctx->timed_draw = ctx->timed_resolve = false; ctx->scan_kernel_timed = false;
-    cur.timing_open = true;
-    return LENTIL_OK;
-  }
   const int next = (ctx->slot + 1) % 3;
   // (at most two passes in flight unobserved: with two there already this one waits for the older -- the device still has the newer to work on)
   while (ctx->inflight.size() >= 2 || (!ctx->inflight.empty() && ctx->inflight.front().slot == next)) {

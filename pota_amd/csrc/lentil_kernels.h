@@ -51,10 +51,9 @@ struct DevCounters {
   unsigned int stuck, tile_next;       // a wave gave up waiting for its queue slot (kStuckTicks): the pass is void; scan_dma_kernel's tile cursor
   // a candidate for a closest-filtered AOV came with |Z| == 0 or NaN (closest_key_of): the pass is refused, see there
   unsigned int degenerate_depth, pad_;
-  // Streamed pass with extension (ItemLive): items whose current batch is not complete yet / the task queue has its end
-  // markers / tasks and items the solve waves added themselves
-  unsigned int items_open, queue_final, ext_tasks, ext_items;
-  unsigned int ext_n, ext_head, pad2_[2];        // the extension's own task queue (DrawArgs::ext_q): tasks appended / tickets drawn
+  // (unused: keeps the words below at the offsets they have always had -- which of the atomically updated counters share a
+  // cache line moves with them)
+  unsigned int reserved_[8];
   // diagnostics of a stall (lentil_hip_last_redo_note): accept blocks that have begun, per round parity; what the wave that
   // gave up first saw -- round, parity, the queue's n_tasks, accept_done[0], accept_started[0], its slot's tag word, block
   unsigned int accept_started[2];
@@ -67,9 +66,6 @@ struct DevCounters {
   // accept's last item was finished with blocks of its grid still not begun (lentil_hip_last_redo_note prints it)
   unsigned int probe_accept_xcc[8], probe_res_xcc[3][8];
   unsigned int probe_snap[1 + 8 + 24 + 2];
-  // DrawArgs::early_accept: items whose first batch is complete (every result delivered, parked solves counted as delivered),
-  // pushed by the solve wave that delivered the last one / tickets drawn on that queue by accept_kernel<4>
-  unsigned int n_ready, ready_head;
 };
 
 LD_DEV uint32_t xcc_id() { return (uint32_t)__builtin_amdgcn_s_getreg((3 << 11) | 20) & 7u; }      // HW_REG_XCC_ID[3:0]
@@ -181,11 +177,7 @@ struct ItemHdr {          // written by prep_items_kernel / publish_item; a 128-
   // in the record; accept_kernel<3> -- behind the solve kernel, beside the stragglers -- takes an item whose two counts agree and
   // leaves the others to the accept behind the stragglers.
   uint32_t parked, parked_done;
-  // DrawArgs::early_accept: results the item's first batch holds (one per try and channel) / results delivered so far.  One
-  // 8-byte word: the solve wave that delivers results adds to the high half with ONE returning atomic and reads the low half
-  // from what it returns; the wave whose add makes the two equal pushes the item onto the ready queue.
-  uint32_t issued, delivered;
-  uint32_t pad[20];
+  uint32_t pad[22];
 };
 static_assert(sizeof(ItemHdr) == 128, "ItemHdr is a 128-byte line");
 
@@ -204,33 +196,6 @@ struct ItemProg {         // 48 B, progress of an item across rounds
   uint32_t p_lo, p_hi, p_off;
   uint32_t n_end1;        // attempts the first accept looked at
 };
-
-// Streamed pass, "extension" (round 4).  An item near the frame's edge loses attempts to draws that land outside the frame
-// and needs more than its first batch -- 33 of the headline frame's 1 168 items, 3 % more solves -- and the round that
-// used to serve them (first accept -> tasks -> solves -> their stragglers -> second accept) was 0.4 ms of latency at the
-// end of a 2 ms pass.  Now the first round's solve kernel looks after them itself: every result it delivers is counted per
-// item (one returning atomic per item and wave flush), and the wave that delivers the LAST result of an item's batch
-// compares the successes with what the item needs; if they fall short it appends the next batch's tasks to the very queue
-// it is working on -- sized like accept_next_batch would, from the item's own success rate -- and the item stays open.
-// The queue's end markers are written when the last publisher has signed off AND no item is open (whoever sees both).
-// The result pool holds 5 x samples + retries slots per item from the start, so an item's batches stay contiguous; the
-// first accept takes the batch's end from here.  What it then finds missing (an estimate that was too kind) still goes
-// the old way.  One 32-byte record per item, written through (another CU's waves read it while the kernel runs).
-// MEASURED (round 4, headline frame) AND OFF BY DEFAULT (LENTIL_EXTEND=1 switches it on): draw lists stay bit-identical, the
-// second round disappears (811 appended tasks, no item short in the accept) -- and the pass takes 2.30 ms instead of 2.00.
-// The second round was never idle time: the item found last by the scan needs its first batch (0.15 ms), the batch
-// behind it (0.15 ms) and that batch's slowest solves (100 Newton iterations: 0.25-0.35 ms on a straggler wave) one after
-// the other whoever schedules them, and the old layout runs the first accept of the other 1 100 items BESIDE that chain,
-// this one behind it.
-// The appended batches have a queue of their own (DrawArgs::ext_q), served by the solve kernel's first `ext_keeper_blocks`
-// blocks once the main queue has ended: the other blocks leave as they always did -- the straggler kernel's waves are only
-// placed when solve waves leave -- and the main queue's end does not wait for the items near the frame's edge.
-struct ItemLive {
-  unsigned long long cnt;        // results delivered so far: count (bits 0-20), pixels (21-41), outside the frame (42-62)
-  unsigned long long hi_s;       // R(m) issued so far: [0, m_hi) (low word), samples (high word)
-  uint32_t res_off, pad[3];
-};
-static_assert(sizeof(ItemLive) == 32, "ItemLive is 32 bytes");
 
 struct Task {             // up to 64 consecutive m of one item (and one wavelength channel)
   uint32_t item, m_base, res_off, count;   // count: bits 0-7 number of m, bits 8-9 channel
@@ -258,9 +223,6 @@ struct StreamPub {
   ItemProg *prog;
   uint32_t *active0;
   Task *tasks0;
-  ItemLive *live;              // non-null: extension (ItemLive)
-  Task *ext_q;                 // ... its task queue and the waves that serve it (end markers)
-  uint32_t ext_keepers;
   BatchModelDev model;         // land non-null: first batches sized from the lens and the frame (lentil_batch_model.h)
 };
 
@@ -304,26 +266,6 @@ __global__ void probe_wait_kernel(uint32_t *flag, uint32_t *seen) {
   }
   *seen = 1u;
 }
-// The pass's counters straight into the host's (pinned, device-visible) copy, then a sequence number behind them: the host
-// reads them as soon as they have crossed the bus, without a copy command's completion signal and the wake-up behind it
-// (redistribute_streamed; ~40 us of a 2 ms pass).  One block.
-__global__ __launch_bounds__(256) void report_counters_kernel(const uint32_t *src, uint32_t *host_dst, uint32_t n_words,
-                                                              uint32_t *host_seq, uint32_t seq) {
-  for (uint32_t i = threadIdx.x; i < n_words; i += blockDim.x)
-    __hip_atomic_store(host_dst + i, __hip_atomic_load(src + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __threadfence_system();
-  __syncthreads();
-  if (threadIdx.x == 0) __hip_atomic_store(host_seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// LENTIL_A_FIRST=1 (experiment): ahead of a streamed pass's scan on its stream -- the scan's blocks are dispatched when the
-// resident solve kernel's waves have their registers (waves_started), so that those lie in one piece at the bottom of
-// every SIMD's file and what the scan's waves give back is one piece too (a third solve block fits it, LENTIL_SOLVE_B).
-__global__ void wait_waves_kernel(const DevCounters *ctr, uint32_t want, uint64_t max_ticks) {
-  const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-  while (ld_coherent32(&ctr->waves_started[0]) < want && __builtin_amdgcn_s_memrealtime() - t0 < max_ticks) __builtin_amdgcn_s_sleep(8);
-}
-
 __global__ void probe_set_kernel(uint32_t *flag) { (void)__hip_atomic_exchange(flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 constexpr uint32_t kEndCount = 0xFFu;       // Task::count of the end-of-queue markers behind the last task
@@ -479,17 +421,15 @@ LD_DEV uint32_t first_batch_hi(uint32_t samples, uint32_t retries, uint32_t extr
 // still fills the task slots it reserved (with empty tasks), so that no ticket waits for a slot that never comes.
 LD_DEV void publish_item(const lentil_params &P, const VisitsDev &V, const StreamPub &S, DevCounters *ctr, uint32_t item, uint2 wi,
                          uint32_t count, const float cs[3]) {
-  const uint32_t retries = (uint32_t)S.retries, nch = S.n_channels;
+  const uint32_t nch = S.n_channels;
   const uint32_t nt = (count + 63u) / 64u;
-  // (extension: room for every R(m) the item can ever ask for, so that later batches lie behind the first)
-  const uint32_t reserve = S.live ? wi.y * 5u + retries : count;
-  const unsigned long long off = atomicAdd(&ctr->pool_used[0], (unsigned long long)reserve * nch);
+  const unsigned long long off = atomicAdd(&ctr->pool_used[0], (unsigned long long)count * nch);
   const uint32_t tb = atomicAdd(&ctr->n_tasks[0], nt * nch);
-  const bool ok = item < S.item_cap && off + (unsigned long long)reserve * nch <= S.pool_cap &&
+  const bool ok = item < S.item_cap && off + (unsigned long long)count * nch <= S.pool_cap &&
                   (unsigned long long)tb + nt * nch <= S.task_cap;
   // (which bound it was, for lentil_hip_last_redo_note: 1 items, 2 result pool, 4 task queue)
   if (!ok) atomicOr(&ctr->fallback, (item < S.item_cap ? 0ull : 1ull) |
-                                    (off + (unsigned long long)reserve * nch <= S.pool_cap ? 0ull : 2ull) |
+                                    (off + (unsigned long long)count * nch <= S.pool_cap ? 0ull : 2ull) |
                                     ((unsigned long long)tb + nt * nch <= S.task_cap ? 0ull : 4ull));
   if (item < S.item_cap) {
     const uint32_t v = wi.x;
@@ -502,20 +442,12 @@ LD_DEV void publish_item(const lentil_params &P, const VisitsDev &V, const Strea
     st_agent64(d + 2, (uint64_t)__double_as_longlong(hd.tz));
     st_agent64(d + 3, (uint64_t)hd.seed_a | ((uint64_t)(uint32_t)hd.px_py << 32));
     st_agent64(d + 4, 0ull);          // ItemHdr::parked / parked_done
-    st_agent64(d + 5, ok ? (uint64_t)count * nch : 0ull);      // ItemHdr::issued / delivered
     ItemProg pg{};
     pg.m_lo = 0;
     pg.m_hi = ok ? count : 0u;
     pg.res_off = (uint32_t)off;
     S.prog[item] = pg;
     S.active0[item] = item;
-    if (S.live && ok) {
-      ItemLive *L = S.live + item;
-      st_agent64(&L->cnt, 0ull);
-      st_agent64(&L->hi_s, (uint64_t)count | ((uint64_t)(wi.y & 0xFFFFu) << 32));
-      st_agent32(&L->res_off, (uint32_t)off);
-      atomicAdd(&ctr->items_open, 1u);
-    }
   }
   // the header must have arrived before a task that names the item can be seen
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -2032,26 +1964,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void pu
   uint32_t last = 0;
   if (lane == 0) last = atomicAdd(&a.ctr->publishers_done, 1u) == gridDim.x - 1u ? 1u : 0u;
   if (!__builtin_amdgcn_readfirstlane(last)) return;
-  // the last publisher: the task queue is complete -- unless items are still open (extension, ItemLive): then whoever
-  // closes the last of them writes the markers (live_close_queue)
-  // One end marker for every solve wave that may hold a ticket.
+  // the last publisher: the task queue is complete.  One end marker for every solve wave that may hold a ticket.
   const uint32_t n = ld_coherent32(&a.ctr->n_tasks[0]);
   for (uint32_t i = lane; i < a.end_tasks; i += 64u)
     if ((uint64_t)n + i < a.S.task_cap)
       st_agent64(reinterpret_cast<uint64_t *>(a.S.tasks0 + n + i) + 1,
                  (uint64_t)(kEndCount | (a.S.epoch << kTaskTagShift)) << 32);
-  // extension (ItemLive): its queue ends when no item is open any more -- now, or when a solve wave closes the last one
-  if (a.S.live) {
-    uint32_t open = 0;
-    if (lane == 0) open = ld_coherent32(&a.ctr->items_open);
-    if (__builtin_amdgcn_readfirstlane(open) != 0u) return;
-    if (lane == 0) st_agent32(&a.ctr->queue_final, 1u);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const uint32_t ne = ld_coherent32(&a.ctr->ext_n);
-    for (uint32_t i = lane; i < a.S.ext_keepers; i += 64u)
-      if ((uint64_t)ne + i < a.S.task_cap)
-        st_agent64(reinterpret_cast<uint64_t *>(a.S.ext_q + ne + i) + 1, (uint64_t)(kEndCount | (a.S.epoch << kTaskTagShift)) << 32);
-  }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2135,7 +2053,6 @@ struct DrawArgs {
   int32_t slow_at;         // Newton iterations after which a solve counts as a straggler
   int32_t slow_max_lanes;  // a dry wave parks only when at most this many of its lanes are still busy
   int32_t slow_nap_max;    // an idle straggler wave sleeps 1.7 us x 1, 2, 4 ... up to this many between polls of its queue slot (0: 8)
-  int32_t slow_prio;       // s_setprio of the straggler kernel's waves (their chains of iterations end the pass; LENTIL_SLOW_PRIO)
   int32_t dispatch_probe;  // LENTIL_DISPATCH_PROBE: DevCounters::probe_*
   int32_t round;           // solve/accept round of the chunk (0 = first batch)
   int32_t slow_from_round; // parking starts with this round: the first round's own ramp-down hides most of its stragglers
@@ -2178,30 +2095,14 @@ struct DrawArgs {
   uint32_t unknown_credit;    // accept_item<1>: eighths of the known attempts' success rate credited to the unknown ones (0: none)
   int32_t slow_after_producers;   // first round of a streamed pass: park only once the scan and its publishers have ended
   int32_t slow_dry_only;      // live queue: park as a plain round does (waves running dry, their last slow_max_lanes lanes)
-  int32_t slow_crowd_stays;   // live queue: where more than slow_max_lanes lanes of a wave are past slow_at at once, none is parked
-  int32_t accept_narrow;      // accept kernels: 256-attempt steps (accept_item) where accept_item_wide would apply
   // test hook (LENTIL_INJECT_STALL): the first accept of a streamed pass never closes the queue it feeds, so the second round's
   // resident solve waves give up after kStuckTicks -- a pass stalled with draws already accepted, which the host must recover
   int32_t inject_stall;
-  ItemLive *live;             // streamed pass with extension (ItemLive): the first round's solve kernel and the first accept
-  Task *ext_q;                // ... the queue of the batches it appends, served by its first ext_keeper_blocks blocks
-  uint32_t ext_keeper_blocks;
-  uint32_t ext_end_tasks;     // ... end markers behind that queue (one per wave of those blocks)
-  uint32_t ext_slack;         // ... successes beyond `samples` an item's results must show before it counts as served
-  // Lean tail of a streamed pass with extension: no second round's solve kernels are in flight.  The accept behind the first
-  // one (accept_kernel<2>) does nothing if the first one had to schedule tasks after all (n_tasks of its parity): the host then
-  // runs that round the ordinary way and this accept after it.
   uint64_t stuck_ticks;       // how long a resident wave waits for a queue slot before it declares the pass stuck (0: kStuckTicks)
+  // Lean tail of a streamed pass: no second round's solve kernels are in flight.  The accept behind the first one
+  // (accept_kernel<2>) does nothing if the first one had to schedule tasks after all (n_tasks of its parity): the host then
+  // runs that round the ordinary way and this accept after it.
   int32_t lean_gate;
-  // Round 6, the first accept BESIDE the first round's solves (accept_kernel<4>): the solve kernel writes its results through
-  // (agent-scope atomics, like every other word another CU reads while a kernel runs), counts them per item
-  // (ItemHdr::delivered) and pushes an item whose batch is complete onto `ready_q` (tagged slots, never cleared); the accept
-  // -- launched behind the publishers, when the scan's LDS and registers are free -- draws tickets on that queue and walks the
-  // items as they come, with the solve kernel still at work on the others.  What is left when the last solve wave exits is
-  // the items completed last, not the whole frame's accept.
-  int32_t early_accept;
-  uint32_t ready_cap;
-  uint64_t *ready_q;
   int32_t item_ready;         // streamed pass, lean tail: parked solves are counted per item (ItemHdr::parked / parked_done) for accept_kernel<3>
   int32_t lean_defer;         // ... and the first accept leaves an item that met parked solves to that accept whole: what it still
                               // needs is decided there, from the stragglers' results
@@ -2212,30 +2113,8 @@ LD_DEV uint64_t slow_tag(const DrawArgs &a, uint64_t what) {
   return ((uint64_t)((a.epoch << 8) | (r & 0xFFu)) << 32) | what;
 }
 
-// DrawArgs::early_accept: `cnt` results of `item` have been written through (and waited for); the item whose batch is complete with
-// them goes onto the ready queue.  Called by one lane.
-LD_DEV void ready_deliver(const DrawArgs &a, uint32_t item, uint32_t cnt) {
-  const unsigned long long old = atomicAdd(reinterpret_cast<unsigned long long *>(&a.hdr[item].issued), (unsigned long long)cnt << 32);
-  const uint32_t issued = (uint32_t)old, delivered = (uint32_t)(old >> 32) + cnt;
-  if (issued != 0u && delivered == issued) {
-    const uint32_t slot = atomicAdd(&a.ctr->n_ready, 1u);
-    if (slot < a.ready_cap) st_agent64(a.ready_q + slot, (uint64_t)item | ((uint64_t)((a.epoch << 8) | 1u) << 32));
-  }
-}
-
 LD_DEV ItemVisit load_item_visit(const DrawArgs &a, uint32_t item, double lens_length) {
   return load_work_visit(a.P, a.V, a.work[item], lens_length);
-}
-
-// an item's progress record as an accept kernel takes it: with extension (ItemLive) the first round's batch ends where
-// the solve kernel's last appended batch does
-LD_DEV ItemProg load_prog(const DrawArgs &a, uint32_t item) {
-  ItemProg pg = a.prog[item];
-  if (a.live && a.round == 0) {
-    const uint32_t hi = (uint32_t)a.live[item].hi_s;       // (low word: the batch's end; flags sit in the high word)
-    if (hi > pg.m_hi && pg.m_hi != 0u) pg.m_hi = hi;
-  }
-  return pg;
 }
 
 // emit the solve tasks for m in [m_lo, m_hi) of `item` into the queues of round parity `par`
@@ -2349,100 +2228,6 @@ LD_DEV uint32_t solve_result(const lentil_params &P, const LensT &L, const Newto
   return po_sensor_to_pixel(P, sx, sy, pix) ? pix : kCodeOut;
 }
 
-// ---- extension (ItemLive): results delivered, batches closed, queues ended ----------------------------------------
-// One lane reports `cnt` results of `item`, `okc` of them pixels.  Returns 0, or 1 if that closed the LAST open item while
-// the publishers have all signed off: the caller's wave then writes the queue's end markers (live_close_queue).
-constexpr uint64_t kLiveEarly = 1ull << 62, kLiveClosed = 1ull << 63;     // ItemLive::hi_s flags
-constexpr uint32_t kLiveEarlyAt = 256u;                                    // results after which an item is first looked at
-LD_DEV bool cas64(unsigned long long *p, unsigned long long expect, unsigned long long desired) {
-  return atomicCAS(p, expect, desired) == expect;
-}
-// append R(m_hi .. new_hi) of `item` to the extension's queue (the caller has moved ItemLive::hi_s to new_hi)
-LD_DEV void live_emit(const DrawArgs &a, ItemLive *L, uint32_t item, uint32_t m_hi, uint32_t new_hi) {
-  const uint32_t count = new_hi - m_hi, nt = (count + 63u) / 64u;
-  const uint32_t tb = atomicAdd(&a.ctr->ext_n, nt);
-  const bool fits = (unsigned long long)tb + nt + a.ext_end_tasks <= a.task_cap;
-  if (!fits) atomicAdd(&a.ctr->overflow, 1ull);        // (the queue is as long as the main one: not reached; the pass would be void)
-  const uint32_t res0 = ld_coherent32(&L->res_off);
-  for (uint32_t t = 0; t < nt && fits; ++t) st_agent64(a.ext_q + tb + t, (uint64_t)item | ((uint64_t)(m_hi + t * 64u) << 32));
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  for (uint32_t t = 0; t < nt && fits; ++t) {
-    const uint32_t c = (count - t * 64u) < 64u ? (count - t * 64u) : 64u;
-    st_agent64(reinterpret_cast<uint64_t *>(a.ext_q + tb + t) + 1,
-               (uint64_t)(res0 + m_hi + t * 64u) | ((uint64_t)(c | (a.epoch << kTaskTagShift)) << 32));
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  atomicAdd(&a.ctr->ext_tasks, nt);
-  atomicAdd(&a.ctr->ext_items, 1u);
-}
-LD_DEV uint32_t live_deliver(const DrawArgs &a, uint32_t item, uint32_t cnt, uint32_t okc, uint32_t outc) {
-  ItemLive *L = a.live + item;
-  const unsigned long long old = atomicAdd(&L->cnt, (unsigned long long)cnt | ((unsigned long long)okc << 21) | ((unsigned long long)outc << 42));
-  const uint32_t done0 = (uint32_t)old & 0x1FFFFFu;
-  const uint32_t done = done0 + cnt, ok = ((uint32_t)(old >> 21) & 0x1FFFFFu) + okc, out = ((uint32_t)(old >> 42) & 0x1FFFFFu) + outc;
-  const unsigned long long hs = ld_coherent64(&L->hi_s);
-  const uint32_t m_hi = (uint32_t)hs, S = (uint32_t)(hs >> 32) & 0xFFFFu;
-  const uint32_t retries = (uint32_t)a.retries, m_limit = S * 5u + retries;
-  const uint32_t n = m_hi - retries;          // attempts the issued results cover
-  if (done != m_hi) {
-    // Not the batch's last result.  The first look at an item, after kLiveEarlyAt of its results: where those say that the
-    // batch will fall short -- an attempt is decided by the first of its tries that is not vignetted, a pixel or a point
-    // outside the frame, so about n * pixels / (pixels + outside) of n attempts succeed -- the rest is appended NOW, beside
-    // the batch, not behind it (behind it the items found last ended the pass 0.2 ms later).  Sized from the lower end of what
-    // the sample allows (two standard deviations), + 10 % + 32.
-    if (done0 < kLiveEarlyAt && done >= kLiveEarlyAt && !(hs & (kLiveEarly | kLiveClosed)) && ok + out >= 32u && m_hi < m_limit) {
-      const float k = (float)(ok + out), f = (float)ok / k;
-      float f_lo = f - 2.0f * sqrtf(f * (1.0f - f) / k);
-      if (f_lo < 0.02f) f_lo = 0.02f;
-      if ((float)n * f_lo < (float)(S + a.ext_slack)) {
-        float want = (float)(S + a.ext_slack) / f_lo;
-        want = want * 1.1f + 32.0f + (float)retries;
-        const uint32_t new_hi = want >= (float)m_limit ? m_limit : (uint32_t)want;
-        if (new_hi > m_hi && cas64(&L->hi_s, hs, (hs & 0xFFFFFFFF00000000ull) | (unsigned long long)new_hi | kLiveEarly))
-          live_emit(a, L, item, m_hi, new_hi);
-      }
-    }
-    return 0u;
-  }
-  // The batch is complete (parked solves are not known yet and count as neither pixel nor outside).  Served when the
-  // estimate is ext_slack beyond `samples`; else the next batch, sized like accept_next_batch does it.
-  uint32_t est = (ok + out) ? (uint32_t)(((unsigned long long)n * ok) / (ok + out)) : 0u;
-  {
-    // ... less the attempts all of whose tries are vignetted (a share f of the results fails in the lens or is still parked: f to
-    // the power of retries + 1 of the attempts), and 1 % for what the counts cannot know
-    const float f = done ? (float)(done - ok - out) / (float)done : 0.0f;
-    float lost = 1.0f;
-    for (uint32_t t = 0; t <= retries && t < 32u; ++t) lost *= f;
-    const float e2 = (float)est * (1.0f - lost) - 0.01f * (float)S;
-    est = e2 > 0.0f ? (uint32_t)e2 : 0u;
-  }
-  if (est < S + a.ext_slack && m_hi < m_limit) {
-    const uint32_t remaining = S + a.ext_slack - est;
-    unsigned long long need = est ? ((unsigned long long)remaining * n + est - 1u) / est : (unsigned long long)(m_limit - m_hi);
-    need += need / 4u + 32u;
-    unsigned long long hi2 = (unsigned long long)m_hi + need;
-    if (hi2 > m_limit) hi2 = m_limit;
-    if (cas64(&L->hi_s, hs, (hs & 0xFFFFFFFF00000000ull) | hi2)) live_emit(a, L, item, m_hi, (uint32_t)hi2);
-    return 0u;                              // the item stays open (or somebody else has just moved its end)
-  }
-  // served (or out of attempts): the item is closed -- unless its end has just been moved
-  if (!cas64(&L->hi_s, hs, hs | kLiveClosed)) return 0u;
-  const uint32_t open_before = atomicSub(&a.ctr->items_open, 1u);
-  if (open_before != 1u) return 0u;
-  return ld_coherent32(a.producers_done) >= a.producers_total ? 1u : 0u;
-}
-// all lanes of a wave: the end markers behind the extension's task queue
-LD_DEV void live_close_queue(const DrawArgs &a, uint32_t lane) {
-  if (lane == 0) st_agent32(&a.ctr->queue_final, 1u);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  uint32_t n = 0;
-  if (lane == 0) n = ld_coherent32(&a.ctr->ext_n);
-  n = (uint32_t)__builtin_amdgcn_readfirstlane((int)n);
-  for (uint32_t i = lane; i < a.ext_end_tasks; i += 64u)
-    if ((uint64_t)n + i < a.task_cap)
-      st_agent64(reinterpret_cast<uint64_t *>(a.ext_q + n + i) + 1, (uint64_t)(kEndCount | (a.epoch << kTaskTagShift)) << 32);
-}
-
 // ---- solve, polynomial optics ------------------------------------------------------------------
 // kChroma: tasks carry a wavelength channel (src/lentil_filter.cpp:255-268); every lane then reads the lens
 // header through its own pointer into three LDS copies that differ in the lambda powers only.
@@ -2472,7 +2257,6 @@ __global__ __launch_bounds__(256) LENTIL_SOLVE_ATTR void solve_po_kernel(DrawArg
   __shared__ double s_ap[4][64][2];
   __shared__ double s_fin[4][6][64];                  // x, y, dx, dy, out[0], out[1]
   __shared__ uint32_t s_fin_err[4][64], s_fin_res[4][64];      // error bits | channel << 8; result slot
-  __shared__ uint32_t s_fin_item[4][64];                       // extension (ItemLive): whose result it is
   if (kTables) {
     const uint32_t nt = a.lens->n_terms;
     for (uint32_t i = threadIdx.x; i < nt; i += blockDim.x) s_terms[i] = a.terms[i];
@@ -2523,15 +2307,6 @@ __global__ __launch_bounds__(256) LENTIL_SOLVE_ATTR void solve_po_kernel(DrawArg
   uint32_t res_idx = 0, cur_chan_lane = 0, my_item = 0;
   (void)cur_chan_lane;
   const uint32_t wv = threadIdx.x >> 6;
-  // extension (ItemLive): the first round of a streamed pass counts what it delivers per item and appends batches itself
-  const bool extend = kStream && !kChroma && a.live != nullptr && a.round == 0;
-  const bool early = kStream && !kChroma && a.early_accept != 0 && a.round == 0;       // accept_kernel<4> beside this kernel (DrawArgs::early_accept)
-  bool close_queue = false;      // this wave closed the last open item: it writes the queue's end markers
-  const bool keeper = extend && blockIdx.x < a.ext_keeper_blocks;
-  bool on_ext = false;
-  const Task *tq = a.tasks[(uint32_t)a.parity];
-  unsigned int *tq_head = &a.ctr->task_head[(uint32_t)a.parity];
-  (void)keeper; (void)on_ext; (void)tq; (void)tq_head;
   uint32_t cur_pos = 0;        // wave-uniform: units of the current task handed out so far (index into s_ap)
   uint32_t fin_n = 0;          // wave-uniform: finished solves waiting in s_fin
   // the finished solves of the queue, one per lane: the tail of trace_ray_bw_po + sensor -> pixel (solve_result)
@@ -2540,8 +2315,6 @@ __global__ __launch_bounds__(256) LENTIL_SOLVE_ATTR void solve_po_kernel(DrawArg
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-    bool fin_ok = false, fin_out = false;
-    uint32_t fin_item = 0;
     if (lane < fin_n) {
       NewtonState t;
       t.x = s_fin[wv][0][lane]; t.y = s_fin[wv][1][lane]; t.dx = s_fin[wv][2][lane]; t.dy = s_fin[wv][3][lane];
@@ -2551,44 +2324,11 @@ __global__ __launch_bounds__(256) LENTIL_SOLVE_ATTR void solve_po_kernel(DrawArg
       t.error = (int)(ew & 0xFFu);
       LensT Lf = L;
       if constexpr (kChroma) Lf.k = &s_kc[(ew >> 8) & 3u];
-      const uint32_t code = solve_result(P, Lf, t);
-      if (early) st_agent32(res + s_fin_res[wv][lane], code);      // (read by accept_kernel<4> on another CU while this kernel runs)
-      else res[s_fin_res[wv][lane]] = code;
-      fin_ok = code < kCodePendingBase;
-      fin_out = code == kCodeOut;
-      fin_item = s_fin_item[wv][lane];
-    }
-    if (early) {
-      // every result of this flush is out before any of them is counted; then per item of the queue (usually one or two)
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      unsigned long long todo = __ballot(lane < fin_n);
-      while (todo) {
-        const int leader = __builtin_ctzll(todo);
-        const uint32_t it = (uint32_t)__builtin_amdgcn_readlane((int)fin_item, leader);
-        const unsigned long long same = __ballot(lane < fin_n && fin_item == it) & todo;
-        if ((int)lane == leader) ready_deliver(a, it, (uint32_t)__builtin_popcountll(same));
-        todo &= ~same;
-      }
-    }
-    if (extend) {
-      // per item of the queue: how many results, how many of them pixels / outside the frame (usually one or two items)
-      unsigned long long todo = __ballot(lane < fin_n);
-      const unsigned long long okm = __ballot(lane < fin_n && fin_ok), outm = __ballot(lane < fin_n && fin_out);
-      while (todo) {
-        const int leader = __builtin_ctzll(todo);
-        const uint32_t it = (uint32_t)__builtin_amdgcn_readlane((int)fin_item, leader);
-        const unsigned long long same = __ballot(lane < fin_n && fin_item == it) & todo;
-        uint32_t r = 0;
-        if ((int)lane == leader)
-          r = live_deliver(a, it, (uint32_t)__builtin_popcountll(same), (uint32_t)__builtin_popcountll(same & okm), (uint32_t)__builtin_popcountll(same & outm));
-        if (__ballot(r != 0u)) close_queue = true;
-        todo &= ~same;
-      }
+      res[s_fin_res[wv][lane]] = solve_result(P, Lf, t);
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
     __builtin_amdgcn_wave_barrier();
     fin_n = 0u;
-    if (close_queue) { live_close_queue(a, lane); close_queue = false; }       // (wherever the flush was called from)
   };
   // a task has been taken (cur_* set, its header in s_hdr[wv]): the aperture draws of all its units at once --
   // the reference's try with seed (seed_a, m), src/lentil.h:596-609
@@ -2628,14 +2368,14 @@ __global__ __launch_bounds__(256) LENTIL_SOLVE_ATTR void solve_po_kernel(DrawArg
         if constexpr (kStream) {
           if (ticket == kNoTicket) {
             uint32_t q = 0;
-            if (lane == 0) q = atomicAdd(tq_head, 1u);
+            if (lane == 0) q = atomicAdd(&a.ctr->task_head[par], 1u);
             ticket = __builtin_amdgcn_readfirstlane(q);
             polls = 0;
             ticket_t0 = __builtin_amdgcn_s_memrealtime();
           }
           if (ticket >= a.task_cap) { no_more = true; break; }
           uint64_t w1 = 0;
-          if (lane == 0) w1 = ld_coherent64(reinterpret_cast<const uint64_t *>(tq + ticket) + 1);
+          if (lane == 0) w1 = ld_coherent64(reinterpret_cast<const uint64_t *>(tasks + ticket) + 1);
           const uint32_t w1_hi = __builtin_amdgcn_readfirstlane((uint32_t)(w1 >> 32));
           if ((w1_hi >> kTaskTagShift) != a.epoch) {
             if (lane == 0) tl_add(TL_POLLS_EMPTY, 1u);
@@ -2652,13 +2392,11 @@ __global__ __launch_bounds__(256) LENTIL_SOLVE_ATTR void solve_po_kernel(DrawArg
             break;
           }
           if ((w1_hi & 0xFFu) == kEndCount) {      // behind the last task
-            // (extension: the first blocks of the launch go on with the queue of the batches the solve waves append)
-            if (keeper && !on_ext) { on_ext = true; tq = a.ext_q; tq_head = &a.ctr->ext_head; ticket = kNoTicket; continue; }
             no_more = true;
             break;
           }
           uint64_t w0 = 0;
-          if (lane == 0) w0 = ld_coherent64(reinterpret_cast<const uint64_t *>(tq + ticket));
+          if (lane == 0) w0 = ld_coherent64(reinterpret_cast<const uint64_t *>(tasks + ticket));
           cur_item = __builtin_amdgcn_readfirstlane((uint32_t)w0);
           cur_m = __builtin_amdgcn_readfirstlane((uint32_t)(w0 >> 32));
           cur_res = __builtin_amdgcn_readfirstlane((uint32_t)w1);
@@ -2714,9 +2452,6 @@ __global__ __launch_bounds__(256) LENTIL_SOLVE_ATTR void solve_po_kernel(DrawArg
       }
       cur_pos += take; cur_res += take; cur_left -= take; filled += take;
     }
-    // (extension: an item's batch is judged when its last result is DELIVERED -- a wave that found no work for its idle lanes
-    // delivers what it holds at once, however little: the SIMD has nothing better to do then)
-    if (extend && fin_n && filled < n_idle) flush_finished();
     if (inflight + filled == 0u) {
       flush_finished();
       if (!kStream || no_more) break;
@@ -2724,7 +2459,7 @@ __global__ __launch_bounds__(256) LENTIL_SOLVE_ATTR void solve_po_kernel(DrawArg
       // L2 channel that holds the queue busy enough to hold up every DMA group of the scan that touches it
       // (measured: scan 0.95 -> 2.6 ms beside 1024 idle waves polling every ~2 us).  4 us, doubling to 30 us.
       for (uint32_t i = 0; i < idle_naps; ++i) __builtin_amdgcn_s_sleep(127);
-      if (idle_naps < (on_ext ? 2u : 8u)) idle_naps <<= 1;       // (the extension's queue: a few hundred tasks, latency is all)
+      if (idle_naps < 8u) idle_naps <<= 1;
       continue;
     }
     idle_naps = 1u;
@@ -2748,7 +2483,6 @@ __global__ __launch_bounds__(256) LENTIL_SOLVE_ATTR void solve_po_kernel(DrawArg
           s_fin[wv][4][q] = s.out[0]; s_fin[wv][5][q] = s.out[1];
           s_fin_err[wv][q] = ((uint32_t)s.error & 0xFFu) | ((kChroma ? cur_chan_lane : 0u) << 8);
           s_fin_res[wv][q] = res_idx;
-          s_fin_item[wv][q] = my_item;
           busy = false;
         }
         fin_n += nfin;
@@ -2774,15 +2508,8 @@ __global__ __launch_bounds__(256) LENTIL_SOLVE_ATTR void solve_po_kernel(DrawArg
     if (parking && (!kStream || !a.slow_after_producers || producers_gone || no_more) &&
         ((a.slow_live && !a.slow_dry_only) || (no_more && __builtin_popcountll(__ballot(busy)) <= a.slow_max_lanes))) {
       const bool park = busy && s.k >= a.slow_at;
-      unsigned long long pmask = __ballot(park);
-      // Live queue: outliers only.  Where many lanes of a wave are past slow_at at once it is not a straggler but the item:
-      // near the frame's edge, where the lens vignettes, a third of an item's solves run 20-40 iterations before they
-      // raise an error bit (2 700 of a headline frame's solves -- in ten of its 1 100 items; 83 % of them fail).  Parked,
-      // they swamp the 256 straggler waves and leave half of such an item's attempts unknown to the first accept; in
-      // their lanes they cost the wave a few iterations more.  The crowd thins out by itself, what stays is parked.
-      if (a.slow_live && a.slow_crowd_stays && __builtin_popcountll(pmask) > a.slow_max_lanes) pmask = 0ull;
+      const unsigned long long pmask = __ballot(park);
       if (pmask) {
-        bool parked_closed = false;
         const uint32_t sq = slow_queue(a);
         uint32_t base = 0;
         if (lane == (uint32_t)__builtin_ctzll(pmask)) base = atomicAdd(&a.ctr->n_slow[sq], (uint32_t)__builtin_popcountll(pmask));
@@ -2811,11 +2538,6 @@ __global__ __launch_bounds__(256) LENTIL_SOLVE_ATTR void solve_po_kernel(DrawArg
             if (a.slow_indirect) st_agent32(res + res_idx, kCodePendingBase | slot);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             st_agent64(d + 15, slow_tag(a, kSlowRecord));
-            // (early accept: a parked solve is delivered -- its mark is in the pool; whether its result is in by the time the
-            // accept comes to the item is ItemHdr::parked / parked_done's business)
-            if (early) ready_deliver(a, my_item, 1u);
-            // (extension: a parked solve is delivered -- as a failure, for what the item's batch is judged by)
-            if (extend && live_deliver(a, my_item, 1u, 0u, 0u)) parked_closed = true;
           } else {
             d[0] = target[0]; d[1] = target[1]; d[2] = target[2]; d[3] = ap_x; d[4] = ap_y;
             d[5] = s.x; d[6] = s.y; d[7] = s.dx; d[8] = s.dy; d[9] = s.sqr_err; d[10] = s.sqr_ap_err;
@@ -2824,13 +2546,10 @@ __global__ __launch_bounds__(256) LENTIL_SOLVE_ATTR void solve_po_kernel(DrawArg
           }
           busy = false;
         }
-        if (__ballot(parked_closed)) close_queue = true;
       }
     }
-    if (close_queue) { live_close_queue(a, lane); close_queue = false; }
   }
   flush_finished();
-  if (close_queue) { live_close_queue(a, lane); close_queue = false; }
 #ifdef LENTIL_PROBE_BUILD
   if (kStream && a.dispatch_probe && a.round == 1 && lane == 0) atomicSub(&a.ctr->probe_res_xcc[0][xcc_id()], 1u);
 #endif
@@ -2847,8 +2566,7 @@ __global__ __launch_bounds__(256) LENTIL_SOLVE_ATTR void solve_po_kernel(DrawArg
       const uint32_t begun = ld_coherent32(&a.ctr->waves_started[par]);
       const uint32_t taken = ld_coherent32(&a.ctr->task_head[par]);
       const uint32_t published = kStream ? ld_coherent32(&a.ctr->n_tasks[par]) : n_tasks;
-      const bool complete = !kStream || (ld_coherent32(a.producers_done) >= a.producers_total &&
-                                         (!extend || ld_coherent32(&a.ctr->queue_final) != 0u));
+      const bool complete = !kStream || ld_coherent32(a.producers_done) >= a.producers_total;
       close = (done == begun && complete && taken >= published) ? 1u : 0u;
     }
     if (__builtin_amdgcn_readfirstlane(close)) {
@@ -2988,9 +2706,6 @@ __global__ __launch_bounds__(64) LENTIL_SLOW_ATTR void solve_slow_kernel(DrawArg
   const uint32_t probe_kind = a.round == 0 ? 2u : 1u;      // (the first round's stragglers / the second's)
   if (a.dispatch_probe && threadIdx.x == 0) atomicAdd(&a.ctr->probe_res_xcc[probe_kind][probe_xcc], 1u);
 #endif
-  if (a.slow_prio == 1) __builtin_amdgcn_s_setprio(1);
-  else if (a.slow_prio == 2) __builtin_amdgcn_s_setprio(2);
-  else if (a.slow_prio >= 3) __builtin_amdgcn_s_setprio(3);
   __shared__ CoopShared sh;
   __shared__ uint32_t s_q;
   extern __shared__ __align__(16) unsigned char s_coop[];      // coop_lds_bytes(n_terms)
@@ -3626,33 +3341,6 @@ LD_DEV AcceptResult accept_item_wide(const DrawArgs &a, AcceptShared &sh, Accept
       const uint32_t jc = covered / 256u + 1u;
       if (jc < jn) jn = jc;
     }
-    if (a.early_accept) {
-      // accept_kernel<4>: the solve kernel that wrote these results is still running on other CUs -- they were written through
-      // with agent-scope atomics and are read with returning atomics (ld_coherent*: an L2 of this XCD may hold the line from
-      // before), two results at a time where the batch lies in one piece (an item's first batch always does)
-      const uint32_t count = jn * 256u + retries;
-      if (pg.p_hi == pg.p_lo && n >= pg.m_lo) {
-        const uint32_t e0 = pg.res_off + (n - pg.m_lo), odd = e0 & 1u;
-        for (uint32_t j = threadIdx.x; 2u * j < count + odd; j += 256u) {
-          const uint32_t e = e0 - odd + 2u * j;                      // even: an 8-byte word of the pool
-          uint32_t lo, hi;
-          if ((uint64_t)e + 1u < a.pool_cap) { const uint64_t w = ld_coherent64(res + e); lo = (uint32_t)w; hi = (uint32_t)(w >> 32); }
-          else { lo = ld_coherent32(res + e); hi = kCodeBeyond; }
-          const uint32_t i1 = 2u * j + 1u - odd;                    // window index of the word's upper half (the lower: i1 - 1)
-          if (i1 >= 1u && i1 - 1u < count) ws.win[i1 - 1u] = n + (i1 - 1u) >= pg.m_hi ? kCodeBeyond : lo;
-          if (i1 < count) ws.win[i1] = n + i1 >= pg.m_hi ? kCodeBeyond : hi;
-        }
-      } else {
-        for (uint32_t i = threadIdx.x; i < count; i += 256u) {
-          const uint32_t m = n + i;
-          uint32_t c = kCodeFail;
-          if (m >= pg.m_hi) c = kCodeBeyond;
-          else if (m >= pg.m_lo) c = ld_coherent32(res + pg.res_off + (m - pg.m_lo));
-          else if (m >= pg.p_lo && m < pg.p_hi) c = ld_coherent32(res_prev + pg.p_off + (m - pg.p_lo));
-          ws.win[i] = c;
-        }
-      }
-    } else
     for (uint32_t i = threadIdx.x; i < jn * 256u + retries; i += 256u) ws.win[i] = result_at2(res, res_prev, pg, n + i);
     if (threadIdx.x < kSlabs) { ws.first_u[threadIdx.x] = kStep; ws.m_succ[threadIdx.x] = 0ull; ws.m_unk[threadIdx.x] = 0ull; ws.m_succ1[threadIdx.x] = 0ull; }
     block_sync_lds();
@@ -4033,13 +3721,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LENTIL_ACCE
   // walked twice (mode 1 splatted what was certain of nearly every item and mode 2 then replayed nearly every item: 134 us
   // behind the stragglers for a headline frame); what is left for the accept behind the stragglers is the items whose
   // stragglers were still at work when this kernel came to them.  It never waits for anything.
-  // kMode 4: mode 3 BESIDE the solve kernel (DrawArgs::early_accept): launched behind the publishers, it draws tickets on the queue
-  // of items whose first batch is complete -- pushed by the solve wave that delivered the item's last result -- and walks each
-  // as it comes; its last block leaves when the pass's last item is through, a walk or two behind the solve kernel's last wave
-  // instead of a whole accept (160-190 us for a 4K headline frame).  It waits for the solve kernel (resident since the pass
-  // began, holding everything it will ever need), never for the stragglers: an item with a parked solve still out goes to the
-  // accept behind them, as in mode 3.
-  constexpr int kWalk = (kMode == 3 || kMode == 4) ? 2 : kMode;
+  constexpr int kWalk = kMode == 3 ? 2 : kMode;
   __shared__ uint32_t s_item, s_ready;
   __shared__ AcceptShared sh;
   __shared__ AcceptWideShared ws;
@@ -4070,12 +3752,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LENTIL_ACCE
   constexpr uint32_t kGroup = 8;
   __shared__ uint32_t s_emit_off[kGroup], s_emit_hi[kGroup], s_emitted[kGroup];
   const bool chroma = a.n_channels == 3;
-  // (LENTIL_ACCEPT_WIDE=0 -> DrawArgs::accept_narrow: the 256-attempt steps of accept_item for everything)
-  // (... and for records wider than one wave: accept_item_wide's lane (draw, float) layout serves 64 / U draws per atomic
+  // (accept_item for records wider than one wave: accept_item_wide's lane (draw, float) layout serves 64 / U draws per atomic
   // instruction, which is none at U = 65 -- sixteen gaussian AOVs, LENTIL_MAX_AOVS; accept_item loops over draw x float)
   uint32_t add_floats = 1;
   for (uint32_t k = 0; k < a.F.n_aovs; ++k) if (!(a.F.closest_mask & (1u << k))) add_floats += 4;
-  const bool wide = !chroma && (uint32_t)a.retries <= kAcceptWinRetries && !a.accept_narrow && add_floats <= 64u;
+  const bool wide = !chroma && (uint32_t)a.retries <= kAcceptWinRetries && add_floats <= 64u;
   const bool dry_first = a.emit_live && !chroma && !wide;
   uint32_t per = 1;
   if (dry_first || wide) { per = (n_active + gridDim.x - 1u) / gridDim.x; per = per < 1u ? 1u : (per > kGroup ? kGroup : per); }
@@ -4163,48 +3844,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LENTIL_ACCE
   }
   while (true) {
     __syncthreads();
-    uint32_t ai0 = 0, ready_item = 0;
-    if constexpr (kMode == 4) {
-      // a ticket on the ready queue; its slot is filled when the item it will hold is complete
-      if (threadIdx.x == 0) {
-        uint32_t item = 0xFFFFFFFFu;
-        const uint32_t ticket = atomicAdd(&a.ctr->ready_head, 1u);
-        if (ticket < n_active && ticket < a.ready_cap) {
-          const uint32_t tag = (a.epoch << 8) | 1u;
-          const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-          uint32_t naps = 1u, polls = 0u;
-          while (true) {
-            const uint64_t w = ld_coherent64(a.ready_q + ticket);
-            if ((uint32_t)(w >> 32) == tag) { item = (uint32_t)w; break; }
-            if ((++polls & 15u) == 0u && (ld_coherent32(&a.ctr->stuck) != 0u || ld_coherent64(&a.ctr->fallback) != 0ull)) break;      // the pass is void
-            if (__builtin_amdgcn_s_memrealtime() - t0 > (a.stuck_ticks ? a.stuck_ticks : kStuckTicks)) {
-              if (atomicCAS(&a.ctr->stuck, 0u, 2u | (ticket << 2)) == 0u) {
-                unsigned int *si = a.ctr->stuck_info;
-                si[0] = 0xACCu; si[1] = par; si[2] = ld_coherent32(&a.ctr->n_ready); si[3] = n_active; si[4] = ld_coherent32(&a.ctr->ready_head);
-                si[5] = (uint32_t)(w >> 32); si[6] = blockIdx.x; si[7] = ld_coherent32(&a.ctr->task_head[par]);
-              }
-              break;
-            }
-            for (uint32_t i = 0; i < naps; ++i) __builtin_amdgcn_s_sleep(64);
-            if (naps < 8u) naps <<= 1;
-          }
-        }
-        s_item = item;
-      }
-      __syncthreads();
-      if (s_item == 0xFFFFFFFFu) break;
-      ready_item = s_item;
-    } else {
-      if (threadIdx.x == 0) s_item = atomicAdd(&a.ctr->active_head[par], per);
-      __syncthreads();
-      ai0 = s_item;
-      if (ai0 >= n_active) break;
-    }
-    const uint32_t cnt = kMode == 4 ? 1u : (n_active - ai0 < per ? n_active - ai0 : per);
+    if (threadIdx.x == 0) s_item = atomicAdd(&a.ctr->active_head[par], per);
+    __syncthreads();
+    const uint32_t ai0 = s_item;
+    if (ai0 >= n_active) break;
+    const uint32_t cnt = n_active - ai0 < per ? n_active - ai0 : per;
     if (wide) {
       for (uint32_t j = 0; j < cnt; ++j) {
-        const uint32_t item = kMode == 4 ? ready_item : a.active[par][ai0 + j];
-        const ItemProg pg = load_prog(a, item);
+        const uint32_t item = a.active[par][ai0 + j];
+        const ItemProg pg = a.prog[item];
 #ifdef LENTIL_TIMELINE
         const unsigned long long tm0_ = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -4212,7 +3860,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LENTIL_ACCE
 #ifdef LENTIL_TIMELINE
         if (threadIdx.x == 0 && h.samples) { dbg_add(26, __builtin_amdgcn_s_memrealtime() - tm0_); dbg_add(27, 1); }
 #endif
-        if constexpr (kMode == 3 || kMode == 4) {
+        if constexpr (kMode == 3) {
           if (threadIdx.x == 0) {
             const uint64_t w = ld_coherent64(reinterpret_cast<const uint64_t *>(a.hdr + item) + 4);
             const bool ready = (uint32_t)w == (uint32_t)(w >> 32);
@@ -4240,12 +3888,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LENTIL_ACCE
       ticket_done(cnt);
       continue;
     }
-    if constexpr (kMode == 3 || kMode == 4) {
+    if constexpr (kMode == 3) {
       // (the host launches these modes for frames the wide walk serves; anything else goes to the accept behind the stragglers whole)
       if (threadIdx.x == 0)
         for (uint32_t j = 0; j < cnt; ++j) {
-          const uint32_t item = kMode == 4 ? ready_item : a.active[par][ai0 + j];
-          const ItemProg pg = load_prog(a, item);
+          const uint32_t item = a.active[par][ai0 + j];
+          const ItemProg pg = a.prog[item];
           ItemProg np_ = pg;
           np_.uacc = 0; np_.n_end1 = 0;
           np_.p_lo = pg.m_lo; np_.p_hi = pg.m_hi; np_.p_off = pg.res_off;
@@ -4259,7 +3907,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LENTIL_ACCE
     if (dry_first) {
       for (uint32_t j = 0; j < cnt; ++j) {
         const uint32_t item = a.active[par][ai0 + j];
-        const ItemProg pg = load_prog(a, item);
+        const ItemProg pg = a.prog[item];
         const AcceptResult rd = accept_item<kWalk>(a, sh, item, pg, res, res_prev, rmin, rmax_p1, true);
         if (threadIdx.x == 0) {
           uint32_t off = 0;
@@ -4271,7 +3919,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LENTIL_ACCE
     }
     for (uint32_t j = 0; j < cnt; ++j) {
       const uint32_t item = a.active[par][ai0 + j];
-      const ItemProg pg = load_prog(a, item);
+      const ItemProg pg = a.prog[item];
       const AcceptResult r = chroma ? accept_item_chroma(a, sh, item, pg, res, rmin, rmax_p1)
                                     : accept_item<kWalk>(a, sh, item, pg, res, res_prev, rmin, rmax_p1);
       if (threadIdx.x == 0)
