@@ -683,6 +683,22 @@ int lentil_hip_test_xor128_jump(const uint32_t in[4], uint64_t k, uint32_t out[4
  * intervals on which the circle of confusion is certainly below 0.4, out[4..5] / out[6..7] those outside of which it is
  * certainly not (an interval with lower > upper end is empty).  In between the kernel evaluates the function. */
 int lentil_hip_debug_scan_bands(const lentil_params *params, float out[8]);
+/* Test hook.  The scan kernels a pass may start with; which one runs follows from the stream's shape (visits per pixel, extra
+ * AOV columns and their filters, whether the last pixel is whole, pixels per row) and from the LDS the resident solve blocks
+ * of a streamed pass leave. */
+enum {
+  LENTIL_SCAN_DMA2 = 1,          /* beauty only, whole pixels, rows of >= 2 pixels: 64-pixel tiles pipelined through LDS */
+  LENTIL_SCAN_DMA = 2,           /* ... its unpipelined form: one visit per pixel, one pixel per row, or no LDS for the other */
+  LENTIL_SCAN_DMA_MULTI = 3,     /* extra AOVs, all gaussian, whole pixels of <= 64 visits: groups of <= 64 / M pixels */
+  LENTIL_SCAN_UNIFORM = 4,       /* register-staged, one column at a time: what the three above do not take */
+  LENTIL_SCAN_UNIFORM_MULTI = 5, /* register-staged, all columns: extras with a closest-filtered AOV or a truncated last pixel */
+  LENTIL_SCAN_RUNS = 6,          /* visits_per_pixel == 0: runs of a pixel's visits summed in their order */
+  LENTIL_SCAN_RAGGED = 7         /* visits_per_pixel == 0, LENTIL_SCAN_RUNS=0: an atomic per visit and float */
+};
+/* the scan launch of the last pass (of its last chunk, where the pass ran in chunks): out[0] kernel (LENTIL_SCAN_*), out[1]
+ * pixels per tile/group (0 for the two ragged kernels), out[2] dynamic LDS bytes, out[3] blocks launched.  All zero before
+ * the first pass.  No effect on the pass. */
+int lentil_hip_debug_last_scan(lentil_hip_ctx *ctx, uint32_t out[4]);
 
 #ifdef __cplusplus
 }

@@ -26,7 +26,7 @@ EXPORTS = [
     "lentil_hip_batch_model_stats", "lentil_hip_process_stats", "lentil_hip_process_stall_notes", "lentil_hip_set_async", "lentil_hip_pass_totals", "lentil_hip_set_occlusion_probe", "lentil_hip_probe_stats", "lentil_hip_debug_batch_estimate", "lentil_hip_box_probe",
     "lentil_hip_lens_jit_status", "lentil_hip_lens_jit_wait", "lentil_hip_debug_lens_jit_source", "lentil_hip_debug_lens_jit_compile",
     "lentil_hip_download_draw_log", "lentil_hip_test_lt_sample_aperture",
-    "lentil_hip_test_trace_bw_po", "lentil_hip_test_aperture_sample", "lentil_hip_debug_scan_bands",
+    "lentil_hip_test_trace_bw_po", "lentil_hip_test_aperture_sample", "lentil_hip_debug_scan_bands", "lentil_hip_debug_last_scan",
     "lentil_hip_lens_is_compiled", "lentil_hip_set_lens_mode",
     "lentil_hip_focus_search", "lentil_hip_test_y0_intersection",
     "lentil_hip_set_xor128_state", "lentil_hip_get_xor128_state", "lentil_hip_tl_chroma_stats", "lentil_hip_test_xor128_jump",
@@ -37,6 +37,11 @@ EXPORTS = [
     "lentil_hip_alloc_crypto", "lentil_hip_upload_crypto", "lentil_hip_bind_crypto", "lentil_hip_download_crypto",
     "lentil_hip_download_crypto_table", "lentil_hip_visits_begin_crypto", "lentil_hip_visits_append_crypto",
 ]
+
+# lentil_hip_debug_last_scan()[0]: the scan kernels (include/lentil_hip.h, LENTIL_SCAN_*)
+SCAN_DMA2, SCAN_DMA, SCAN_DMA_MULTI, SCAN_UNIFORM, SCAN_UNIFORM_MULTI, SCAN_RUNS, SCAN_RAGGED = range(1, 8)
+SCAN_NAMES = {SCAN_DMA2: "dma2", SCAN_DMA: "dma", SCAN_DMA_MULTI: "dma_multi", SCAN_UNIFORM: "uniform",
+              SCAN_UNIFORM_MULTI: "uniform_multi", SCAN_RUNS: "runs", SCAN_RAGGED: "ragged"}
 
 _lib = None
 
@@ -120,6 +125,7 @@ def load_library():
         "lentil_hip_get_counters": (i, [vp, C.POINTER(_abi.Counters)]),
         "lentil_hip_last_timing": (i, [vp, C.POINTER(C.c_float)]),
         "lentil_hip_last_launches": (i, [vp, C.POINTER(C.c_uint32)]),
+        "lentil_hip_debug_last_scan": (i, [vp, C.POINTER(C.c_uint32)]),
         "lentil_hip_batch_model_stats": (i, [vp, C.POINTER(C.c_uint64)]),
         "lentil_hip_process_stats": (i, [C.POINTER(C.c_uint64)]),
         "lentil_hip_process_stall_notes": (i, [C.c_char_p, C.c_uint64]),
@@ -565,6 +571,12 @@ class Context:
         n = (C.c_uint32 * 2)()
         self._chk(self.lib.lentil_hip_last_launches(self.h, n))
         return int(n[0]), int(n[1])
+
+    def last_scan(self):
+        """(kernel -- SCAN_DMA2 ... SCAN_RAGGED --, pixels per tile/group, dynamic LDS bytes, blocks) of the last pass's scan launch"""
+        n = (C.c_uint32 * 4)()
+        self._chk(self.lib.lentil_hip_debug_last_scan(self.h, n))
+        return tuple(int(x) for x in n)
 
     def lens_jit_status(self):
         """(state, compile seconds): 0 nothing to compile, 1 compiling, 2 specialised kernel in use, -1 failed"""

@@ -173,6 +173,7 @@ struct lentil_hip_ctx {
   uint64_t longest_pass_visits = 0, longest_pass_sum = 0;      // ... and how large that pass was (visits, draws expected)
   int scan_cus_pct = 84;                     // (100 / 92 / 84 / 76: 2.10 / 2.12 / 2.02 / 2.04 ms, means of four runs of 60 steps on one box)
   int scan_cus_pct_multi = 100;              // ... for frames with extra AOV columns (scan_dma_multi_kernel): LENTIL_SCAN_CUS_PCT_MULTI
+  uint32_t last_scan[4] = {0, 0, 0, 0};      // the last scan launch: kernel (LENTIL_SCAN_*), pixels per tile/group, LDS bytes, blocks (lentil_hip_debug_last_scan)
   unsigned last_scan_skipped = 0;             // blocks of the last scan launch that left at once (scan_dma2_kernel, ScanArgs::skip_blocks)
   int crypto_tile_blocks = 16;               // blocks per CU of crypto_direct_tile_kernel (LENTIL_CRYPTO_TILE_BLOCKS)
   bool predict = true;
@@ -2192,6 +2193,7 @@ static int launch_scan(lentil_hip_ctx *ctx, const ScanPlan &pl, const lentil_hip
   const uint64_t max_blocks = (uint64_t)ctx->num_cu * 8;
   uint64_t blocks;
   unsigned multi_skipped = 0;
+  uint32_t scan_id;       // which kernel, for lentil_hip_debug_last_scan
   // (a streamed pass's single launch: timed by its own dispatch, lentil_hip_last_timing)
   const bool own_events = streamed_pass && (pl.dma || pl.dma_multi);
   ctx->scan_kernel_timed = own_events;
@@ -2216,9 +2218,11 @@ static int launch_scan(lentil_hip_ctx *ctx, const ScanPlan &pl, const lentil_hip
         sa.skip_blocks = (uint32_t)(blocks - ((uint64_t)ctx->num_cu * (uint64_t)ctx->scan_cus_pct + 99) / 100);
       if (own_events) hipExtLaunchKernelGGL(scan_dma2_kernel, dim3((unsigned)blocks), dim3(256), pl.lds, ctx->stream, ctx->ev_scan_k[0], ctx->ev_scan_k[1], 0, sa);
       else hipLaunchKernelGGL(scan_dma2_kernel, dim3((unsigned)blocks), dim3(256), pl.lds, ctx->stream, sa);
+      scan_id = LENTIL_SCAN_DMA2;
     } else {
       if (own_events) hipExtLaunchKernelGGL(scan_dma_kernel, dim3((unsigned)blocks), dim3(256), pl.lds, ctx->stream, ctx->ev_scan_k[0], ctx->ev_scan_k[1], 0, sa);
       else hipLaunchKernelGGL(scan_dma_kernel, dim3((unsigned)blocks), dim3(256), pl.lds, ctx->stream, sa);
+      scan_id = LENTIL_SCAN_DMA;
     }
   } else if (pl.dma_multi) {
     // persistent: a wave draws runs of 16 groups
@@ -2235,11 +2239,13 @@ static int launch_scan(lentil_hip_ctx *ctx, const ScanPlan &pl, const lentil_hip
     }
     if (own_events) hipExtLaunchKernelGGL(scan_dma_multi_kernel, dim3((unsigned)blocks), dim3(256), pl.lds, ctx->stream, ctx->ev_scan_k[0], ctx->ev_scan_k[1], 0, sa);
     else hipLaunchKernelGGL(scan_dma_multi_kernel, dim3((unsigned)blocks), dim3(256), pl.lds, ctx->stream, sa);
+    scan_id = LENTIL_SCAN_DMA_MULTI;
   } else if (pl.M) {
     blocks = (ch.tile_end - ch.tile_begin + 3) / 4;
     if (blocks > max_blocks) blocks = max_blocks;
     if (pl.multi) hipLaunchKernelGGL(scan_uniform_multi_kernel, dim3((unsigned)blocks), dim3(256), pl.lds, ctx->stream, sa);
     else hipLaunchKernelGGL(scan_uniform_kernel, dim3((unsigned)blocks), dim3(256), pl.lds, ctx->stream, sa);
+    scan_id = pl.multi ? LENTIL_SCAN_UNIFORM_MULTI : LENTIL_SCAN_UNIFORM;
   } else {
     blocks = (ch.v_end - ch.v_begin + 255) / 256;
     if (blocks > max_blocks) blocks = max_blocks;
@@ -2247,9 +2253,14 @@ static int launch_scan(lentil_hip_ctx *ctx, const ScanPlan &pl, const lentil_hip
     const bool runs = !(getenv("LENTIL_SCAN_RUNS") && getenv("LENTIL_SCAN_RUNS")[0] == '0');       // (read per launch: the tests switch it)
     if (runs) hipLaunchKernelGGL(scan_runs_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, sa);
     else hipLaunchKernelGGL(scan_ragged_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, sa);
+    scan_id = runs ? LENTIL_SCAN_RUNS : LENTIL_SCAN_RAGGED;
   }
   HIP_TRY(ctx, hipGetLastError());
   if (blocks_out) *blocks_out = (unsigned)blocks;
+  ctx->last_scan[0] = scan_id;
+  ctx->last_scan[1] = pl.M ? sa.ppt : 0u;
+  ctx->last_scan[2] = pl.M ? (uint32_t)pl.lds : 0u;
+  ctx->last_scan[3] = (uint32_t)blocks;
   ctx->last_scan_skipped = (pl.dma && pl.dma2) ? sa.skip_blocks : (pl.dma_multi ? multi_skipped : 0u);
   return LENTIL_OK;
 }
@@ -2553,6 +2564,11 @@ static int redistribute_streamed(lentil_hip_ctx *ctx, bool *streamed, bool *defe
     if (ctx->est_sum_total >= (ctx->stream_below > by_visits ? ctx->stream_below : by_visits)) return LENTIL_OK;
   }
   if (ctx->V.n_extra && !dma_multi_applies(ctx)) return LENTIL_OK;
+  // ... nor where a scan block could not share a CU's LDS with even one resident solve block (scan_dma_multi_kernel from twelve
+  // extra AOVs on, from nine beside the table interpreter): whichever the dispatcher places first keeps the other out, and where
+  // that is the solve blocks they wait for a scan that cannot start until a publisher gives up -- 250 ms, then the redo
+  // (tests/test_gpu_scan_shapes.py: second passes with 14 and 15 extra AOVs)
+  if (ctx->V.n_extra && dma_multi_lds(ctx) + 512u + solve_block_lds(ctx) > 160u * 1024u) return LENTIL_OK;
   lentil_hip_ctx::Chunk &ch = ctx->chunks[0];
   // One streamed pass per device at a time: the resident kernels of two of them could keep each other's scan off the chip.
   // A context that finds another one's streamed pass in flight does not wait for it: its pass runs in the chunked form,
@@ -4324,6 +4340,14 @@ LENTIL_API int lentil_hip_last_launches(lentil_hip_ctx *ctx, uint32_t n[2]) {
   if (!n) return fail(ctx, LENTIL_ERR_INVALID, "n is null");
   n[0] = ctx->last_scan_launches;
   n[1] = (uint32_t)ctx->last_rounds;
+  return LENTIL_OK;
+}
+
+// test hook: which scan kernel the last pass launched, and how (launch_scan)
+LENTIL_API int lentil_hip_debug_last_scan(lentil_hip_ctx *ctx, uint32_t out[4]) {
+  CHECK_CTX(ctx);
+  if (!out) return fail(ctx, LENTIL_ERR_INVALID, "out is null");
+  for (int i = 0; i < 4; ++i) out[i] = ctx->last_scan[i];
   return LENTIL_OK;
 }
 
