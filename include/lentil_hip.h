@@ -620,8 +620,15 @@ int lentil_hip_process_stall_notes(char *buf, uint64_t capacity);
  *   AiMakeRay(AI_RAY_SHADOW, origin, normalize(target - origin), |target - origin|).
  *   camera_to_world: 16 floats, row-vector convention like lentil_params::world_to_camera (AiCameraToWorldMatrix); NULL: the
  *   inverse of params.world_to_camera (of every motion key, where lentil_hip_set_camera_motion has set keys), computed in fp64.
- *   fn == NULL switches probing off.  Not with abb_chromatic != 0 (LENTIL_ERR_UNSUPPORTED from the pass): the reference draws a
- *   thin-lens attempt's colour channel AFTER its probe, from one generator in visit order.
+ *   fn == NULL switches probing off.
+ *   Thin lens with abb_chromatic > 0: the reference draws an attempt's colour channel AFTER its probe, from one generator in visit
+ *   order, and an occluded attempt draws none.  There the probes come before the walk that draws the channels, in a loop: the
+ *   attempts every item can possibly reach (no item goes past its samples-th attempt that lands in the frame in all three
+ *   channels) that have not been asked about go to the callback in ONE list, the occluded ones are lost, which lets items reach
+ *   further -- until a turn has nothing to ask.  One callback per turn of that loop and pass (tests/test_gpu_probe_tl_chroma.py);
+ *   with a communicator every rank asks about its own items.  A pass the library runs a second time (closest-filtered AOVs with
+ *   candidates at depth 0 / NaN and no draw log) re-applies the first run's answers and does not call back.
+ *   Polynomial optics with abb_chromatic != 0 and a probe: LENTIL_ERR_UNSUPPORTED from the pass.
  * Cost: INTEGRATION.md section 3c (the list travels over PCIe: 24 B out and 1 B back per try that got through the lens). */
 typedef struct lentil_probe_segment {
   float origin[3];   /* the sample, world space */

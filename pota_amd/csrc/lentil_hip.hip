@@ -266,6 +266,12 @@ struct lentil_hip_ctx {
   uint64_t tlc_entry_cap = 0, tlc_val_cap = 0;
   std::vector<uint32_t> tlc_gids;
   bool tlc_have_entries = false, tlc_rewalk = false;
+  // ... under an occlusion probe (tl_chroma_probe): how far every item can go and how far it has been asked about; the slots
+  // of the attempts the pass's first run found occluded, which a run of the same pass again (closest_rerun_with_log:
+  // pass_rerun) fails once more without asking the renderer
+  uint32_t *d_tlc_bound = nullptr, *d_tlc_probed = nullptr, *d_tlc_occ = nullptr;
+  uint64_t tlc_bound_cap = 0, tlc_probed_cap = 0, tlc_occ_cap = 0, tlc_occ_n = 0, tlc_occ_slots = 0;
+  bool tlc_occ_valid = false, pass_rerun = false;
   uint64_t tlc_items = 0, tlc_dependent = 0, tlc_gathered = 0;     // lentil_hip_tl_chroma_stats
   double lens_housing_radius = 0.0;  // lens_aperture_housing_radius of the current table (focus search)
   float4 *d_dummy = nullptr;          // ScanArgs::dummy
@@ -778,6 +784,7 @@ LENTIL_API int lentil_hip_destroy(lentil_hip_ctx *ctx) {
   (void)hipFree(ctx->d_bm_land); (void)hipFree(ctx->d_bm_box); (void)hipFree(ctx->d_bm_npass);
   (void)hipFree(ctx->d_xor); (void)hipFree(ctx->d_tlc_res); (void)hipFree(ctx->d_tlc_off); (void)hipFree(ctx->d_tlc_tasks);
   (void)hipFree(ctx->d_xor_jump); (void)hipFree(ctx->d_tlc_entry); (void)hipFree(ctx->d_tlc_val);
+  (void)hipFree(ctx->d_tlc_bound); (void)hipFree(ctx->d_tlc_probed); (void)hipFree(ctx->d_tlc_occ);
   (void)hipFree(ctx->d_log);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);       // (ctx->ev[]: one of the slots' sets, destroyed with them above)
   delete ctx;
@@ -1240,11 +1247,8 @@ LENTIL_API int lentil_hip_probe_stats(lentil_hip_ctx *ctx, uint64_t stats[3]) {
   return LENTIL_OK;
 }
 
-// One round's probes, between its solves (and stragglers) and its accept, on the round's stream: list, callback, apply.  The
-// host waits twice -- for the list and, inside the callback, for the renderer.
-static int probe_round(lentil_hip_ctx *ctx, const DrawArgs &da, hipStream_t st) {
-  if (!ctx->probe_fn) return LENTIL_OK;
-  ProbeArgs pr{};
+// What every list of probes needs: AiCameraToWorldMatrix (and its motion keys, on the device) and the list's counter.
+static int probe_prepare(lentil_hip_ctx *ctx, ProbeArgs &pr, hipStream_t st) {
   if (ctx->probe_c2w_given) memcpy(pr.c2w, ctx->probe_c2w, sizeof pr.c2w);
   else invert4x4(&ctx->P.world_to_camera[0][0], &pr.c2w[0][0]);
   if (ctx->n_cam_keys >= 2 && ctx->h_cam_keys.size() == (size_t)16 * ctx->n_cam_keys) {
@@ -1256,21 +1260,32 @@ static int probe_round(lentil_hip_ctx *ctx, const DrawArgs &da, hipStream_t st) 
     pr.c2w_keys = ctx->d_c2w_keys;
   }
   if (!ctx->d_probe_count) HIP_TRY(ctx, hipMalloc(&ctx->d_probe_count, sizeof(unsigned int)));
-  const dim3 grid((unsigned)ctx->num_cu * 4u), block(256);
+  return LENTIL_OK;
+}
+
+static int probe_alloc(lentil_hip_ctx *ctx, uint64_t cap) {
+  HIP_TRY(ctx, hipMalloc(&ctx->d_probe_seg, cap * sizeof(lentil_probe_segment)));
+  HIP_TRY(ctx, hipMalloc(&ctx->d_probe_idx, cap * sizeof(uint32_t)));
+  HIP_TRY(ctx, hipMalloc(&ctx->d_probe_occ, cap));
+  HIP_TRY(ctx, hipHostMalloc((void **)&ctx->h_probe_seg, cap * sizeof(lentil_probe_segment), hipHostMallocDefault));
+  HIP_TRY(ctx, hipHostMalloc((void **)&ctx->h_probe_occ, cap, hipHostMallocDefault));
+  ctx->probe_cap = cap;
+  return LENTIL_OK;
+}
+
+// One list of probes and the renderer's answers: `launch_list(pr)` enqueues the kernel that fills pr.seg / pr.idx and counts
+// in pr.count (a list that outgrew the buffers is made once more, into larger ones); the callback, on the calling thread;
+// the answers in pr.occluded on the device when some segment is occluded.  *n: segments asked; *occ: of them occluded --
+// the caller applies those.  The host waits twice: for the list and, inside the callback, for the renderer.
+template <class LaunchList>
+static int probe_ask(lentil_hip_ctx *ctx, ProbeArgs &pr, hipStream_t st, LaunchList launch_list, unsigned int *n_out, uint64_t *occ_out) {
+  *n_out = 0; *occ_out = 0;
   for (int attempt = 0; attempt < 2; ++attempt) {
-    if (ctx->probe_cap == 0) {
-      const uint64_t cap = 1ull << 20;
-      HIP_TRY(ctx, hipMalloc(&ctx->d_probe_seg, cap * sizeof(lentil_probe_segment)));
-      HIP_TRY(ctx, hipMalloc(&ctx->d_probe_idx, cap * sizeof(uint32_t)));
-      HIP_TRY(ctx, hipMalloc(&ctx->d_probe_occ, cap));
-      HIP_TRY(ctx, hipHostMalloc((void **)&ctx->h_probe_seg, cap * sizeof(lentil_probe_segment), hipHostMallocDefault));
-      HIP_TRY(ctx, hipHostMalloc((void **)&ctx->h_probe_occ, cap, hipHostMallocDefault));
-      ctx->probe_cap = cap;
-    }
+    if (ctx->probe_cap == 0) { const int rc = probe_alloc(ctx, 1ull << 20); if (rc) return rc; }
     pr.seg = ctx->d_probe_seg; pr.idx = ctx->d_probe_idx; pr.cap = (uint32_t)(ctx->probe_cap < 0xFFFFFFF0ull ? ctx->probe_cap : 0xFFFFFFF0ull);
     pr.count = ctx->d_probe_count; pr.occluded = ctx->d_probe_occ;
     HIP_TRY(ctx, hipMemsetAsync(ctx->d_probe_count, 0, sizeof(unsigned int), st));
-    hipLaunchKernelGGL(probe_list_kernel, grid, block, 0, st, da, pr);
+    launch_list(pr);
     HIP_TRY(ctx, hipGetLastError());
     unsigned int n = 0;
     HIP_TRY(ctx, hipMemcpyAsync(&n, ctx->d_probe_count, sizeof n, hipMemcpyDeviceToHost, st));
@@ -1281,13 +1296,9 @@ static int probe_round(lentil_hip_ctx *ctx, const DrawArgs &da, hipStream_t st) 
       (void)hipFree(ctx->d_probe_seg); (void)hipFree(ctx->d_probe_idx); (void)hipFree(ctx->d_probe_occ);
       (void)hipHostFree(ctx->h_probe_seg); (void)hipHostFree(ctx->h_probe_occ);
       ctx->d_probe_seg = nullptr; ctx->d_probe_idx = nullptr; ctx->d_probe_occ = nullptr; ctx->h_probe_seg = nullptr; ctx->h_probe_occ = nullptr;
-      const uint64_t cap = (uint64_t)n + (uint64_t)n / 4 + 4096;
-      HIP_TRY(ctx, hipMalloc(&ctx->d_probe_seg, cap * sizeof(lentil_probe_segment)));
-      HIP_TRY(ctx, hipMalloc(&ctx->d_probe_idx, cap * sizeof(uint32_t)));
-      HIP_TRY(ctx, hipMalloc(&ctx->d_probe_occ, cap));
-      HIP_TRY(ctx, hipHostMalloc((void **)&ctx->h_probe_seg, cap * sizeof(lentil_probe_segment), hipHostMallocDefault));
-      HIP_TRY(ctx, hipHostMalloc((void **)&ctx->h_probe_occ, cap, hipHostMallocDefault));
-      ctx->probe_cap = cap;
+      ctx->probe_cap = 0;
+      const int rc = probe_alloc(ctx, (uint64_t)n + (uint64_t)n / 4 + 4096);
+      if (rc) return rc;
       continue;
     }
     if (n == 0) return LENTIL_OK;
@@ -1298,12 +1309,26 @@ static int probe_round(lentil_hip_ctx *ctx, const DrawArgs &da, hipStream_t st) 
     uint64_t occ = 0;
     for (unsigned int i = 0; i < n; ++i) occ += ctx->h_probe_occ[i] ? 1u : 0u;
     ctx->n_probes += n; ctx->n_probes_occluded += occ; ++ctx->n_probe_calls;
-    if (occ) {
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->d_probe_occ, ctx->h_probe_occ, n, hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL(probe_apply_kernel, grid, block, 0, st, da, pr, (uint32_t)n);
-      HIP_TRY(ctx, hipGetLastError());
-    }
+    if (occ) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_probe_occ, ctx->h_probe_occ, n, hipMemcpyHostToDevice, st));
+    *n_out = n; *occ_out = occ;
     return LENTIL_OK;
+  }
+  return LENTIL_OK;
+}
+
+// One round's probes, between its solves (and stragglers) and its accept, on the round's stream: list, callback, apply.
+static int probe_round(lentil_hip_ctx *ctx, const DrawArgs &da, hipStream_t st) {
+  if (!ctx->probe_fn) return LENTIL_OK;
+  ProbeArgs pr{};
+  int rc;
+  if ((rc = probe_prepare(ctx, pr, st))) return rc;
+  const dim3 grid((unsigned)ctx->num_cu * 4u), block(256);
+  unsigned int n = 0;
+  uint64_t occ = 0;
+  if ((rc = probe_ask(ctx, pr, st, [&](const ProbeArgs &q) { hipLaunchKernelGGL(probe_list_kernel, grid, block, 0, st, da, q); }, &n, &occ))) return rc;
+  if (occ) {
+    hipLaunchKernelGGL(probe_apply_kernel, grid, block, 0, st, da, pr, (uint32_t)n);
+    HIP_TRY(ctx, hipGetLastError());
   }
   return LENTIL_OK;
 }
@@ -3137,6 +3162,82 @@ static unsigned tl_chroma_item_blocks(const lentil_hip_ctx *ctx, uint32_t n_item
 
 static int tl_chroma_across_ranks(lentil_hip_ctx *ctx, TlChromaArgs &ta, const std::vector<uint32_t> &gids);      // lentil_comm.h
 
+// The occlusion probes of a thin-lens abb_chromatic > 0 pass (kernels: tl_chroma_probe_*), between tl_chroma_solve_kernel and
+// the walk, on this rank's own items: no collective.  Every turn of the loop bounds how far each item can go, lists the
+// surviving attempts below the bound that have not been asked about, asks the renderer once, and fails the occluded ones;
+// the bounds only grow, up to 5 * samples, and the loop ends with the turn that lists nothing.  A pass run again
+// (`reapply`) fails the attempts its first run found occluded and asks nothing.
+static int tl_chroma_probe(lentil_hip_ctx *ctx, const TlChromaArgs &ta, uint64_t slots, bool reapply) {
+  hipStream_t st = ctx->stream;
+  const dim3 items_grid(tl_chroma_item_blocks(ctx, ta.n_items)), grid((unsigned)ctx->num_cu * 4u), block(256);
+  int rc;
+  if (reapply) {
+    if (!ctx->tlc_occ_valid || ctx->tlc_occ_slots != slots)
+      return fail(ctx, LENTIL_ERR_INVALID, "thin-lens abb_chromatic > 0: the pass run again found other attempts than its first run probed");
+    if (ctx->tlc_occ_n) {
+      hipLaunchKernelGGL(tl_chroma_probe_apply_kernel, grid, block, 0, st, ta.res, (const uint32_t *)ctx->d_tlc_occ, (const uint8_t *)nullptr,
+                         (uint32_t)ctx->tlc_occ_n, (uint32_t *)nullptr, (unsigned int *)nullptr);
+      HIP_TRY(ctx, hipGetLastError());
+    }
+    return LENTIL_OK;
+  }
+  ctx->tlc_occ_valid = false;
+  ctx->tlc_occ_n = 0;
+  ctx->tlc_occ_slots = slots;
+  if (!ta.n_items) { ctx->tlc_occ_valid = true; return LENTIL_OK; }
+  if (slots > 0xFFFFFFF0ull)
+    return fail(ctx, LENTIL_ERR_NOMEM, "thin-lens abb_chromatic > 0 under an occlusion probe: more than 2^32 attempt slots in one pass");
+  auto grow_to = [&](uint32_t **p, uint64_t &cap, uint64_t need) -> int {
+    if (cap >= need) return LENTIL_OK;
+    (void)hipFree(*p);
+    *p = nullptr;
+    cap = 0;
+    HIP_TRY(ctx, hipMalloc((void **)p, need * sizeof(uint32_t)));
+    cap = need;
+    return LENTIL_OK;
+  };
+  if ((rc = grow_to(&ctx->d_tlc_bound, ctx->tlc_bound_cap, ta.n_items))) return rc;
+  if ((rc = grow_to(&ctx->d_tlc_probed, ctx->tlc_probed_cap, ta.n_items))) return rc;
+  ProbeArgs pr{};
+  if ((rc = probe_prepare(ctx, pr, st))) return rc;
+  TlChromaProbe b{};
+  b.bound = ctx->d_tlc_bound; b.probed = ctx->d_tlc_probed;
+  HIP_TRY(ctx, hipMemsetAsync(ctx->d_tlc_probed, 0, (size_t)ta.n_items * sizeof(uint32_t), st));
+  for (;;) {
+    hipLaunchKernelGGL(tl_chroma_probe_bound_kernel, items_grid, block, 0, st, ta, b);
+    HIP_TRY(ctx, hipGetLastError());
+    unsigned int n = 0;
+    uint64_t occ = 0;
+    if ((rc = probe_ask(ctx, pr, st, [&](const ProbeArgs &q) { hipLaunchKernelGGL(tl_chroma_probe_list_kernel, items_grid, block, 0, st, ta, b, q); },
+                        &n, &occ)))
+      return rc;
+    if (!n) break;
+    if (occ) {
+      if (ctx->tlc_occ_n + occ > ctx->tlc_occ_cap) {      // (the slots kept so far move into the larger buffer)
+        const uint64_t cap = ctx->tlc_occ_n + occ + (ctx->tlc_occ_n + occ) / 2 + 4096;
+        uint32_t *grown = nullptr;
+        HIP_TRY(ctx, hipMalloc(&grown, cap * sizeof(uint32_t)));
+        hipError_t e = hipSuccess;
+        if (ctx->tlc_occ_n) e = hipMemcpyAsync(grown, ctx->d_tlc_occ, ctx->tlc_occ_n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) { (void)hipFree(grown); HIP_TRY(ctx, e); }
+        (void)hipFree(ctx->d_tlc_occ);
+        ctx->d_tlc_occ = grown;
+        ctx->tlc_occ_cap = cap;
+      }
+      HIP_TRY(ctx, hipMemsetAsync(ctx->d_probe_count, 0, sizeof(unsigned int), st));
+      hipLaunchKernelGGL(tl_chroma_probe_apply_kernel, grid, block, 0, st, ta.res, (const uint32_t *)pr.idx, pr.occluded, (uint32_t)n,
+                         ctx->d_tlc_occ + ctx->tlc_occ_n, ctx->d_probe_count);
+      HIP_TRY(ctx, hipGetLastError());
+      ctx->tlc_occ_n += occ;
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tlc_probed, ctx->d_tlc_bound, (size_t)ta.n_items * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    if (!occ) break;       // (nothing failed: the bounds stand)
+  }
+  ctx->tlc_occ_valid = true;
+  return LENTIL_OK;
+}
+
 // Thin lens with abb_chromatic > 0 (kernels: tl_chroma_*): scan, the work list put into visit order on the host, every
 // possible attempt's channel-independent part solved in parallel, then the walk in visit order.  Without a communicator one
 // block walks the items one after the other.  With one (lentil_tl_chroma_mgpu.h) the items are ordered by frame-wide visit
@@ -3237,6 +3338,7 @@ static int redistribute_tl_chroma(lentil_hip_ctx *ctx) {
     hipLaunchKernelGGL(tl_chroma_solve_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, ta);
     HIP_TRY(ctx, hipGetLastError());
   }
+  if (ctx->probe_fn && (rc = tl_chroma_probe(ctx, ta, slots, ctx->pass_rerun))) return rc;      // (this rank's own items; a rank without any goes on to the collective)
   if (!ctx->comm) {
     hipLaunchKernelGGL(tl_chroma_walk_kernel, dim3(1), dim3(256), 0, ctx->stream, ta);
     HIP_TRY(ctx, hipGetLastError());
@@ -3338,8 +3440,10 @@ static int closest_rerun_with_log(lentil_hip_ctx *ctx, const uint32_t *xor_entry
   // (with a communicator the run is this rank's alone: thin lens, abb_chromatic > 0 walks its items again from the entry
   // states the first run kept, and starts no collective -- the other ranks are not running the pass)
   ctx->tlc_rewalk = ctx->comm != nullptr;
+  ctx->pass_rerun = true;         // (thin lens, abb_chromatic > 0 under an occlusion probe: the first run's answers, not the renderer's again)
   rc = redistribute_impl(ctx);
   ctx->tlc_rewalk = false;
+  ctx->pass_rerun = false;
   if (rc) return rc;
   // (counters and timing describe the second run; that there were two is reported like any pass that was redone)
   ++ctx->last_fallback;
@@ -3643,9 +3747,9 @@ static int redistribute_pass(lentil_hip_ctx *ctx) {
   for (uint32_t k = 1; k < ctx->F.n_aovs; ++k)
     if (ctx->V.n && !ctx->V.extra[k - 1] && !(ctx->F.debug_mask & (1u << k)))
       return fail(ctx, LENTIL_ERR_INVALID, "an extra AOV column is null");
-  if (ctx->probe_fn && P.abb_chromatic != 0.0f)
-    return fail(ctx, LENTIL_ERR_UNSUPPORTED, "occlusion probes with abb_chromatic != 0: the reference draws an attempt's colour channel behind its probe, from "
-                                             "one generator in visit order (src/lentil_filter.cpp:356-406); not built");
+  if (ctx->probe_fn && P.cameraType == LENTIL_POLYNOMIAL_OPTICS && P.abb_chromatic != 0.0f)
+    return fail(ctx, LENTIL_ERR_UNSUPPORTED, "occlusion probes with polynomial optics and abb_chromatic != 0 (three wavelengths per attempt, "
+                                             "src/lentil_filter.cpp:248-299): not built; the thin lens is probed with any abb_chromatic");
   if (ctx->F.debug_mask && ctx->closest_deferred && !ctx->comm)
     return fail(ctx, LENTIL_ERR_UNSUPPORTED, "the lentil_debug AOV is exchanged between GPUs by lentil_hip_allreduce / _exchange_bands only");
   HIP_TRY(ctx, hipSetDevice(ctx->device));

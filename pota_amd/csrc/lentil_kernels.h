@@ -3974,11 +3974,41 @@ LD_DEV void probe_target(const lentil_params &P, const float c2w[4][4], float lx
   out[2] = vx * c2w[0][2] + vy * c2w[1][2] + vz * c2w[2][2] + c2w[3][2];
 }
 
+// sample_is_from_skydome, src/lentil_filter.cpp:119-133 (an item at infinity exists only with enable_skydome)
+LD_DEV bool probe_from_skydome(float4 pos_z) {
+  const bool small = fabsf(pos_z.x) < kAiEpsilon && fabsf(pos_z.y) < kAiEpsilon && fabsf(pos_z.z) < kAiEpsilon;
+  return ((double)pos_z.w == (double)kAiInfinite) || small;
+}
+
+// AiCameraToWorldMatrix at the sample's time: the static matrix, or the motion keys blended like the world-to-camera keys
+LD_DEV void probe_cam_to_world(const CamMotion &cm, const ProbeArgs &pr, float time, float c2w[4][4]) {
+  if (cm.n >= 2u && pr.c2w_keys) {
+    float tt = (time - cm.t0) * cm.inv_dt;
+    tt = tt < 0.0f ? 0.0f : (tt > 1.0f ? 1.0f : tt);
+    const float sc = tt * (float)(cm.n - 1u);
+    uint32_t i0 = (uint32_t)sc;
+    if (i0 > cm.n - 2u) i0 = cm.n - 2u;
+    const float f = sc - (float)i0;
+    const float *ka = pr.c2w_keys + (size_t)i0 * 16u, *kb = ka + 16;
+    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) c2w[r][c] = ((kb[r * 4 + c] - ka[r * 4 + c]) * f) + ka[r * 4 + c];
+  } else {
+    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) c2w[r][c] = pr.c2w[r][c];
+  }
+}
+
+// One wave's wanted lanes take consecutive slots of the list: one atomic per wave.  Called by the whole wave.
+LD_DEV uint32_t probe_wave_slot(unsigned int *count, unsigned long long wmask, uint32_t lane) {
+  const int first = __builtin_ctzll(wmask);
+  uint32_t base = 0;
+  if ((int)lane == first) base = atomicAdd(count, (unsigned int)__builtin_popcountll(wmask));
+  base = __shfl(base, first);
+  return base + (uint32_t)__builtin_popcountll(wmask & ((1ull << lane) - 1ull));
+}
+
 __global__ __launch_bounds__(256) void probe_list_kernel(DrawArgs a, ProbeArgs pr) {
   const uint32_t par = (uint32_t)a.parity;
   const uint32_t n_tasks = a.ctr->n_tasks[par] < a.task_cap ? a.ctr->n_tasks[par] : a.task_cap;
   const uint32_t lane = threadIdx.x & 63u;
-  const unsigned long long lt_mask = (1ull << lane) - 1ull;
   const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6;
   const bool po = a.P.cameraType == LENTIL_POLYNOMIAL_OPTICS;
@@ -3993,24 +4023,10 @@ __global__ __launch_bounds__(256) void probe_list_kernel(DrawArgs a, ProbeArgs p
       const uint32_t v = a.work[t.item].x;
       const float4 pos_z = a.V.pos_z[v];
       const float4 raydir_time = a.V.raydir_time[v];
-      const bool small = fabsf(pos_z.x) < kAiEpsilon && fabsf(pos_z.y) < kAiEpsilon && fabsf(pos_z.z) < kAiEpsilon;
-      const bool from_skydome = ((double)pos_z.w == (double)kAiInfinite) || small;      // (an item at infinity exists only with enable_skydome)
-      if (from_skydome) want = false;
+      if (probe_from_skydome(pos_z)) want = false;
       if (want) {
         float c2w[4][4];
-        const CamMotion &cm = a.V.cam;
-        if (cm.n >= 2u && pr.c2w_keys) {
-          float tt = (raydir_time.w - cm.t0) * cm.inv_dt;
-          tt = tt < 0.0f ? 0.0f : (tt > 1.0f ? 1.0f : tt);
-          const float sc = tt * (float)(cm.n - 1u);
-          uint32_t i0 = (uint32_t)sc;
-          if (i0 > cm.n - 2u) i0 = cm.n - 2u;
-          const float f = sc - (float)i0;
-          const float *ka = pr.c2w_keys + (size_t)i0 * 16u, *kb = ka + 16;
-          for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) c2w[r][c] = ((kb[r * 4 + c] - ka[r * 4 + c]) * f) + ka[r * 4 + c];
-        } else {
-          for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) c2w[r][c] = pr.c2w[r][c];
-        }
+        probe_cam_to_world(a.V.cam, pr, raydir_time.w, c2w);
         org[0] = pos_z.x; org[1] = pos_z.y; org[2] = pos_z.z;
         const uint32_t m = t.m_base + lane;
         if (po) {
@@ -4027,10 +4043,7 @@ __global__ __launch_bounds__(256) void probe_list_kernel(DrawArgs a, ProbeArgs p
     }
     const unsigned long long wmask = __ballot(want);
     if (wmask) {
-      uint32_t base = 0;
-      if (lane == (uint32_t)__builtin_ctzll(wmask)) base = atomicAdd(pr.count, (unsigned int)__builtin_popcountll(wmask));
-      base = __shfl(base, __builtin_ctzll(wmask));
-      const uint32_t slot = base + (uint32_t)__builtin_popcountll(wmask & lt_mask);
+      const uint32_t slot = probe_wave_slot(pr.count, wmask, lane);
       if (want && slot < pr.cap) {
         lentil_probe_segment sg;
         sg.origin[0] = org[0]; sg.origin[1] = org[1]; sg.origin[2] = org[2];
@@ -4293,6 +4306,102 @@ __global__ __launch_bounds__(256) void tl_chroma_walk_kernel(TlChromaArgs a) {
     if (tot_accepted) atomicAdd(&a.ctr->accepted, tot_accepted);
   }
   flush_row_range(a.ctr, rmin, rmax_p1);
+}
+
+// ---- thin lens with abb_chromatic > 0 under an occlusion probe (src/lentil_filter.cpp:356-375, then :393-406) ---------------
+// The reference probes an attempt before its vignetting test and its colour draw; an occluded attempt is lost and draws no
+// colour -- to the walks it is what a vignetted one is: all three codes kCodeFail.  So the probes go between
+// tl_chroma_solve_kernel and the walk.  Which attempts the reference makes depends on the channels drawn, which the walk
+// alone knows; but an attempt whose three codes are all pixels counts whatever channel it draws, so no item goes past the
+// samples-th such attempt.  The host (redistribute_tl_chroma) loops: that bound per item, the surviving attempts below it
+// that have not been asked about yet listed and asked, the occluded ones failed -- which moves the bound on -- until a turn
+// lists nothing.  Attempts between the reference's real last one and the bound are asked about in vain; they change nothing.
+struct TlChromaProbe {
+  uint32_t *bound;               // [n_items] no attempt at or past it is made
+  const uint32_t *probed;        // [n_items] attempts below it have been asked about
+};
+
+// One wave per item, the walk's bookkeeping with "all three channels land in the frame" for a success: the index just past
+// the samples-th such attempt, or 5 * samples.
+__global__ __launch_bounds__(256) void tl_chroma_probe_bound_kernel(TlChromaArgs a, TlChromaProbe b) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const unsigned long long lt_mask = (1ull << lane) - 1ull;
+  for (uint32_t item = blockIdx.x * 4u + (threadIdx.x >> 6); item < a.n_items; item += gridDim.x * 4u) {
+    const uint32_t S = a.work[item].y, max_total = S * 5u;
+    const uint32_t *res = a.res + a.att_off[item] * 3ull;
+    uint32_t n = 0, acc = 0;
+    while (acc < S && n < max_total) {
+      const uint32_t my_n = n + lane;
+      bool all_in = false;
+      if (my_n < max_total) all_in = res[my_n * 3ull] < kCodeOut && res[my_n * 3ull + 1] < kCodeOut && res[my_n * 3ull + 2] < kCodeOut;
+      const unsigned long long im = __ballot(all_in);
+      const uint32_t rank = acc + (uint32_t)__builtin_popcountll(im & lt_mask);      // such attempts before this one
+      const unsigned long long lm = __ballot(all_in && rank + 1u == S);
+      const uint32_t step_n = (max_total - n) < 64u ? (max_total - n) : 64u;
+      if (lm) { n += (uint32_t)__builtin_ctzll(lm) + 1u; break; }
+      acc += (uint32_t)__builtin_popcountll(im);
+      n += step_n;
+    }
+    if (lane == 0) b.bound[item] = n;
+  }
+}
+
+// One wave per item: the surviving attempts in [probed, bound), as probe_list_kernel lists a round's thin-lens tries -- the
+// segment, and the attempt's slot in `res` (the host keeps the slots below 2^32 under a probe).
+__global__ __launch_bounds__(256) void tl_chroma_probe_list_kernel(TlChromaArgs a, TlChromaProbe b, ProbeArgs pr) {
+  const uint32_t lane = threadIdx.x & 63u;
+  for (uint32_t item = blockIdx.x * 4u + (threadIdx.x >> 6); item < a.n_items; item += gridDim.x * 4u) {
+    const uint32_t lo = b.probed[item], hi = b.bound[item];
+    if (lo >= hi) continue;
+    const uint32_t v = a.work[item].x;
+    const float4 pos_z = a.V.pos_z[v];
+    if (probe_from_skydome(pos_z)) continue;
+    const ItemVisit h = load_work_visit(a.P, a.V, a.work[item], 0.0);
+    float c2w[4][4];
+    probe_cam_to_world(a.V.cam, pr, a.V.raydir_time[v].w, c2w);
+    const uint64_t slot0 = a.att_off[item];
+    const uint32_t *res = a.res + slot0 * 3ull;
+    for (uint32_t n = lo; n < hi; n += 64u) {
+      const uint32_t my_n = n + lane;
+      bool want = false;
+      if (my_n < hi) want = !(res[my_n * 3ull] == kCodeFail && res[my_n * 3ull + 1] == kCodeFail && res[my_n * 3ull + 2] == kCodeFail);
+      float tgt[3] = {0.f, 0.f, 0.f};
+      if (want) {
+        TlRay ray;
+        if (thinlens_ray(a.P, a.bokeh, a.bokeh.cdfRow, h.I.cs, h.px, h.py, my_n, ray)) probe_target(a.P, c2w, ray.lx, ray.ly, 0.0f, tgt);
+        else want = false;       // (the optical vignetting test failed it: tl_chroma_solve_kernel has found the same)
+      }
+      const unsigned long long wmask = __ballot(want);
+      if (!wmask) continue;
+      const uint32_t slot = probe_wave_slot(pr.count, wmask, lane);
+      if (want && slot < pr.cap) {
+        lentil_probe_segment sg;
+        sg.origin[0] = pos_z.x; sg.origin[1] = pos_z.y; sg.origin[2] = pos_z.z;
+        sg.target[0] = tgt[0]; sg.target[1] = tgt[1]; sg.target[2] = tgt[2];
+        pr.seg[slot] = sg;
+        pr.idx[slot] = (uint32_t)(slot0 + my_n);
+      }
+    }
+  }
+}
+
+// The listed attempts the host found occluded (occluded null: every one of idx) are lost: all three codes kCodeFail.  With
+// `kept`, their slots are appended there (kept_count counts them) for a pass that is run again.
+__global__ __launch_bounds__(256) void tl_chroma_probe_apply_kernel(uint32_t *res, const uint32_t *idx, const uint8_t *occluded, uint32_t n,
+                                                                    uint32_t *kept, unsigned int *kept_count) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  const uint64_t n_up = ((uint64_t)n + 63u) & ~63ull;   // (whole waves go round the loop together)
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_up; i += stride) {
+    const bool occ = i < n && (!occluded || occluded[i]);
+    const uint32_t s = occ ? idx[i] : 0u;
+    if (occ) { uint32_t *dst = res + s * 3ull; dst[0] = kCodeFail; dst[1] = kCodeFail; dst[2] = kCodeFail; }
+    const unsigned long long om = __ballot(occ);
+    if (kept && om) {
+      const uint32_t k = probe_wave_slot(kept_count, om, lane);
+      if (occ) kept[k] = s;
+    }
+  }
 }
 
 // closest-filter AOVs: copy the winning visit's value into AOVData::buffer (src/lentil.h:835)

@@ -383,13 +383,13 @@ void LentilCamera::setup(AtUniverse *universe) {
   for (const lentil_aov_plan &a : aovs) kinds.push_back((uint8_t)lentil_aov_frame_kind(&a));
   if (!check(lentil_hip_alloc_frame(gpu, (uint32_t)aovs.size(), kinds.data()), "alloc_frame")) return;
   // scene occlusion along every backward trace, as the reference asks the renderer (LENTIL_OCCLUSION_PROBES=0: none; the
-  // camera-to-world matrices are the inverses of the world-to-camera keys above).  Not with a thin lens's chromatic
-  // aberration, whose colour draw the reference orders behind the probe (the library refuses the pair): said once, not probed.
+  // camera-to-world matrices are the inverses of the world-to-camera keys above).  The thin lens is probed with any
+  // abb_chromatic; polynomial optics with abb_chromatic != 0 is not (the library refuses the pair): said once, not probed.
   {
     const char *op = getenv("LENTIL_OCCLUSION_PROBES");
     bool probes = !(op && op[0] == '0');
-    if (probes && P.abb_chromatic != 0.0f) {
-      AiMsgWarning("[LENTIL BIDIRECTIONAL] abb_chromatic is set: scene occlusion along the redistributed rays is not probed");
+    if (probes && P.cameraType == LENTIL_POLYNOMIAL_OPTICS && P.abb_chromatic != 0.0f) {
+      AiMsgWarning("[LENTIL BIDIRECTIONAL] abb_chromatic is set on polynomial optics: scene occlusion along the redistributed rays is not probed");
       probes = false;
     }
     if (!check(lentil_hip_set_occlusion_probe(gpu, probes ? arnold_probe : nullptr, nullptr, nullptr), "set_occlusion_probe")) return;
