@@ -659,6 +659,42 @@ int lentil_hip_set_draw_log(lentil_hip_ctx *ctx, uint64_t capacity); /* 0 disabl
 int lentil_hip_download_draw_log(lentil_hip_ctx *ctx, lentil_draw_record *out, uint64_t capacity,
                                  uint64_t *n_records);
 
+/* --- forward camera rays in batches ---------------------------------------------------
+ * camera_create_ray (src/lentil_camera.cpp:78-125) for n camera samples at once: Camera::trace_ray_fw_po /
+ * trace_ray_fw_thinlens (src/lentil.h:283-569) for the ray and, at sx + dsx * 0.001f and sy + dsy * 0.001f, for the two
+ * rays its differentials are the finite differences to -- what lentil_host_camera_create_ray (lentil_host.h) computes for
+ * one ray on the CPU, operation for operation, one GPU lane per ray.  For a renderer whose camera samples live on the GPU.
+ * Uses the context's parameters, the table of set_lens (polynomial optics; the thin lens needs none) and the tables of
+ * set_bokeh (bokeh_enable_image); needs no frame and no visits.
+ *   in    [n][6]  sx, sy, dsx, dsy, lensx, lensy
+ *   out   [n][21] the layout of lentil_host_camera_ray: origin, dir, weight, dOdx, dOdy, dDdx, dDdy.  weight = exposure, or
+ *                 0 * exposure when every try of the ray was vignetted (polynomial optics: or a NaN came out)
+ *   tries [n]     optional: the vignetted tries of the ray's own trace (what trace_ray_fw_* returns for deriv_ray = 0)
+ * xor128 (src/global.h:22-27; the lens sample of a retry): the reference keeps one state per process in function statics.
+ * Here ray i owns one, derived from its id = first_ray + i (which must fit 32 bits): w0 = tea8(id, rng_seed),
+ * w1 = tea8(id, w0), w2 = tea8(id, w1), w3 = tea8(id, w2) (tea<8>, src/global.h:32-57), the generator's initial constants
+ * should all four come out zero -- so a batch does not depend on how it is split into calls.
+ * flags: LENTIL_RAYS_DEVICE_POINTERS: in / out / tries are device memory of the context's GPU; the call enqueues its kernel
+ * on lentil_hip_stream(ctx) and returns (order it with lentil_hip_sync or the stream).  Without it they are host memory and
+ * the call returns when out is filled.  LENTIL_RAYS_NO_DIFFERENTIALS: one trace per ray, the four derivative vectors zero.
+ * The call observes the context (a pass in flight is finished first) and takes no part in the streamed passes' turns.
+ * LENTIL_ERR_INVALID: no parameters, polynomial optics without a lens, bokeh_enable_image without tables, in or out NULL
+ * with n > 0, first_ray + n > 2^32.  n == 0 launches nothing. */
+#define LENTIL_RAYS_DEVICE_POINTERS 1u
+#define LENTIL_RAYS_NO_DIFFERENTIALS 2u
+typedef struct lentil_camera_ray_batch {
+  uint64_t n;              /* rays in this call */
+  uint64_t first_ray;      /* id of ray 0; ray i has id first_ray + i (must fit 32 bits) */
+  const float *in;         /* [n][6]: sx, sy, dsx, dsy, lensx, lensy -- the in[6] of lentil_host_camera_create_ray */
+  float *out;              /* [n][21]: layout of lentil_host_camera_ray (origin, dir, weight, dOdx, dOdy, dDdx, dDdy) */
+  int32_t *tries;          /* optional [n]: tries of the main trace (what trace_ray_fw_* returns for deriv_ray = 0) */
+  double lambda;           /* micrometres, PO only */
+  float exposure;
+  uint32_t rng_seed;
+  uint32_t flags;          /* LENTIL_RAYS_DEVICE_POINTERS: in/out/tries are device memory; LENTIL_RAYS_NO_DIFFERENTIALS */
+} lentil_camera_ray_batch;
+int lentil_hip_camera_rays(lentil_hip_ctx *ctx, const lentil_camera_ray_batch *batch);
+
 /* --- single-function device tests (parity of the optics primitives) -----------------
  * Runs n independent evaluations on the GPU; host pointers in/out.
  * lt_sample_aperture: Camera::lens_lt_sample_aperture (src/lentil.h:1296-1313) for

@@ -8,6 +8,8 @@ UNIT_MM, UNIT_CM, UNIT_DM, UNIT_M = 0, 1, 2, 3
 FILTER_GAUSSIAN, FILTER_CLOSEST, FILTER_VARIANCE, FILTER_CLOSEST_DEBUG = 0, 1, 2, 3
 GEOM_SPHERICAL, GEOM_CYL_Y, GEOM_CYL_X = 0, 1, 2
 OK, ERR_INVALID, ERR_HIP, ERR_UNSUPPORTED, ERR_NOMEM = 0, -1, -2, -3, -4
+RAYS_DEVICE_POINTERS, RAYS_NO_DIFFERENTIALS = 1, 2
+RAY_IN_FLOATS, RAY_OUT_FLOATS = 6, 21
 
 
 class Params(C.Structure):
@@ -102,3 +104,9 @@ class PassTotals(C.Structure):
 
 class DrawRecord(C.Structure):
     _fields_ = [("visit", C.c_uint32), ("attempt", C.c_uint32), ("pixel", C.c_uint32)]
+
+
+class CameraRayBatch(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("first_ray", C.c_uint64),
+                ("inp", C.c_void_p), ("out", C.c_void_p), ("tries", C.c_void_p),
+                ("lam", C.c_double), ("exposure", C.c_float), ("rng_seed", C.c_uint32), ("flags", C.c_uint32)]

@@ -28,7 +28,7 @@ EXPORTS = [
     "lentil_hip_download_draw_log", "lentil_hip_test_lt_sample_aperture",
     "lentil_hip_test_trace_bw_po", "lentil_hip_test_aperture_sample", "lentil_hip_debug_scan_bands", "lentil_hip_debug_last_scan",
     "lentil_hip_lens_is_compiled", "lentil_hip_set_lens_mode",
-    "lentil_hip_focus_search", "lentil_hip_test_y0_intersection",
+    "lentil_hip_focus_search", "lentil_hip_test_y0_intersection", "lentil_hip_camera_rays",
     "lentil_hip_set_xor128_state", "lentil_hip_get_xor128_state", "lentil_hip_tl_chroma_stats", "lentil_hip_test_xor128_jump",
     "lentil_hip_host_alloc", "lentil_hip_host_free", "lentil_hip_visits_begin", "lentil_hip_visits_append",
     "lentil_hip_visits_wait", "lentil_hip_visits_end",
@@ -62,6 +62,31 @@ def process_stall_notes():
     buf = C.create_string_buffer(1 << 14)
     lib.lentil_hip_process_stall_notes(buf, 1 << 14)
     return buf.value.decode(errors="replace")
+
+
+def _tea8(v0, v1):
+    """tea<8> (src/global.h:32-57) on uint32 arrays"""
+    v0 = np.asarray(v0, np.uint32).copy()
+    v1 = np.broadcast_to(np.asarray(v1, np.uint32), v0.shape).copy()
+    s0 = np.uint32(0)
+    with np.errstate(over="ignore"):
+        for _ in range(8):
+            s0 = np.uint32((int(s0) + 0x9E3779B9) & 0xFFFFFFFF)
+            v0 += ((v1 << np.uint32(4)) + np.uint32(0xA341316C)) ^ (v1 + s0) ^ ((v1 >> np.uint32(5)) + np.uint32(0xC8013EA4))
+            v1 += ((v0 << np.uint32(4)) + np.uint32(0xAD90777D)) ^ (v0 + s0) ^ ((v0 >> np.uint32(5)) + np.uint32(0x7E95761E))
+    return v0
+
+
+def ray_rng_state(ray_id, seed):
+    """The xor128 state (uint32 [..., 4]) lentil_hip_camera_rays starts ray `ray_id` from: w0 = tea8(id, seed), w1 = tea8(id, w0),
+    w2 = tea8(id, w1), w3 = tea8(id, w2); the generator's initial constants where all four are zero."""
+    rid = np.asarray(ray_id, np.uint32)
+    w = [_tea8(rid, np.uint32(int(seed) & 0xFFFFFFFF))]
+    for _ in range(3):
+        w.append(_tea8(rid, w[-1]))
+    st = np.stack(w, -1)
+    st[~st.any(-1)] = np.array([123456789, 362436069, 521288629, 88675123], np.uint32)
+    return st
 
 
 class LentilError(RuntimeError):
@@ -155,6 +180,7 @@ def load_library():
         "lentil_hip_lens_is_compiled": (i, [vp]),
         "lentil_hip_set_lens_mode": (i, [vp, i]),
         "lentil_hip_focus_search": (i, [vp, C.c_double, C.c_double, C.POINTER(C.c_double)]),
+        "lentil_hip_camera_rays": (i, [vp, C.POINTER(_abi.CameraRayBatch)]),
         "lentil_hip_set_xor128_state": (i, [vp, C.POINTER(C.c_uint32)]),
         "lentil_hip_get_xor128_state": (i, [vp, C.POINTER(C.c_uint32)]),
         "lentil_hip_tl_chroma_stats": (i, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
@@ -257,6 +283,7 @@ class Context:
     def __init__(self, device=0):
         self.lib = load_library()
         self.h = C.c_void_p()
+        self.device = int(device)
         rc = self.lib.lentil_hip_create(device, C.byref(self.h))
         if rc:
             raise LentilError(rc, (self.lib.lentil_hip_last_error(None) or b"").decode())
@@ -411,6 +438,45 @@ class Context:
         best = C.c_double()
         self._chk(self.lib.lentil_hip_focus_search(self.h, focal_distance, lam, C.byref(best)))
         return best.value
+
+    def camera_rays(self, inp, first_ray=0, lam=0.55, exposure=1.0, seed=0, differentials=True, want_tries=False):
+        """Forward camera rays in a batch (lentil_hip_camera_rays): camera_create_ray for every row of inp, fp32 [n, 6] =
+        sx, sy, dsx, dsy, lensx, lensy -> fp32 [n, 21] = origin, dir, weight, dOdx, dOdy, dDdx, dDdy (and, want_tries, int32
+        [n]: the vignetted tries of each ray's own trace).  Ray i draws its retries from its own xor128 state, the four
+        words ray_rng_state(first_ray + i, seed) -- the same whatever batch the ray is part of.
+        numpy in: host pointers, numpy out, complete on return.  A contiguous torch tensor on this context's device: device
+        pointers, torch tensors out, enqueued on the context's stream (stream()) without waiting.  The caller orders both ends:
+        whatever produced inp must be complete on, or ordered before, the context's stream; sync() or the stream orders the
+        results; and inp and the returned tensors must stay alive until the stream has passed the call."""
+        flags = 0 if differentials else _abi.RAYS_NO_DIFFERENTIALS
+        b = _abi.CameraRayBatch()
+        if isinstance(inp, np.ndarray) or not hasattr(inp, "data_ptr"):
+            a = np.ascontiguousarray(inp, np.float32)
+            if a.ndim != 2 or a.shape[1] != _abi.RAY_IN_FLOATS:
+                raise ValueError("camera_rays: inp must be [n, 6]")
+            n = a.shape[0]
+            out = np.empty((n, _abi.RAY_OUT_FLOATS), np.float32)
+            tries = np.empty((n,), np.int32) if want_tries else None
+            ptrs = (a.ctypes.data, out.ctypes.data, tries.ctypes.data if want_tries else None)
+        else:
+            import torch
+            if inp.dtype != torch.float32 or inp.dim() != 2 or inp.shape[1] != _abi.RAY_IN_FLOATS:
+                raise ValueError("camera_rays: inp must be a float32 [n, 6] tensor")
+            if not inp.is_cuda or inp.device.index != self.device:
+                raise ValueError("camera_rays: inp is on %s, the context on GPU %d" % (inp.device, self.device))
+            if not inp.is_contiguous():      # (a copy here would run on torch's stream, unordered with the context's)
+                raise ValueError("camera_rays: inp must be contiguous")
+            a = inp
+            n = a.shape[0]
+            out = torch.empty((n, _abi.RAY_OUT_FLOATS), dtype=torch.float32, device=a.device)
+            tries = torch.empty((n,), dtype=torch.int32, device=a.device) if want_tries else None
+            ptrs = (a.data_ptr(), out.data_ptr(), tries.data_ptr() if want_tries else None)
+            flags |= _abi.RAYS_DEVICE_POINTERS
+        b.n, b.first_ray = n, int(first_ray)
+        b.inp, b.out, b.tries = (p if n else None for p in ptrs)
+        b.lam, b.exposure, b.rng_seed, b.flags = float(lam), float(exposure), int(seed) & 0xFFFFFFFF, flags
+        self._chk(self.lib.lentil_hip_camera_rays(self.h, C.byref(b)))
+        return (out, tries) if want_tries else out
 
     def test_y0_intersection(self, sensor_shift, lam):
         import numpy as np

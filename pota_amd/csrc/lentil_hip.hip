@@ -19,6 +19,7 @@
 #include "lentil_closest_replay.h"
 #include "lentil_tl_chroma_mgpu.h"
 #include "lentil_lens_jit.h"
+#include "lentil_camera_rays.h"
 #include "generated/embedded_sources.inc"
 
 #define LENTIL_API extern "C" __attribute__((visibility("default")))
@@ -4791,6 +4792,48 @@ LENTIL_API int lentil_hip_test_aperture_sample(lentil_hip_ctx *ctx, uint64_t n, 
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   HIP_TRY(ctx, hipMemcpy(xy, o0, n * 2 * 8, hipMemcpyDeviceToHost));
+  return LENTIL_OK;
+}
+
+// ---- forward camera rays in batches (lentil_camera_rays.h) -------------------------------------------------------------
+LENTIL_API int lentil_hip_camera_rays(lentil_hip_ctx *ctx, const lentil_camera_ray_batch *batch) {
+  CHECK_CTX(ctx);
+  if (!batch) return fail(ctx, LENTIL_ERR_INVALID, "batch is null");
+  if (!ctx->have_params) return fail(ctx, LENTIL_ERR_INVALID, "set_params first");
+  const bool po = ctx->P.cameraType == LENTIL_POLYNOMIAL_OPTICS;
+  if (po && !ctx->have_lens) return fail(ctx, LENTIL_ERR_INVALID, "a polynomial-optics camera needs set_lens first");
+  if (ctx->P.bokeh_enable_image && !ctx->have_bokeh) return fail(ctx, LENTIL_ERR_INVALID, "bokeh_enable_image needs set_bokeh first");
+  const uint64_t n = batch->n;
+  if (batch->first_ray > (1ull << 32) || n > (1ull << 32) - batch->first_ray)
+    return fail(ctx, LENTIL_ERR_INVALID, "ray ids first_ray ... first_ray + n - 1 must fit 32 bits");
+  if (!n) return LENTIL_OK;
+  if (!batch->in || !batch->out) return fail(ctx, LENTIL_ERR_INVALID, "in / out is null");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  CameraRayArgs a{};
+  a.P = ctx->P; a.lens = po ? ctx->d_lens : nullptr; a.terms = po ? ctx->d_terms : nullptr; a.bokeh = ctx->bokeh;
+  a.n = n; a.first_ray = (uint32_t)batch->first_ray; a.differentials = (batch->flags & LENTIL_RAYS_NO_DIFFERENTIALS) ? 0u : 1u;
+  a.lambda = batch->lambda; a.exposure = batch->exposure; a.rng_seed = batch->rng_seed;
+  const bool device = (batch->flags & LENTIL_RAYS_DEVICE_POINTERS) != 0u;
+  TmpFree tf;
+  float *d_in = nullptr, *d_out = nullptr;
+  int32_t *d_tries = nullptr;
+  if (device) {
+    a.in = batch->in; a.out = batch->out; a.tries = batch->tries;
+  } else {
+    int rc;
+    if ((rc = dev_copy_in(ctx, batch->in, (size_t)n * kRayInFloats, &d_in, tf.v))) return rc;
+    if ((rc = dev_alloc(ctx, (size_t)n * kRayOutFloats, &d_out, tf.v))) return rc;
+    if (batch->tries && (rc = dev_alloc(ctx, (size_t)n, &d_tries, tf.v))) return rc;
+    a.in = d_in; a.out = d_out; a.tries = d_tries;
+  }
+  const dim3 grid((unsigned)((n + kRayBlock - 1) / kRayBlock));
+  if (po) hipLaunchKernelGGL(camera_rays_kernel<true>, grid, dim3(kRayBlock), 0, ctx->stream, a);
+  else hipLaunchKernelGGL(camera_rays_kernel<false>, grid, dim3(kRayBlock), 0, ctx->stream, a);
+  HIP_TRY(ctx, hipGetLastError());
+  if (device) return LENTIL_OK;
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  HIP_TRY(ctx, hipMemcpy(batch->out, d_out, (size_t)n * kRayOutFloats * sizeof(float), hipMemcpyDeviceToHost));
+  if (batch->tries) HIP_TRY(ctx, hipMemcpy(batch->tries, d_tries, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
   return LENTIL_OK;
 }
 
