@@ -276,7 +276,8 @@ int lentil_hip_set_bokeh(lentil_hip_ctx *ctx, const lentil_bokeh_table *bokeh);
  * tables it ships (tools/gen_lens_code.py) and recognises them by a hash of the table passed to
  * set_lens.  Any other table runs through the LDS table interpreter (same arithmetic, slower).
  * lens_is_compiled: 1 if the current table has a compiled-in kernel.  set_lens_mode: 0 = auto,
- * 1 = always interpret the table (parity tests compare the two). */
+ * 1 = always interpret the table (parity tests compare the two) -- in the passes' solve kernels, in
+ * lentil_hip_camera_rays and in lentil_hip_focus_search alike. */
 int lentil_hip_lens_is_compiled(lentil_hip_ctx *ctx);
 int lentil_hip_set_lens_mode(lentil_hip_ctx *ctx, int mode);
 /* A table that has no kernel compiled into the library gets one at run time -- the reference compiles every lens into the plugin
@@ -291,7 +292,7 @@ int lentil_hip_lens_jit_status(lentil_hip_ctx *ctx, int *state, double *compile_
 int lentil_hip_lens_jit_wait(lentil_hip_ctx *ctx, double timeout_seconds);
 int lentil_hip_debug_lens_jit_source(lentil_hip_ctx *ctx, char *buf, uint64_t capacity, uint64_t *length);
 /* ... and without a context or a GPU (hiprtc cross-compiles): pack the table, emit the lens code and, compile != 0, compile the
- * four solve kernels; the emitted source and the compiler's log are copied out (truncated to the capacities). */
+ * four solve kernels and the camera-rays kernel; the emitted source and the compiler's log are copied out (truncated to the capacities). */
 int lentil_hip_debug_lens_jit_compile(const lentil_lens_table *t, int compile, char *source, uint64_t source_capacity,
                                       uint64_t *source_length, char *log, uint64_t log_capacity, double *seconds, uint64_t *code_bytes);
 int lentil_hip_alloc_frame(lentil_hip_ctx *ctx, uint32_t n_aovs, const uint8_t *aov_filter_kind);
@@ -694,6 +695,13 @@ typedef struct lentil_camera_ray_batch {
   uint32_t flags;          /* LENTIL_RAYS_DEVICE_POINTERS: in/out/tries are device memory; LENTIL_RAYS_NO_DIFFERENTIALS */
 } lentil_camera_ray_batch;
 int lentil_hip_camera_rays(lentil_hip_ctx *ctx, const lentil_camera_ray_batch *batch);
+/* What the last lentil_hip_camera_rays call of this context ran: *path 0 the thin lens (or no call yet), 1 the table
+ * interpreter, 2 the straight-line kernel of a compiled-in lens, 3 the kernel compiled for the table at run time (once
+ * lentil_hip_lens_jit_status reports state 2; until then, and after a failed compilation, the interpreter).  The rays are the
+ * same bit for bit whichever ran.  Paths 2 and 3 are taken by a context created with LENTIL_RAYS_COMPILED=1 in the
+ * environment; without it, or with LENTIL_RAYS_COMPILED=0, camera rays run path 1 (the default until the compiled kernels'
+ * rate has been measured against the interpreter's).  lentil_hip_set_lens_mode(ctx, 1) forces path 1 too. */
+int lentil_hip_camera_rays_path(lentil_hip_ctx *ctx, int *path);
 
 /* --- single-function device tests (parity of the optics primitives) -----------------
  * Runs n independent evaluations on the GPU; host pointers in/out.

@@ -10,6 +10,7 @@ GEOM_SPHERICAL, GEOM_CYL_Y, GEOM_CYL_X = 0, 1, 2
 OK, ERR_INVALID, ERR_HIP, ERR_UNSUPPORTED, ERR_NOMEM = 0, -1, -2, -3, -4
 RAYS_DEVICE_POINTERS, RAYS_NO_DIFFERENTIALS = 1, 2
 RAY_IN_FLOATS, RAY_OUT_FLOATS = 6, 21
+RAYS_PATH_THIN_LENS, RAYS_PATH_INTERPRETER, RAYS_PATH_COMPILED_IN, RAYS_PATH_RUN_TIME = 0, 1, 2, 3      # lentil_hip_camera_rays_path
 
 
 class Params(C.Structure):

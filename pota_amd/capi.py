@@ -28,7 +28,7 @@ EXPORTS = [
     "lentil_hip_download_draw_log", "lentil_hip_test_lt_sample_aperture",
     "lentil_hip_test_trace_bw_po", "lentil_hip_test_aperture_sample", "lentil_hip_debug_scan_bands", "lentil_hip_debug_last_scan",
     "lentil_hip_lens_is_compiled", "lentil_hip_set_lens_mode",
-    "lentil_hip_focus_search", "lentil_hip_test_y0_intersection", "lentil_hip_camera_rays",
+    "lentil_hip_focus_search", "lentil_hip_test_y0_intersection", "lentil_hip_camera_rays", "lentil_hip_camera_rays_path",
     "lentil_hip_set_xor128_state", "lentil_hip_get_xor128_state", "lentil_hip_tl_chroma_stats", "lentil_hip_test_xor128_jump",
     "lentil_hip_host_alloc", "lentil_hip_host_free", "lentil_hip_visits_begin", "lentil_hip_visits_append",
     "lentil_hip_visits_wait", "lentil_hip_visits_end",
@@ -181,6 +181,7 @@ def load_library():
         "lentil_hip_set_lens_mode": (i, [vp, i]),
         "lentil_hip_focus_search": (i, [vp, C.c_double, C.c_double, C.POINTER(C.c_double)]),
         "lentil_hip_camera_rays": (i, [vp, C.POINTER(_abi.CameraRayBatch)]),
+        "lentil_hip_camera_rays_path": (i, [vp, C.POINTER(C.c_int)]),
         "lentil_hip_set_xor128_state": (i, [vp, C.POINTER(C.c_uint32)]),
         "lentil_hip_get_xor128_state": (i, [vp, C.POINTER(C.c_uint32)]),
         "lentil_hip_tl_chroma_stats": (i, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
@@ -318,7 +319,8 @@ class Context:
         return bool(self.lib.lentil_hip_lens_is_compiled(self.h))
 
     def set_lens_mode(self, mode):
-        """0 = compiled-in kernel when the table is a shipped lens, 1 = always the table interpreter."""
+        """0 = compiled-in kernel when the table is a shipped lens, 1 = always the table interpreter (passes, camera rays and
+        the focus search)."""
         self._chk(self.lib.lentil_hip_set_lens_mode(self.h, mode))
 
     def set_bokeh(self, tables):
@@ -477,6 +479,13 @@ class Context:
         b.lam, b.exposure, b.rng_seed, b.flags = float(lam), float(exposure), int(seed) & 0xFFFFFFFF, flags
         self._chk(self.lib.lentil_hip_camera_rays(self.h, C.byref(b)))
         return (out, tries) if want_tries else out
+
+    def camera_rays_path(self):
+        """What the last camera_rays call ran: one of _abi.RAYS_PATH_* (lentil_hip_camera_rays_path).  The compiled paths need
+        LENTIL_RAYS_COMPILED=1 in the environment when the context is created; the default is the interpreter."""
+        path = C.c_int()
+        self._chk(self.lib.lentil_hip_camera_rays_path(self.h, C.byref(path)))
+        return path.value
 
     def test_y0_intersection(self, sensor_shift, lam):
         import numpy as np

@@ -12,7 +12,9 @@
 // a lane that is done (or past the batch's end) computes along on the values it has and commits nothing.  The three
 // traces are one wave-uniform loop for the same reason.  (The Newton loop inside lens_pt_sample_aperture still ends
 // per lane, as in focus_miss_kernel: every lane reads the same term, so the value readfirstlane returns is right for
-// whichever lanes are still iterating.)
+// whichever lanes are still iterating.)  A compiled lens (GenLens<Gen>: the polynomials as straight-line code, no
+// readfirstlane) runs the same uniform loops: a wave lasts as long as its slowest lane whether the others leave or
+// compute along, and one body of trace_ray_fw_po serves every lens type.
 //
 // xor128.  The reference redraws the lens sample of a vignetted try from xor128 (src/global.h:22-27), whose state
 // it keeps in function statics -- one per process, advanced by whichever thread gets there first.  Here every ray
@@ -78,7 +80,8 @@ LD_DEV void fw_lens_sample(const lentil_params &P, const DevBokeh &B, RayRng &rn
 
 // Camera::trace_ray_fw_po, src/lentil.h:283-427.  A differential trace (deriv_ray) keeps r1, r2, so every one of its
 // tries computes what its first did: it makes that one try only (its try count is not part of the result).
-LD_DEV void trace_ray_fw_po(const lentil_params &P, const LdsLens &L, const DevBokeh &B, RayRng &rng, double sx, double sy,
+template <class Lens>
+LD_DEV void trace_ray_fw_po(const lentil_params &P, const Lens &L, const DevBokeh &B, RayRng &rng, double sx, double sy,
                             double &r1, double &r2, bool deriv_ray, bool active, FwRay &ray) {
   const DevLens &k = L.consts();
   const int last_try = (deriv_ray && P.vignetting_retries > 0) ? 0 : P.vignetting_retries;
@@ -189,14 +192,19 @@ LD_DEV void trace_ray_fw_thinlens(const lentil_params &P, const DevBokeh &B, Ray
 
 // One lane per ray, 256 rays per block.  A block's input (24 B per ray) and output (84 B per ray) are contiguous in
 // memory: both go through LDS, lanes moving consecutive dwords, so that no lane strides through 21 dwords of its own.
-template <bool PO>
+// LensT / kTables: LdsLens with the term table staged into LDS (the interpreter; also the thin lens's, which has no lens:
+// PO false), or GenLens<Gen> of a compiled-in or run-time lens -- straight-line polynomials, only the header, the lambda
+// powers and the I/O buffer in LDS.
+template <class LensT, bool kTables, bool PO>
 __global__ __launch_bounds__(kRayBlock) void camera_rays_kernel(CameraRayArgs a) {
-  __shared__ DevTerm s_terms[PO ? kMaxTerms : 1];
+  __shared__ DevTerm s_terms[kTables ? kMaxTerms : 1];
   __shared__ DevLens s_k;
   __shared__ float s_io[kRayBlock * kRayOutFloats];
   if (PO) {
-    const uint32_t nt = a.lens->n_terms;
-    for (uint32_t i = threadIdx.x; i < nt; i += kRayBlock) s_terms[i] = a.terms[i];
+    if (kTables) {
+      const uint32_t nt = a.lens->n_terms;
+      for (uint32_t i = threadIdx.x; i < nt; i += kRayBlock) s_terms[i] = a.terms[i];
+    }
     if (threadIdx.x == 0) {
       s_k = *a.lens;
       s_k.lambda_pow[0] = 1.0; s_k.lambda_pow[1] = a.lambda;
@@ -214,7 +222,9 @@ __global__ __launch_bounds__(kRayBlock) void camera_rays_kernel(CameraRayArgs a)
   for (int c = 0; c < kRayInFloats; ++c) in[c] = s_io[li * kRayInFloats + c];
   __syncthreads();                                             // (s_io takes the output next)
 
-  const LdsLens L{s_terms, &s_k};
+  LensT L{};
+  if constexpr (kTables) L.terms = s_terms;
+  L.k = &s_k;
   RayRng rng = ray_rng_init(a.first_ray + (uint32_t)ray0 + li, a.rng_seed);
   double r1 = (double)in[4], r2 = (double)in[5];
   const float step = 0.001f;

@@ -323,6 +323,19 @@ struct LdsLens {
     Jout[2] = eval(P_DOUT_10, v); Jout[3] = eval(P_DOUT_11, v);
   }
   LD_DEV double transmittance(const double v[4]) const { return eval(P_OUT_T, v); }
+  // one Newton step of lens_pt_sample_aperture, and lens_evaluate's four outer-pupil polynomials
+  LD_DEV void eval_fw_newton(const double v[4], double pred_ap[2], double pred_dir[2], double Jap[4], double Jappos[4]) const {
+    pred_ap[0] = eval(P_AP_X, v); pred_ap[1] = eval(P_AP_Y, v);
+    pred_dir[0] = eval(P_AP_DX, v); pred_dir[1] = eval(P_AP_DY, v);
+    Jap[0] = eval(P_DAP_00, v); Jappos[0] = eval(P_DAPPOS_00, v);
+    Jap[1] = eval(P_DAP_01, v); Jappos[1] = eval(P_DAPPOS_01, v);
+    Jap[2] = eval(P_DAP_10, v); Jappos[2] = eval(P_DAPPOS_10, v);
+    Jap[3] = eval(P_DAP_11, v); Jappos[3] = eval(P_DAPPOS_11, v);
+  }
+  LD_DEV void eval_out(const double v[4], double out[4]) const {
+    out[0] = eval(P_OUT_X, v); out[1] = eval(P_OUT_Y, v);
+    out[2] = eval(P_OUT_DX, v); out[3] = eval(P_OUT_DY, v);
+  }
   LD_DEV const DevLens &consts() const { return *k; }
 };
 
@@ -409,30 +422,34 @@ LD_DEV void newton_iter(const Lens &L, const double scene[3], double ap_x, doubl
 // polynomial-optics generator emits it: at most 5 Newton steps on the direction at the sensor, tolerance 1e-4, the
 // Jacobian with the dist * d/dpos chain term of the shifted start point), and on top of them
 // Camera::camera_get_y0_intersection_distance (:1361-1386) -- what the focus search evaluates per candidate.
-// Table interpreter only (a camera update runs them 20 001 times, not per draw).
+// Lens: LdsLens (the table interpreter) or GenLens<Gen> (straight-line code, eval_fw_newton / eval_out / transmittance of
+// tools/gen_lens_code.py); either way every polynomial is the same operations in the same order.
 // ---------------------------------------------------------------------------------------
-LD_DEV double lens_evaluate(const LdsLens &L, const double in[4], double out[4]) {
-  out[0] = L.eval(P_OUT_X, in); out[1] = L.eval(P_OUT_Y, in);
-  out[2] = L.eval(P_OUT_DX, in); out[3] = L.eval(P_OUT_DY, in);
-  return fmax(0.0, L.eval(P_OUT_T, in));
+template <class Lens>
+LD_DEV double lens_evaluate(const Lens &L, const double in[4], double out[4]) {
+  L.eval_out(in, out);
+  return fmax(0.0, L.transmittance(in));
 }
 
 // in: x, y, dx, dy at the sensor (dx, dy solved for); ap_x, ap_y: the aperture point to hit; out_dx/out_dy: the
 // direction predicted at the aperture
-LD_DEV void lens_pt_sample_aperture(const LdsLens &L, double in[4], double ap_x, double ap_y, double dist,
+template <class Lens>
+LD_DEV void lens_pt_sample_aperture(const Lens &L, double in[4], double ap_x, double ap_y, double dist,
                                     double &out_dx, double &out_dy) {
   double dx = in[2], dy = in[3];
   double pred_dx = 0.0, pred_dy = 0.0;
   double sqr_err = 3.4028234663852886e38;
   for (int k = 0; k < 5 && sqr_err > 1e-4; ++k) {
     const double begin[4] = {in[0] + dist * dx, in[1] + dist * dy, dx, dy};
-    const double pred_x = L.eval(P_AP_X, begin), pred_y = L.eval(P_AP_Y, begin);
-    pred_dx = L.eval(P_AP_DX, begin);
-    pred_dy = L.eval(P_AP_DY, begin);
-    const double j00 = L.eval(P_DAP_00, begin) + dist * L.eval(P_DAPPOS_00, begin);
-    const double j01 = L.eval(P_DAP_01, begin) + dist * L.eval(P_DAPPOS_01, begin);
-    const double j10 = L.eval(P_DAP_10, begin) + dist * L.eval(P_DAPPOS_10, begin);
-    const double j11 = L.eval(P_DAP_11, begin) + dist * L.eval(P_DAPPOS_11, begin);
+    double pred[2], pred_dir[2], Jap[4], Jappos[4];
+    L.eval_fw_newton(begin, pred, pred_dir, Jap, Jappos);
+    const double pred_x = pred[0], pred_y = pred[1];
+    pred_dx = pred_dir[0];
+    pred_dy = pred_dir[1];
+    const double j00 = Jap[0] + dist * Jappos[0];
+    const double j01 = Jap[1] + dist * Jappos[1];
+    const double j10 = Jap[2] + dist * Jappos[2];
+    const double j11 = Jap[3] + dist * Jappos[3];
     const double invdet = 1.0 / (j00 * j11 - j01 * j10);
     const double i00 = j11 * invdet, i11 = j00 * invdet, i01 = -j01 * invdet, i10 = -j10 * invdet;
     const double r0 = ap_x - pred_x, r1 = ap_y - pred_y;
@@ -452,7 +469,8 @@ LD_DEV double y0_plane_z(const double pos[3], const double dir[3]) {
   return pos[2] + (dz * (0.0 - pos[1])) / dy;
 }
 
-LD_DEV double camera_get_y0_intersection_distance(const LdsLens &L, double sensor_shift, double aperture_housing_radius,
+template <class Lens>
+LD_DEV double camera_get_y0_intersection_distance(const Lens &L, double sensor_shift, double aperture_housing_radius,
                                                   double sensor_out[4], double out[4], double &transmittance) {
   const DevLens &k = L.consts();
   double sensor[4] = {0.0, 0.0, 0.0, 0.0};
@@ -506,6 +524,10 @@ struct GenLens {
     Gen::eval_bw(v, k->lambda_pow, pred_ap, Jap, out, Jout);
   }
   LD_DEV double transmittance(const double v[4]) const { return Gen::transmittance(v, k->lambda_pow); }
+  LD_DEV void eval_fw_newton(const double v[4], double pred_ap[2], double pred_dir[2], double Jap[4], double Jappos[4]) const {
+    Gen::eval_fw_newton(v, k->lambda_pow, pred_ap, pred_dir, Jap, Jappos);
+  }
+  LD_DEV void eval_out(const double v[4], double out[4]) const { Gen::eval_out(v, k->lambda_pow, out); }
   LD_DEV const DevLens &consts() const { return *k; }
 };
 

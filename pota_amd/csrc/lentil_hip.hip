@@ -75,8 +75,13 @@ struct lentil_hip_ctx {
   std::shared_ptr<lentil_jit::Entry> jit;
   hipModule_t jit_module = nullptr;
   hipFunction_t jit_fn[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+  hipFunction_t jit_rays_fn = nullptr;       // camera_rays_kernel of the same code object
   bool jit_loaded = false, jit_load_failed = false;
   bool use_generated = true;          // LENTIL_FORCE_TABLES=1 forces the table interpreter
+  // lentil_hip_camera_rays through the lens's compiled kernel (LENTIL_RAYS_COMPILED=1) or through the interpreter (=0, and
+  // the default: the compiled kernels' rate against the interpreter's has not been measured on an MI355X)
+  bool rays_compiled = false;
+  int rays_path = 0;                  // what the last lentil_hip_camera_rays call ran (lentil_hip_camera_rays_path)
 
   DevBokeh bokeh{};
   bool have_bokeh = false;
@@ -633,6 +638,7 @@ LENTIL_API int lentil_hip_create(int device, lentil_hip_ctx **out_ctx) {
   if (const char *e = getenv("LENTIL_PREDICT")) ctx->predict = e[0] != '0';
   if (const char *e = getenv("LENTIL_PREDICT_MAX_DRAWS")) ctx->predict_max_draws = strtoull(e, nullptr, 10);
   if (const char *e = getenv("LENTIL_LENS_JIT")) ctx->jit_enabled = e[0] != '0';
+  if (const char *e = getenv("LENTIL_RAYS_COMPILED")) ctx->rays_compiled = e[0] != '0';
   if (const char *e = getenv("LENTIL_SCAN_CUS_PCT_MULTI")) { ctx->scan_cus_pct_multi = atoi(e); if (ctx->scan_cus_pct_multi < 25) ctx->scan_cus_pct_multi = 25; if (ctx->scan_cus_pct_multi > 100) ctx->scan_cus_pct_multi = 100; }
   if (const char *e = getenv("LENTIL_SCAN_CUS_PCT")) { ctx->scan_cus_pct = atoi(e); if (ctx->scan_cus_pct < 25) ctx->scan_cus_pct = 25; if (ctx->scan_cus_pct > 100) ctx->scan_cus_pct = 100; }
   if (const char *e = getenv("LENTIL_PREDICT_GRID")) {
@@ -891,12 +897,13 @@ static std::vector<std::string> jit_flags(const std::string &arch) {
 }
 // the layouts the run-time kernels share with this library, checked inside their translation unit
 static std::string jit_layout_checks() {
-  char b[512];
+  char b[768];
   snprintf(b, sizeof b,
            "static_assert(sizeof(DrawArgs) == %zu, \"DrawArgs differs from the library's\");\n"
            "static_assert(sizeof(DevCounters) == %zu, \"DevCounters differs from the library's\");\n"
-           "static_assert(sizeof(SlowRec) == %zu && sizeof(Task) == %zu && sizeof(ItemProg) == %zu, \"queue records differ from the library's\");\n",
-           sizeof(DrawArgs), sizeof(DevCounters), sizeof(SlowRec), sizeof(Task), sizeof(ItemProg));
+           "static_assert(sizeof(SlowRec) == %zu && sizeof(Task) == %zu && sizeof(ItemProg) == %zu, \"queue records differ from the library's\");\n"
+           "static_assert(sizeof(CameraRayArgs) == %zu, \"CameraRayArgs differs from the library's\");\n",
+           sizeof(DrawArgs), sizeof(DevCounters), sizeof(SlowRec), sizeof(Task), sizeof(ItemProg), sizeof(CameraRayArgs));
   return b;
 }
 static std::string device_arch(int device) {
@@ -910,7 +917,7 @@ static std::string device_arch(int device) {
 // what a cached code object must have been built from: the kernel sources, the flags, the architecture, the compiler
 static uint64_t jit_source_hash(const std::string &arch) {
   static const uint64_t base = [] {
-    uint64_t v = lentil_jit::fnv("lentil-jit-2", 12);
+    uint64_t v = lentil_jit::fnv("lentil-jit-3", 12);       // (-3: the code object holds the camera-rays kernel too)
     for (const lentil_jit::Source &s : kEmbeddedSources) v = lentil_jit::fnv(s.text, strlen(s.text), v);
     for (const char *f : kBuildFlags) v = lentil_jit::fnv(f, strlen(f), v);
     const std::string chk = jit_layout_checks();
@@ -977,19 +984,40 @@ static void jit_request(lentil_hip_ctx *ctx) {
   }
 }
 // the compiled kernels for this context's device, once the code object is there (null: not yet / not at all)
-static hipFunction_t jit_function(lentil_hip_ctx *ctx, bool chroma, bool stream) {
-  if (!ctx->jit || !ctx->use_generated || ctx->jit_load_failed) return nullptr;
+static bool jit_module_ready(lentil_hip_ctx *ctx) {
+  if (!ctx->jit || !ctx->use_generated || ctx->jit_load_failed) return false;
   if (!ctx->jit_loaded) {
-    if (ctx->jit->state.load() != lentil_jit::Entry::kReady) return nullptr;
+    if (ctx->jit->state.load() != lentil_jit::Entry::kReady) return false;
     (void)hipSetDevice(ctx->device);
     bool ok = hipModuleLoadData(&ctx->jit_module, ctx->jit->co.code.data()) == hipSuccess;
     for (int c = 0; c < 2 && ok; ++c)
       for (int s2 = 0; s2 < 2 && ok; ++s2)
         ok = hipModuleGetFunction(&ctx->jit_fn[c][s2], ctx->jit_module, ctx->jit->co.name[c][s2].c_str()) == hipSuccess;
-    if (!ok) { (void)hipGetLastError(); ctx->jit_load_failed = true; return nullptr; }
+    ok = ok && hipModuleGetFunction(&ctx->jit_rays_fn, ctx->jit_module, ctx->jit->co.rays_name.c_str()) == hipSuccess;
+    if (!ok) { (void)hipGetLastError(); ctx->jit_load_failed = true; return false; }
     ctx->jit_loaded = true;
   }
-  return ctx->jit_fn[chroma ? 1 : 0][stream ? 1 : 0];
+  return true;
+}
+static hipFunction_t jit_function(lentil_hip_ctx *ctx, bool chroma, bool stream) {
+  return jit_module_ready(ctx) ? ctx->jit_fn[chroma ? 1 : 0][stream ? 1 : 0] : nullptr;
+}
+static hipFunction_t jit_rays_function(lentil_hip_ctx *ctx) { return jit_module_ready(ctx) ? ctx->jit_rays_fn : nullptr; }
+
+// the table as the kernels and the emitter read it: the nine base polynomials, then the c * e derivatives
+static bool pack_lens_table(const lentil_lens_table *t, std::vector<DevTerm> &terms, DevLens &h) {
+  bool ok = true;
+  for (int i = 0; i < 5; ++i) ok &= pack_terms(t, t->out[i], -1, terms, h.first[P_OUT_X + i], h.count[P_OUT_X + i]);
+  for (int i = 0; i < 4; ++i) ok &= pack_terms(t, t->ap[i], -1, terms, h.first[P_AP_X + i], h.count[P_AP_X + i]);
+  for (int i = 0; i < 2; ++i)
+    for (int j = 0; j < 2; ++j) {
+      ok &= pack_terms(t, t->ap[i], 2 + j, terms, h.first[P_DAP_00 + i * 2 + j], h.count[P_DAP_00 + i * 2 + j]);
+      ok &= pack_terms(t, t->out[2 + i], j, terms, h.first[P_DOUT_00 + i * 2 + j], h.count[P_DOUT_00 + i * 2 + j]);
+    }
+  for (int i = 0; i < 2; ++i)       // behind everything the draw kernels use
+    for (int j = 0; j < 2; ++j)
+      ok &= pack_terms(t, t->ap[i], j, terms, h.first[P_DAPPOS_00 + i * 2 + j], h.count[P_DAPPOS_00 + i * 2 + j]);
+  return ok;
 }
 
 LENTIL_API int lentil_hip_set_lens(lentil_hip_ctx *ctx, const lentil_lens_table *t) {
@@ -1002,17 +1030,7 @@ LENTIL_API int lentil_hip_set_lens(lentil_hip_ctx *ctx, const lentil_lens_table 
   ctx->park_dry_seen = false; ctx->parked_frac = 0.0; ctx->mean_iters = 0.0;      // what the passes learnt about the previous lens
   std::vector<DevTerm> terms;
   DevLens h{};
-  bool ok = true;
-  for (int i = 0; i < 5; ++i) ok &= pack_terms(t, t->out[i], -1, terms, h.first[P_OUT_X + i], h.count[P_OUT_X + i]);
-  for (int i = 0; i < 4; ++i) ok &= pack_terms(t, t->ap[i], -1, terms, h.first[P_AP_X + i], h.count[P_AP_X + i]);
-  for (int i = 0; i < 2; ++i)
-    for (int j = 0; j < 2; ++j) {
-      ok &= pack_terms(t, t->ap[i], 2 + j, terms, h.first[P_DAP_00 + i * 2 + j], h.count[P_DAP_00 + i * 2 + j]);
-      ok &= pack_terms(t, t->out[2 + i], j, terms, h.first[P_DOUT_00 + i * 2 + j], h.count[P_DOUT_00 + i * 2 + j]);
-    }
-  for (int i = 0; i < 2; ++i)       // behind everything the draw kernels use
-    for (int j = 0; j < 2; ++j)
-      ok &= pack_terms(t, t->ap[i], j, terms, h.first[P_DAPPOS_00 + i * 2 + j], h.count[P_DAPPOS_00 + i * 2 + j]);
+  const bool ok = pack_lens_table(t, terms, h);
   if (!ok) return fail(ctx, LENTIL_ERR_UNSUPPORTED, "lens table exponent > 15");
   if (terms.size() > (size_t)kMaxTerms)
     return fail(ctx, LENTIL_ERR_UNSUPPORTED, "lens table has too many terms for the LDS staging area");
@@ -1102,7 +1120,7 @@ LENTIL_API int lentil_hip_debug_lens_jit_source(lentil_hip_ctx *ctx, char *buf, 
 }
 
 // Context-free (no GPU needed: hiprtc cross-compiles): the table packed as lentil_hip_set_lens packs it, the lens code emitted,
-// and -- compile != 0 -- the four solve kernels compiled.  The emitted source goes to `source` (capacity bytes, NUL-terminated,
+// and -- compile != 0 -- the four solve kernels and the camera-rays kernel compiled.  The emitted source goes to `source` (capacity bytes, NUL-terminated,
 // truncated if longer; *source_length its full length), the compiler's log likewise.  LENTIL_OK, LENTIL_ERR_UNSUPPORTED for a
 // table the library cannot hold, LENTIL_ERR_HIP when the compilation fails.
 LENTIL_API int lentil_hip_debug_lens_jit_compile(const lentil_lens_table *t, int compile, char *source, uint64_t source_capacity,
@@ -1111,14 +1129,7 @@ LENTIL_API int lentil_hip_debug_lens_jit_compile(const lentil_lens_table *t, int
   if (!t || !t->terms) return LENTIL_ERR_INVALID;
   std::vector<DevTerm> terms;
   DevLens h{};
-  bool ok = true;
-  for (int i = 0; i < 5; ++i) ok &= pack_terms(t, t->out[i], -1, terms, h.first[P_OUT_X + i], h.count[P_OUT_X + i]);
-  for (int i = 0; i < 4; ++i) ok &= pack_terms(t, t->ap[i], -1, terms, h.first[P_AP_X + i], h.count[P_AP_X + i]);
-  for (int i = 0; i < 2; ++i)
-    for (int j = 0; j < 2; ++j) {
-      ok &= pack_terms(t, t->ap[i], 2 + j, terms, h.first[P_DAP_00 + i * 2 + j], h.count[P_DAP_00 + i * 2 + j]);
-      ok &= pack_terms(t, t->out[2 + i], j, terms, h.first[P_DOUT_00 + i * 2 + j], h.count[P_DOUT_00 + i * 2 + j]);
-    }
+  const bool ok = pack_lens_table(t, terms, h);
   if (!ok || terms.size() > (size_t)kMaxTerms) return LENTIL_ERR_UNSUPPORTED;
   const std::string src = lentil_jit::lens_jit_emit(h, terms, 0ull);
   auto put = [](const std::string &text, char *buf, uint64_t cap, uint64_t *len) {
@@ -1143,7 +1154,7 @@ LENTIL_API int lentil_hip_debug_lens_jit_compile(const lentil_lens_table *t, int
 LENTIL_API int lentil_hip_set_lens_mode(lentil_hip_ctx *ctx, int mode) {
   CHECK_CTX(ctx);
   if (mode != 0 && mode != 1) return fail(ctx, LENTIL_ERR_INVALID, "lens mode must be 0 (auto) or 1 (tables)");
-  ctx->use_generated = (mode == 0);
+  ctx->use_generated = (mode == 0);       // (the pass's solve kernels, lentil_hip_camera_rays and the focus search all ask it)
   return LENTIL_OK;
 }
 
@@ -4703,7 +4714,17 @@ static int run_focus(lentil_hip_ctx *ctx, const double *shift, uint32_t n, doubl
   if (out && (rc = dev_alloc(ctx, (uint64_t)n * 5, &d_out, tf.v))) return rc;
   if ((rc = dev_alloc(ctx, 2, &d_best, tf.v))) return rc;
   f.shift = d_shift; f.miss = d_miss; f.sensor = d_sensor; f.out = d_out; f.best = d_best;
-  hipLaunchKernelGGL(focus_miss_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, f);
+  // a compiled-in lens runs its straight-line code; a run-time lens keeps the interpreter (the search runs at set_lens time,
+  // before a compilation can have finished)
+  bool launched = false;
+#define LENTIL_LAUNCH_GEN(NAME)                                                                              \
+  if (!launched && ctx->use_generated && ctx->lens_hash == gen::Lens_##NAME::kTableHash) {                    \
+    hipLaunchKernelGGL((focus_miss_kernel<GenLens<gen::Lens_##NAME>, false>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, f); \
+    launched = true;                                                                                         \
+  }
+  LENTIL_GENERATED_LENSES(LENTIL_LAUNCH_GEN)
+#undef LENTIL_LAUNCH_GEN
+  if (!launched) hipLaunchKernelGGL((focus_miss_kernel<LdsLens, true>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, f);
   HIP_TRY(ctx, hipGetLastError());
   hipLaunchKernelGGL(focus_argmin_kernel, dim3(1), dim3(1024), 0, ctx->stream, f);
   HIP_TRY(ctx, hipGetLastError());
@@ -4827,13 +4848,53 @@ LENTIL_API int lentil_hip_camera_rays(lentil_hip_ctx *ctx, const lentil_camera_r
     a.in = d_in; a.out = d_out; a.tries = d_tries;
   }
   const dim3 grid((unsigned)((n + kRayBlock - 1) / kRayBlock));
-  if (po) hipLaunchKernelGGL(camera_rays_kernel<true>, grid, dim3(kRayBlock), 0, ctx->stream, a);
-  else hipLaunchKernelGGL(camera_rays_kernel<false>, grid, dim3(kRayBlock), 0, ctx->stream, a);
+  int path = 0;
+  if (po) {
+    const bool compiled = ctx->use_generated && ctx->rays_compiled;
+#define LENTIL_LAUNCH_GEN(NAME)                                                                              \
+    if (!path && compiled && ctx->lens_hash == gen::Lens_##NAME::kTableHash) {                               \
+      hipLaunchKernelGGL((camera_rays_kernel<GenLens<gen::Lens_##NAME>, false, true>), grid, dim3(kRayBlock), 0, ctx->stream, a); \
+      path = 2;                                                                                              \
+    }
+    LENTIL_GENERATED_LENSES(LENTIL_LAUNCH_GEN)
+#undef LENTIL_LAUNCH_GEN
+    if (!path && compiled) {
+      // the kernel specialised for this table at run time (lentil_lens_jit.h), once its code object is there
+      if (hipFunction_t fn = jit_rays_function(ctx)) {
+        CameraRayArgs args = a;
+        void *params[] = {&args};
+        const hipError_t le = hipModuleLaunchKernel(fn, grid.x, 1, 1, kRayBlock, 1, 1, 0, ctx->stream, params, nullptr);
+        if (le == hipSuccess) {
+          path = 3;
+        } else {
+          // a code object whose kernel does not launch is given up for this context: lentil_hip_lens_jit_status reports -1
+          // from here on, and the interpreter serves the lens without trying the launch again on every call
+          (void)hipGetLastError();
+          ctx->jit_load_failed = true;
+          if (getenv("LENTIL_STREAM_DEBUG")) fprintf(stderr, "[lens jit] the run-time camera-rays kernel did not launch (%s): the table interpreter serves the lens\n", hipGetErrorString(le));
+        }
+      }
+    }
+    if (!path) {
+      hipLaunchKernelGGL((camera_rays_kernel<LdsLens, true, true>), grid, dim3(kRayBlock), 0, ctx->stream, a);
+      path = 1;
+    }
+  } else {
+    hipLaunchKernelGGL((camera_rays_kernel<LdsLens, false, false>), grid, dim3(kRayBlock), 0, ctx->stream, a);
+  }
+  ctx->rays_path = path;
   HIP_TRY(ctx, hipGetLastError());
   if (device) return LENTIL_OK;
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   HIP_TRY(ctx, hipMemcpy(batch->out, d_out, (size_t)n * kRayOutFloats * sizeof(float), hipMemcpyDeviceToHost));
   if (batch->tries) HIP_TRY(ctx, hipMemcpy(batch->tries, d_tries, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return LENTIL_OK;
+}
+
+LENTIL_API int lentil_hip_camera_rays_path(lentil_hip_ctx *ctx, int *path) {
+  CHECK_CTX(ctx);
+  if (!path) return fail(ctx, LENTIL_ERR_INVALID, "path is null");
+  *path = ctx->rays_path;
   return LENTIL_OK;
 }
 

@@ -4769,18 +4769,24 @@ struct FocusArgs {
   double *best;            // [2]: winning shift, its miss (focus_argmin_kernel)
 };
 
+// LensT: LdsLens (kTables: the term table staged into LDS) or GenLens<Gen> of a compiled-in lens (the header alone)
+template <class LensT, bool kTables>
 __global__ __launch_bounds__(256) void focus_miss_kernel(FocusArgs f) {
-  __shared__ DevTerm s_terms[kMaxTerms];
+  __shared__ DevTerm s_terms[kTables ? kMaxTerms : 1];
   __shared__ DevLens s_k;
-  const uint32_t nt = f.lens->n_terms;
-  for (uint32_t i = threadIdx.x; i < nt; i += blockDim.x) s_terms[i] = f.terms[i];
+  if (kTables) {
+    const uint32_t nt = f.lens->n_terms;
+    for (uint32_t i = threadIdx.x; i < nt; i += blockDim.x) s_terms[i] = f.terms[i];
+  }
   if (threadIdx.x == 0) {
     s_k = *f.lens;
     s_k.lambda_pow[0] = 1.0; s_k.lambda_pow[1] = f.lambda;
     for (uint32_t e = 2; e <= kMaxExp; ++e) s_k.lambda_pow[e] = ipow_u(f.lambda, e);     // lens_ipow, like the host
   }
   __syncthreads();
-  const LdsLens L{s_terms, &s_k};
+  LensT L{};
+  if constexpr (kTables) L.terms = s_terms;
+  L.k = &s_k;
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t ii = i < f.n ? i : f.n - 1u;      // whole waves stay converged: table reads go through readfirstlane
   double sensor[4], out[4], T;

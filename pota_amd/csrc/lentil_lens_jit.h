@@ -11,7 +11,8 @@
 //                     integer powers shared between terms, term = c * f(x) * f(y) * f(dx) * f(dy) * lambda^e left to right,
 //                     terms summed in table order: the interpreter's and the oracle's operations in their order;
 //   hiprtc            (bound at run time: dlopen, like RCCL) compiles solve_po_kernel<GenLens<Lens_rt>, ...> -- the four
-//                     instances a pass can launch -- from the library's own kernel sources, which ride inside the .so
+//                     instances a pass can launch -- and camera_rays_kernel<GenLens<Lens_rt>, ...> (the lens's forward
+//                     members eval_fw_newton / eval_out) from the library's own kernel sources, which ride inside the .so
 //                     (generated/embedded_sources.inc, written by __graft_entry__.build());
 //   a cache           of code objects on disk, in a directory private to the caller, keyed by the table's hash and the hash of
 //                     the sources, the flags, the compiler's version and the device's architecture; every file checksummed;
@@ -205,6 +206,18 @@ static inline std::string lens_jit_emit(const lentil::DevLens &h, const std::vec
   PlainEmitter et(coef);
   et.poly("const double t", P(P_OUT_T), N(P_OUT_T));
   const std::vector<std::string> tl = et.lines();
+  // the forward members (lens_pt_sample_aperture's Newton step, lens_evaluate): the same emitters, their coefficients behind
+  PrefetchEmitter ef(coef);
+  ef.poly("pred_ap[0]", P(P_AP_X), N(P_AP_X));
+  ef.poly("pred_ap[1]", P(P_AP_Y), N(P_AP_Y));
+  ef.poly("pred_dir[0]", P(P_AP_DX), N(P_AP_DX));
+  ef.poly("pred_dir[1]", P(P_AP_DY), N(P_AP_DY));
+  { const int ids[4] = {P_DAP_00, P_DAP_01, P_DAP_10, P_DAP_11}; for (int i = 0; i < 4; ++i) ef.poly("Jap[" + std::to_string(i) + "]", P(ids[i]), N(ids[i])); }
+  { const int ids[4] = {P_DAPPOS_00, P_DAPPOS_01, P_DAPPOS_10, P_DAPPOS_11}; for (int i = 0; i < 4; ++i) ef.poly("Jappos[" + std::to_string(i) + "]", P(ids[i]), N(ids[i])); }
+  const std::vector<std::string> fw = ef.lines();
+  PrefetchEmitter eo(coef);
+  { const int ids[4] = {P_OUT_X, P_OUT_Y, P_OUT_DX, P_OUT_DY}; for (int i = 0; i < 4; ++i) eo.poly("out[" + std::to_string(i) + "]", P(ids[i]), N(ids[i])); }
+  const std::vector<std::string> ol = eo.lines();
   std::string s;
   char hb[32];
   snprintf(hb, sizeof hb, "0x%016llx", table_hash);
@@ -231,7 +244,17 @@ static inline std::string lens_jit_emit(const lentil::DevLens &h, const std::vec
   s += "  }\n  static __device__ __forceinline__ double transmittance(const double v[4], const double *lp) {\n"
        "  const double x = v[0], y = v[1], dx = v[2], dy = v[3];\n  LENTIL_COEF_PTR(C, kCoef_rt);\n";
   for (const std::string &l : tl) s += l + "\n";
-  s += "  return t;\n  }\n};\n}}  // namespace lentil::gen\n";
+  s += "  return t;\n  }\n"
+       "  // one Newton step of lens_pt_sample_aperture at v: the aperture point and direction, d ap / d (dx, dy), d ap / d (x, y)\n"
+       "  static __device__ __forceinline__ void eval_fw_newton(const double v[4], const double *lp, double pred_ap[2],\n"
+       "                                                        double pred_dir[2], double Jap[4], double Jappos[4]) {\n"
+       "  const double x = v[0], y = v[1], dx = v[2], dy = v[3];\n  LENTIL_COEF_PTR(C, kCoef_rt);\n";
+  for (const std::string &l : fw) s += l + "\n";
+  s += "  }\n  // lens_evaluate's four outer-pupil polynomials at v\n"
+       "  static __device__ __forceinline__ void eval_out(const double v[4], const double *lp, double out[4]) {\n"
+       "  const double x = v[0], y = v[1], dx = v[2], dy = v[3];\n  LENTIL_COEF_PTR(C, kCoef_rt);\n";
+  for (const std::string &l : ol) s += l + "\n";
+  s += "  }\n};\n}}  // namespace lentil::gen\n";
   return s;
 }
 
@@ -284,9 +307,13 @@ static const char *const kInstance[2][2] = {
     {"solve_po_kernel<lentil::GenLens<lentil::gen::Lens_rt>, false, false, false>", "solve_po_kernel<lentil::GenLens<lentil::gen::Lens_rt>, false, false, true>"},
     {"solve_po_kernel<lentil::GenLens<lentil::gen::Lens_rt>, false, true, false>", "solve_po_kernel<lentil::GenLens<lentil::gen::Lens_rt>, false, true, true>"}};
 
+// ... and the camera-rays kernel of the lens (lentil_camera_rays.h)
+static const char *const kRaysInstance = "camera_rays_kernel<lentil::GenLens<lentil::gen::Lens_rt>, false, true>";
+
 struct CodeObject {
   std::vector<char> code;
   std::string name[2][2];          // lowered (mangled) kernel names
+  std::string rays_name;
 };
 
 struct Source { const char *name; const char *text; };
@@ -320,13 +347,15 @@ static inline bool compile(const std::vector<Source> &sources, const std::string
   names.push_back("stdint.h"); bodies.push_back(kStdint);
   names.push_back("stddef.h"); bodies.push_back(kEmpty);
   names.push_back("hip/hip_runtime.h"); bodies.push_back(kEmpty);
-  std::string tu = "#include \"lentil_kernels.h\"\n" + checks;
+  std::string tu = "#include \"lentil_kernels.h\"\n#include \"lentil_camera_rays.h\"\n" + checks;
   for (int c = 0; c < 2; ++c)
     for (int s = 0; s < 2; ++s) tu += std::string("template __global__ void ") + kInstance[c][s] + "(DrawArgs);\n";
+  tu += std::string("template __global__ void ") + kRaysInstance + "(CameraRayArgs);\n";
   void *prog = nullptr;
   if (r.CreateProgram(&prog, tu.c_str(), "lentil_lens_rt.hip", (int)names.size(), bodies.data(), names.data()) != 0) { log = "hiprtcCreateProgram failed"; return false; }
   for (int c = 0; c < 2; ++c)
     for (int s = 0; s < 2; ++s) (void)r.AddNameExpression(prog, kInstance[c][s]);
+  (void)r.AddNameExpression(prog, kRaysInstance);
   std::vector<const char *> opts;
   for (const std::string &f : flags) opts.push_back(f.c_str());
   const int rc = r.CompileProgram(prog, (int)opts.size(), opts.data());
@@ -340,6 +369,11 @@ static inline bool compile(const std::vector<Source> &sources, const std::string
         ok = r.GetLoweredName(prog, kInstance[c][s], &low) == 0 && low;
         if (ok) out.name[c][s] = low;
       }
+    if (ok) {
+      const char *low = nullptr;
+      ok = r.GetLoweredName(prog, kRaysInstance, &low) == 0 && low;
+      if (ok) out.rays_name = low;
+    }
     size_t cs = 0;
     ok = ok && r.GetCodeSize(prog, &cs) == 0 && cs > 0;
     if (ok) { out.code.resize(cs); ok = r.GetCode(prog, out.code.data()) == 0; }
@@ -349,7 +383,7 @@ static inline bool compile(const std::vector<Source> &sources, const std::string
   return ok;
 }
 
-// ---- the cache on disk: <dir>/<table hash>_<source hash>.lco = "LCO2", u64 checksum, 4 x (u32 length, name), u64 size, code ------
+// ---- the cache on disk: <dir>/<table hash>_<source hash>.lco = "LCO3", u64 checksum, 5 x (u32 length, name), u64 size, code ------
 // The directory is the caller's own and nobody else's: LENTIL_JIT_CACHE, $XDG_CACHE_HOME/lentil_hip, $HOME/.cache/lentil_hip, or
 // /tmp/lentil_hip_<uid>; created 0700, and used only if it is a directory (not a link) that the caller owns and that neither its
 // group nor others can write to.  Without such a directory there is no disk cache (every process compiles for itself).  A file is
@@ -380,9 +414,10 @@ static inline std::string cache_file(const std::string &dir, uint64_t table_hash
   return dir + b;
 }
 static inline uint64_t code_checksum(const CodeObject &co) {
-  uint64_t h = fnv("lco2", 4);
+  uint64_t h = fnv("lco3", 4);
   for (int c = 0; c < 2; ++c)
     for (int s = 0; s < 2; ++s) h = fnv(co.name[c][s].data(), co.name[c][s].size(), h);
+  h = fnv(co.rays_name.data(), co.rays_name.size(), h);
   return fnv(co.code.data(), co.code.size(), h);
 }
 static inline bool cache_load(const std::string &path, CodeObject &out) {
@@ -396,7 +431,7 @@ static inline bool cache_load(const std::string &path, CodeObject &out) {
   bool ok = false;
   char magic[4];
   uint64_t sum = 0;
-  if (fread(magic, 1, 4, f) == 4 && memcmp(magic, "LCO2", 4) == 0 && fread(&sum, 8, 1, f) == 1) {
+  if (fread(magic, 1, 4, f) == 4 && memcmp(magic, "LCO3", 4) == 0 && fread(&sum, 8, 1, f) == 1) {
     ok = true;
     for (int c = 0; c < 2 && ok; ++c)
       for (int s = 0; s < 2 && ok; ++s) {
@@ -404,13 +439,18 @@ static inline bool cache_load(const std::string &path, CodeObject &out) {
         ok = fread(&n, 4, 1, f) == 1 && n > 0 && n < 4096;
         if (ok) { out.name[c][s].resize(n); ok = fread(&out.name[c][s][0], 1, n, f) == n; }
       }
+    if (ok) {
+      uint32_t n = 0;
+      ok = fread(&n, 4, 1, f) == 1 && n > 0 && n < 4096;
+      if (ok) { out.rays_name.resize(n); ok = fread(&out.rays_name[0], 1, n, f) == n; }
+    }
     uint64_t cs = 0;
     ok = ok && fread(&cs, 8, 1, f) == 1 && cs > 0 && cs < (1ull << 30);
     if (ok) { out.code.resize(cs); ok = fread(out.code.data(), 1, cs, f) == cs; }
     ok = ok && code_checksum(out) == sum;
   }
   fclose(f);
-  if (!ok) { out.code.clear(); for (int c = 0; c < 2; ++c) for (int s = 0; s < 2; ++s) out.name[c][s].clear(); }
+  if (!ok) { out.code.clear(); out.rays_name.clear(); for (int c = 0; c < 2; ++c) for (int s = 0; s < 2; ++s) out.name[c][s].clear(); }
   return ok;
 }
 static inline void cache_store(const std::string &path, const CodeObject &co) {
@@ -421,12 +461,16 @@ static inline void cache_store(const std::string &path, const CodeObject &co) {
   FILE *f = fdopen(fd, "wb");
   if (!f) { close(fd); (void)remove(tmp.c_str()); return; }
   const uint64_t sum = code_checksum(co);
-  bool ok = fwrite("LCO2", 1, 4, f) == 4 && fwrite(&sum, 8, 1, f) == 1;
+  bool ok = fwrite("LCO3", 1, 4, f) == 4 && fwrite(&sum, 8, 1, f) == 1;
   for (int c = 0; c < 2 && ok; ++c)
     for (int s = 0; s < 2 && ok; ++s) {
       const uint32_t n = (uint32_t)co.name[c][s].size();
       ok = fwrite(&n, 4, 1, f) == 1 && fwrite(co.name[c][s].data(), 1, n, f) == n;
     }
+  if (ok) {
+    const uint32_t n = (uint32_t)co.rays_name.size();
+    ok = fwrite(&n, 4, 1, f) == 1 && fwrite(co.rays_name.data(), 1, n, f) == n;
+  }
   const uint64_t cs = co.code.size();
   ok = ok && fwrite(&cs, 8, 1, f) == 1 && fwrite(co.code.data(), 1, cs, f) == cs;
   ok = (fclose(f) == 0) && ok;

@@ -224,6 +224,25 @@ def gen_lens(name, spec):
     em_lines = em.lines() if prefetch else em.lines
     et = Emitter(coef, "C")
     et.poly("const double t", polys["out_t"])
+    # the forward members (lens_pt_sample_aperture's Newton step and lens_evaluate, csrc/lentil_camera_rays.h and the focus
+    # search): the same two emitters, their coefficients behind the backward ones in the same array
+    dappos = [[derive(polys["ap_" + a], j) for j in range(2)] for a in ("x", "y")]
+    ef = PrefetchEmitter(coef) if prefetch else Emitter(coef, "C")
+    ef.poly("pred_ap[0]", polys["ap_x"])
+    ef.poly("pred_ap[1]", polys["ap_y"])
+    ef.poly("pred_dir[0]", polys["ap_dx"])
+    ef.poly("pred_dir[1]", polys["ap_dy"])
+    for i in range(2):
+        for j in range(2):
+            ef.poly("Jap[%d]" % (i * 2 + j), dap[i][j])
+    for i in range(2):
+        for j in range(2):
+            ef.poly("Jappos[%d]" % (i * 2 + j), dappos[i][j])
+    ef_lines = ef.lines() if prefetch else ef.lines
+    eo = PrefetchEmitter(coef) if prefetch else Emitter(coef, "C")
+    for i, n in enumerate(["out_x", "out_y", "out_dx", "out_dy"]):
+        eo.poly("out[%d]" % i, polys[n])
+    eo_lines = eo.lines() if prefetch else eo.lines
     n_terms = sum(len(polys[n]) for n in OUT_NAMES + AP_NAMES)
     h = table_hash(spec)
     src = []
@@ -269,6 +288,19 @@ def gen_lens(name, spec):
     src.append("  LENTIL_COEF_PTR(C, %s);" % cname)
     src.extend(et.lines)
     src.append("  return t;")
+    src.append("  }")
+    src.append("  // one Newton step of lens_pt_sample_aperture at v: the aperture point and direction, d ap / d (dx, dy), d ap / d (x, y)")
+    src.append("  static __device__ __forceinline__ void eval_fw_newton(const double v[4], const double *lp, double pred_ap[2],")
+    src.append("                                                        double pred_dir[2], double Jap[4], double Jappos[4]) {")
+    src.append("  const double x = v[0], y = v[1], dx = v[2], dy = v[3];")
+    src.append("  LENTIL_COEF_PTR(C, %s);" % cname)
+    src.extend(ef_lines)
+    src.append("  }")
+    src.append("  // lens_evaluate's four outer-pupil polynomials at v")
+    src.append("  static __device__ __forceinline__ void eval_out(const double v[4], const double *lp, double out[4]) {")
+    src.append("  const double x = v[0], y = v[1], dx = v[2], dy = v[3];")
+    src.append("  LENTIL_COEF_PTR(C, %s);" % cname)
+    src.extend(eo_lines)
     src.append("  }")
     src.append("};")
     src.append("}}  // namespace lentil::gen")

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Registers / spills / LDS / occupancy of every kernel in liblentil_hip.so, from hipcc's
+"""Registers / spills (SGPR spills go to VGPR lanes, VGPR spills to scratch) / scratch bytes per lane / LDS / occupancy of every kernel in liblentil_hip.so, from hipcc's
 -Rpass-analysis=kernel-resource-usage remarks (compiles to a scratch file, no GPU needed)."""
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,12 +24,13 @@ def main():
         m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[a-z/A-Z]+\])?: (\d+) \[-Rpass", line)
         if m and cur is not None:
             cur[m.group(1).strip()] = int(m.group(2))
-    print("%-72s %5s %5s %6s %6s %7s %4s" % ("kernel", "VGPR", "AGPR", "SGPR", "spillV", "LDS", "occ"))
+    print("%-72s %5s %5s %6s %6s %6s %7s %7s %4s" % ("kernel", "VGPR", "AGPR", "SGPR", "spillS", "spillV", "scratch", "LDS", "occ"))
     for r in rows:
         n = re.sub(r"\(.*", "", r["name"])[:72]
-        print("%-72s %5d %5d %6d %6d %7d %4d" % (n, r.get("VGPRs", -1), r.get("AGPRs", -1), r.get("TotalSGPRs", -1),
-                                                r.get("VGPRs Spill", r.get("VGPR Spill", -1)), r.get("LDS Size", -1),
-                                                r.get("Occupancy", -1)))
+        print("%-72s %5d %5d %6d %6d %6d %7d %7d %4d" % (n, r.get("VGPRs", -1), r.get("AGPRs", -1), r.get("TotalSGPRs", -1),
+                                                          r.get("SGPRs Spill", r.get("SGPR Spill", -1)),
+                                                          r.get("VGPRs Spill", r.get("VGPR Spill", -1)), r.get("ScratchSize", -1),
+                                                          r.get("LDS Size", -1), r.get("Occupancy", -1)))
 
 if __name__ == "__main__":
     main()
