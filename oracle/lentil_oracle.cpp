@@ -536,6 +536,7 @@ struct arrayCompare {                                           /* src/imageboke
 /* bokehProbability, src/imagebokeh.h:143-338; pixelData = x*y*nchannels floats */
 ORC_API OrcBokeh *orc_bokeh_create(const float *pixelData, int x, int y, int nchannels) {
   if (!(x * y * nchannels > 0 && nchannels >= 3) || x != y) return nullptr;
+  if (!pixelData || x <= 0) return nullptr;                     /* (a product of two negative sizes is positive too) */
   OrcBokeh *B = new OrcBokeh();
   B->x = x; B->y = y;
   const int npixels = x * y;

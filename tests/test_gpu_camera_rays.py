@@ -26,7 +26,11 @@ LAM = float(np.float32(550.0)) * 0.001
 TL_MATH_ULPS = 0
 
 
-def _bokeh_tables(orc):
+def _bokeh_tables(orc, case=None):
+    """(tables, the oracle's OrcBokeh): the reference's example kernel, or a case of tests/bokeh_tables.py"""
+    if case is not None:
+        import bokeh_tables
+        return bokeh_tables.tables(case), bokeh_tables.oracle_bokeh(orc, case)
     tex = np.load(os.path.join(common.ROOT, "tests", "golden", "example_bokeh_kernel_u8.npy")).astype(np.float32) / np.float32(255)
     tables = bokeh.build_tables(tex)
     bt = _abi.BokehTable()
@@ -148,6 +152,30 @@ def test_po_rays_bitwise(orc, gpu_ctx_factory, lens_name, setup):
     assert bad.size == 0, (bad[:8], got[bad[:2]], want[bad[:2]])
 
 
+def test_po_rays_with_a_crafted_2049_table(orc, gpu_ctx_factory):
+    """tests/bokeh_tables.py's crafted 2049 x 2049 table: a quarter of the rays clamp the row, half of the others the column,
+    and the clamped entries are not row / column 0.  (test_po_rays_bitwise's comparison.)"""
+    p, model, table, keep = common.po_setup(W, H, bokeh_enable_image=1)
+    tables, ob = _bokeh_tables(orc, "clamp2049")
+    plain_tables, plain = _bokeh_tables(orc)
+    lens = orc.orc_lens_create(C.byref(table))
+    try:
+        inp = _inputs(N, 9, 1.1, 0.7)
+        want, want_tries = oracle_rays(orc, p, lens, ob, inp, seed=0x1234)
+        other, _ = oracle_rays(orc, p, lens, plain, inp[:64], seed=0x1234, differentials=False)
+        assert not _same_bits(want[:64, 0:9], other[:, 0:9])                 # the table decides the rays
+        assert int((want_tries > 0).sum()) > 0, "no ray of this case retries"
+        ctx = _ctx(gpu_ctx_factory, p, table, tables)
+        got, got_tries = ctx.camera_rays(inp, lam=LAM, seed=0x1234, want_tries=True)
+    finally:
+        orc.orc_lens_destroy(lens)
+        orc.orc_bokeh_destroy(ob)
+        orc.orc_bokeh_destroy(plain)
+    assert np.array_equal(got_tries, want_tries)
+    bad = np.nonzero((got.view(np.uint32) != want.view(np.uint32)).any(1))[0]
+    assert bad.size == 0, (bad[:8], got[bad[:2]], want[bad[:2]])
+
+
 # ---- thin lens -------------------------------------------------------------------------------------------------------------------
 TL_SETUPS = {
     # name: (parameters, vignetting case, a coma or optical-vignetting case: the only ones TL_MATH_ULPS may ever loosen)
@@ -186,6 +214,23 @@ def test_thinlens_rays(orc, gpu_ctx_factory, setup):
     assert np.array_equal(got_tries, want_tries)
     assert _same_bits(got[:, 0:3], want[:, 0:3]) and _same_bits(got[:, 6:15], want[:, 6:15])     # origin, weight, dOdx, dOdy: no libm
     assert ulps <= (TL_MATH_ULPS if coma_or_ov else 0)
+
+
+def test_thinlens_rays_with_a_crafted_2049_table(orc, gpu_ctx_factory):
+    """(test_thinlens_rays' "image_ov" with tests/bokeh_tables.py's crafted 2049 x 2049 table, and its comparison)"""
+    p = common.tl_setup(W, H, bokeh_enable_image=1, optical_vignetting_distance=2.0)
+    tables, ob = _bokeh_tables(orc, "clamp2049")
+    try:
+        inp = _inputs(N, 10, 1.0, 0.6)
+        want, want_tries = oracle_rays(orc, p, None, ob, inp, seed=77, exposure=0.5)
+        assert int((want_tries > 0).sum()) > 0, "no ray of this case retries"
+        ctx = _ctx(gpu_ctx_factory, p, None, tables)
+        got, got_tries = ctx.camera_rays(inp, seed=77, exposure=0.5, want_tries=True)
+    finally:
+        orc.orc_bokeh_destroy(ob)
+    assert np.array_equal(got_tries, want_tries)
+    assert _same_bits(got[:, 0:3], want[:, 0:3]) and _same_bits(got[:, 6:15], want[:, 6:15])     # origin, weight, dOdx, dOdy: no libm
+    assert _ulps(got, want) <= TL_MATH_ULPS
 
 
 # ---- splitting, forms, flags ------------------------------------------------------------------------------------------------------

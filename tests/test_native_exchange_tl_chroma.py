@@ -54,24 +54,24 @@ def _log_of(ctx, to_gid):
     return log
 
 
-def _whole(p, cols, passes=PASSES):
+def _whole(p, cols, passes=PASSES, bokeh=None):
     """one context over the whole frame: its logs and generator states after every pass; the context holds the last frame"""
     visits, keep = capi.make_visits(cols, visits_per_pixel=M, pixels_per_row=W)
     ctx = capi.Context(0)
     logs, states = [], []
     for _ in range(passes):
-        gpu_run(ctx, p, None, visits, n_aovs=3, kinds=KINDS)
+        gpu_run(ctx, p, None, visits, n_aovs=3, kinds=KINDS, bokeh_tables=bokeh)
         logs.append(common.sort_log(ctx.draw_log()))
         states.append(ctx.get_xor128_state())
     ctx.P = p
     return ctx, logs, states, keep
 
 
-def _context(p, cols, log=True, **layout):
+def _context(p, cols, log=True, bokeh=None, **layout):
     v, kv = capi.make_visits(cols, visits_per_pixel=M, pixels_per_row=W, **layout)
     ctx = capi.Context(0)
     ctx.set_params(p)
-    ctx.set_bokeh(None)
+    ctx.set_bokeh(bokeh)
     ctx.alloc_frame(3, KINDS)
     if log:
         ctx.set_draw_log(1 << 22)
@@ -84,11 +84,11 @@ def _log_for(log, rank):
     return log[rank] if isinstance(log, (list, tuple)) else log
 
 
-def _band_ranks(p, cols, world, bounds, log=True):
+def _band_ranks(p, cols, world, bounds, log=True, bokeh=None):
     ctxs, keep, bands, gid = [], [], [], []
     for rank in range(world):
         b_lo, b_hi = distributed.band_of(rank, world, H, p.yres, bounds)
-        ctx, k = _context(p, _slice(cols, slice(b_lo * W * M, min(b_hi, H) * W * M)), _log_for(log, rank), pixel_y0=b_lo)
+        ctx, k = _context(p, _slice(cols, slice(b_lo * W * M, min(b_hi, H) * W * M)), _log_for(log, rank), bokeh=bokeh, pixel_y0=b_lo)
         ctxs.append(ctx); keep.append(k); bands.append((b_lo, b_hi))
         gid.append(lambda v, b=b_lo: v + b * W * M)
     return ctxs, keep, bands, gid
@@ -228,6 +228,49 @@ def test_bands_match_the_oracle(orc, fake_rccl):
         assert out[r][0][1] == list(st)
         ctxs[r].close()
     ref.close()
+
+
+def test_bands_with_an_aperture_image_match_the_oracle(orc, fake_rccl):
+    """bokeh_enable_image on two uneven bands, the table one whose clamps bite (tests/bokeh_tables.py: cdfRow ends at 0.75, every
+    cdfColumn at 0.5): the per-rank kernels form every attempt's aperture point from the image.  The merged accepted-draw
+    lists and the generator state are the single-threaded oracle's, a whole-frame context is the oracle's within 1e-5, and
+    every band's rows are that context's."""
+    import bokeh_tables
+    from test_gpu_parity import check_frame, check_logs
+    p = _params(0, chroma=0.5)
+    p.bokeh_enable_image = 1
+    tables = bokeh_tables.tables("clamp16")
+    ob = bokeh_tables.oracle_bokeh(orc, "clamp16")
+    cols = _columns(p)
+    visits, vk = capi.make_visits(cols, visits_per_pixel=M, pixels_per_row=W)
+    ref = oracle_lib.Frame(orc, p, n_aovs=3, kinds=KINDS, keep_log=True)
+    plain = oracle_lib.Frame(orc, _params(0, chroma=0.5), n_aovs=3, kinds=KINDS, keep_log=True)
+    try:
+        ref.run(None, ob, visits)
+        plain.run(None, None, visits)
+        assert ref.counters().accepted_draws > 5000
+        assert not np.array_equal(common.sort_log(ref.log()), common.sort_log(plain.log()))       # the image changes the draws
+        st = (C.c_uint32 * 4)()
+        orc.orc_frame_get_xor128(ref.h, st)
+        bounds = [0, 23, 64]
+        ctxs, ck, bands, gid = _band_ranks(p, cols, 2, bounds, bokeh=tables)
+        out = _run_native(ctxs, 2, lambda ctx: distributed.frame_step_bands_native(ctx, H, bounds), gid, passes=1)
+        merged = common.sort_log(np.concatenate([out[r][0][0] for r in range(2)]))
+        assert np.array_equal(merged, common.sort_log(ref.log()))
+        assert set(np.unique(merged[:, 1] >> 30)) == {0, 1, 2}
+        whole, wl, ws, wk = _whole(p, cols, passes=1, bokeh=tables)
+        check_logs(whole, ref)
+        check_frame(whole, ref, n_aovs=3, kinds=KINDS)
+        assert ws[0] == list(st)
+        for r in range(2):
+            assert out[r][0][1] == list(st)
+            _compare_with_whole(ctxs[r], whole, KINDS, rows=bands[r])
+            ctxs[r].close()
+        whole.close()
+    finally:
+        ref.close()
+        plain.close()
+        orc.orc_bokeh_destroy(ob)
 
 
 @pytest.mark.parametrize("partition", ["bands", "interleaved"])
