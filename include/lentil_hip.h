@@ -734,6 +734,11 @@ int lentil_hip_test_xor128_jump(const uint32_t in[4], uint64_t k, uint32_t out[4
  * intervals on which the circle of confusion is certainly below 0.4, out[4..5] / out[6..7] those outside of which it is
  * certainly not (an interval with lower > upper end is empty).  In between the kernel evaluates the function. */
 int lentil_hip_debug_scan_bands(const lentil_params *params, float out[8]);
+/* Test hook, needs no GPU.  scan_dma2_kernel runs a tile with only the depth column in its ring wherever the depth decides
+ * (the lean body) or with all three decision columns (the full body): out[0] the lean ring's slots, out[1] the open groups
+ * that make a tile busy (a wave goes to the full body after a busy tile), out[2] the tiles in a row that are not busy before
+ * it returns to the lean body. */
+int lentil_hip_debug_scan_lean_counts(uint32_t out[3]);
 /* Test hook.  The scan kernels a pass may start with; which one runs follows from the stream's shape (visits per pixel, extra
  * AOV columns and their filters, whether the last pixel is whole, pixels per row) and from the LDS the resident solve blocks
  * of a streamed pass leave. */

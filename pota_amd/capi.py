@@ -26,7 +26,7 @@ EXPORTS = [
     "lentil_hip_batch_model_stats", "lentil_hip_process_stats", "lentil_hip_process_stall_notes", "lentil_hip_set_async", "lentil_hip_pass_totals", "lentil_hip_set_occlusion_probe", "lentil_hip_probe_stats", "lentil_hip_debug_batch_estimate", "lentil_hip_box_probe",
     "lentil_hip_lens_jit_status", "lentil_hip_lens_jit_wait", "lentil_hip_debug_lens_jit_source", "lentil_hip_debug_lens_jit_compile",
     "lentil_hip_download_draw_log", "lentil_hip_test_lt_sample_aperture",
-    "lentil_hip_test_trace_bw_po", "lentil_hip_test_aperture_sample", "lentil_hip_debug_scan_bands", "lentil_hip_debug_last_scan",
+    "lentil_hip_test_trace_bw_po", "lentil_hip_test_aperture_sample", "lentil_hip_debug_scan_bands", "lentil_hip_debug_scan_lean_counts", "lentil_hip_debug_last_scan",
     "lentil_hip_lens_is_compiled", "lentil_hip_set_lens_mode",
     "lentil_hip_focus_search", "lentil_hip_test_y0_intersection", "lentil_hip_camera_rays", "lentil_hip_camera_rays_path",
     "lentil_hip_set_xor128_state", "lentil_hip_get_xor128_state", "lentil_hip_tl_chroma_stats", "lentil_hip_test_xor128_jump",

@@ -2071,6 +2071,14 @@ LENTIL_API int lentil_hip_debug_scan_bands(const lentil_params *P, float out[8])
   return LENTIL_OK;
 }
 
+// test hook (no GPU needed): scan_dma2_kernel's lean ring slots, the open groups that make a tile busy, the quiet tiles before
+// a wave returns to the lean body (kLeanRing, kBusyGroups, kQuietTiles)
+LENTIL_API int lentil_hip_debug_scan_lean_counts(uint32_t out[3]) {
+  if (!out) return LENTIL_ERR_INVALID;
+  out[0] = kLeanRing; out[1] = kBusyGroups; out[2] = kQuietTiles;
+  return LENTIL_OK;
+}
+
 // How the bound visit stream is scanned: kernel, tile size, LDS.
 struct ScanPlan {
   ScanArgs sa{};

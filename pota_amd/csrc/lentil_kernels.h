@@ -987,8 +987,33 @@ __global__ __launch_bounds__(256) void scan_dma_kernel(ScanArgs a) {
 //             linear index from a multiply-high instead of a division.
 // Same decisions, same sums bit for bit as scan_dma_kernel (tests: every parity case that runs a beauty-only frame).
 // ---------------------------------------------------------------------------------------
+//   lean       every test but the depth's can only turn a decision OFF, so a group none of whose 64
+//             visits the depth leaves open needs neither volume_ignore nor transmission.  A wave runs its tiles in one of two
+//             bodies.  FULL is the body described above.  LEAN keeps only pos_z in the ring -- the same 6 KiB as D = min(M, 6)
+//             slots of one column -- and a group with an open visit reads its two veto columns straight from global memory
+//             (two untracked loads and a vmcnt(0): one drained pipeline per open group).  A step of the lean steady state
+//             issues TWO loads (pos_z of group G + D, rgba group g of the next tile), so behind the group about to be read
+//             lie the pos_z of G + 1 .. G + D - 1 and D rgba groups: `vmcnt(2 D - 1)`, 11 KiB in flight at M >= 6 where the
+//             full body keeps 5.  A tile is BUSY when kBusyGroups or more of its groups were open; a wave goes to the full
+//             body after a busy tile and back to the lean one after kQuietTiles tiles in a row that were not, draining and
+//             re-priming the ring at that tile boundary.
 __host__ __device__ constexpr uint32_t dma2_wave_f4(uint32_t M) { return 2u * M * 64u + 2u * 192u + 16u; }
+constexpr uint32_t kLeanRing = 6;      // pos_z slots of the lean ring: what the full body's two three-column slots take
+constexpr uint32_t kBusyGroups = 2;    // open groups that make a tile busy (one costs a drain; a switch there and back, two)
+constexpr uint32_t kQuietTiles = 2;    // tiles in a row without that many before a wave returns to the lean body
 LD_DEV float4 lds_read_f4(const float4 *p);       // (below, with the other untracked reads)
+LD_DEV void global_read_2f4_untracked(const float4 *p, const float4 *q, uint32_t lane16, float4 &x, float4 &y);
+
+// s_waitcnt vmcnt(n) for the lean body's counts, n <= 2 * kLeanRing (anything else: vmcnt(0), which waits for more)
+LD_DEV void wait_vmcnt_lean(uint32_t n) {
+#define LENTIL_VMCNT_CASE(N) case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
+  switch (n) {
+    LENTIL_VMCNT_CASE(1) LENTIL_VMCNT_CASE(2) LENTIL_VMCNT_CASE(3) LENTIL_VMCNT_CASE(4) LENTIL_VMCNT_CASE(5) LENTIL_VMCNT_CASE(6)
+    LENTIL_VMCNT_CASE(7) LENTIL_VMCNT_CASE(8) LENTIL_VMCNT_CASE(9) LENTIL_VMCNT_CASE(10) LENTIL_VMCNT_CASE(11) LENTIL_VMCNT_CASE(12)
+    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+  }
+#undef LENTIL_VMCNT_CASE
+}
 
 LD_DEV void dma2_col(const float4 *ubase, uint32_t lane16, float4 *lds_uniform) {
   // 64 lanes x 16 B at ubase + lane -> lds_uniform[lane]; the base is wave-uniform (scalar registers), the lane part a
@@ -1036,7 +1061,7 @@ __global__ __launch_bounds__(256) void scan_dma2_kernel(ScanArgs a) {
   const uint32_t M = V.visits_per_pixel;
   const uint32_t wave_f4 = dma2_wave_f4(M);
   float4 *rg = smem + (size_t)wave * wave_f4;                      // [2][M][64]
-  float4 *ring = rg + (size_t)2u * M * 64u;                        // [2][3][64]
+  float4 *ring = rg + (size_t)2u * M * 64u;                        // full body: [2][3][64]; lean body: [D][64] of pos_z
   uint32_t *nskip = reinterpret_cast<uint32_t *>(ring + 384u);     // [64]
   uint2 *qmem = reinterpret_cast<uint2 *>(smem + (size_t)4u * wave_f4);
   WaveQueue wq;
@@ -1060,6 +1085,7 @@ __global__ __launch_bounds__(256) void scan_dma2_kernel(ScanArgs a) {
   const bool never = a.P.adaptive_sampling && a.P.inverse_sample_density > 0.2f;
   const double inside_lens = a.lens_length * 0.1;
   const bool po = a.P.cameraType == LENTIL_POLYNOMIAL_OPTICS;
+  const CamMotion still{nullptr, 0u, 0.0f, 1.0f};                  // (no key interpolation code in the tiles' bodies: registers)
 
   nskip[lane] = 0u;
   auto issue_ring = [&](uint64_t v_group, uint32_t slot) {
@@ -1072,22 +1098,46 @@ __global__ __launch_bounds__(256) void scan_dma2_kernel(ScanArgs a) {
   // ---- one tile.  Its rgba column has been requested into rg[buf], its first two ring groups into slots par, par ^ 1.
   // has_next: the tile that follows is `next_tile` -- its rgba goes to rg[buf ^ 1], its first ring groups behind this
   // tile's last.
-  auto do_tile = [&](uint64_t tile, bool has_next, uint64_t next_tile, uint32_t buf, uint32_t par) {
+  // The lean body finds its pos_z groups in the D one-column slots, this tile's group 0 in slot
+  // `ls` (which the body moves on, a slot per group); the full body finds its first two ring groups in slots par, par ^ 1.
+  // Returns the number of open groups: groups in which the depth left some visit's decision to the other columns.
+  const uint32_t D = M < kLeanRing ? M : kLeanRing;               // lean ring slots: group G + D of the wave's chain lies in
+                                                                   // this tile or the next (D <= M), the only one a step knows
+  uint32_t ls = 0;
+  auto do_tile = [&](bool lean, uint64_t tile, bool has_next, uint64_t next_tile, uint32_t buf, uint32_t par) -> uint32_t {
     const uint64_t v0 = tile * TV;
     const uint64_t nv0 = next_tile * TV;
     float4 *srgba = rg + (size_t)buf * M * 64u;
     float4 *nrgba = rg + (size_t)(buf ^ 1u) * M * 64u;
     bool tile_any = false;
+    uint32_t open_groups = 0;
     for (uint32_t g = 0; g < M; ++g) {
-      if (has_next) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-      else if (g + 1u < M) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      const uint32_t slot = (par + g) & 1u;
       float4 pz, vi, tr;
-      lds_read_slot(ring + (size_t)slot * 192u + lane, pz, vi, tr);
-      // the slot's values are in registers: refill it, and ask for the next tile's rgba group
-      if (g + 2u < M) issue_ring(v0 + (uint64_t)(g + 2u) * 64u, slot);
-      else if (has_next) issue_ring(nv0 + (uint64_t)(g + 2u - M) * 64u, slot);
+      if (lean) {
+        // Loads issued behind pos_z group g's, in issue order (loads return in order; a record store among them only makes
+        // the wait include a load more).  With a next tile every step issues pos_z of group G + D, then an rgba group: behind
+        // pos_z(G) lie the rgba of its own step, and two loads from each of the D - 1 steps since -- 2 D - 1.  (Behind a
+        // prologue, a switch or an open group's vmcnt(0) fewer are outstanding than that, and what is awaited has landed.)
+        // Without one no rgba is asked for and the chain ends with this tile: the pos_z of groups g + 1 .. min(g + D, M) - 1.
+        if (has_next) wait_vmcnt_lean(2u * D - 1u);
+        else wait_vmcnt_lean(M - 1u - g < D - 1u ? M - 1u - g : D - 1u);
+        float4 *s = ring + (size_t)ls * 64u;
+        pz = lds_read_f4(s + lane);
+        // the slot's value is in registers: refill it with group G + D
+        if (g + D < M) dma2_col(V.pos_z + v0 + (uint64_t)(g + D) * 64u, lane16, s);
+        else if (has_next) dma2_col(V.pos_z + nv0 + (uint64_t)(g + D - M) * 64u, lane16, s);
+        ls = ls + 1u == D ? 0u : ls + 1u;
+        vi = tr = make_float4(0.f, 0.f, 0.f, 0.f);
+      } else {
+        if (has_next) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
+        else if (g + 1u < M) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const uint32_t slot = (par + g) & 1u;
+        lds_read_slot(ring + (size_t)slot * 192u + lane, pz, vi, tr);
+        // the slot's values are in registers: refill it, and ask for the next tile's rgba group
+        if (g + 2u < M) issue_ring(v0 + (uint64_t)(g + 2u) * 64u, slot);
+        else if (has_next) issue_ring(nv0 + (uint64_t)(g + 2u - M) * 64u, slot);
+      }
       if (has_next) dma2_col(V.rgba + nv0 + (uint64_t)g * 64u, lane16, nrgba + (size_t)g * 64u);
       // ---- the decision (visit_redistributes, src/lentil_filter.cpp:105-165,240)
       const float wx = pz.x, wy = pz.y, wz = pz.z, depth = pz.w;
@@ -1095,19 +1145,30 @@ __global__ __launch_bounds__(256) void scan_dma2_kernel(ScanArgs a) {
       const bool far = (depth == kAiInfinite) || small;
       const float cz = (wx * mz0 + wy * mz1 + wz * mz2 + mz3) * scale;
       const int below = coc_below_by_bands(a.bands, cz);
-      bool flagged;
-      if (__ballot((far && a.P.enable_skydome) || below == 2) == 0ull) {
-        bool r = !never && !far;
-        if (fmaxf(fmaxf(vi.x, vi.y), vi.z) > 0.0f) r = false;
-        if (!a.P.enable_bidir_transmission && fmaxf(fmaxf(tr.x, tr.y), tr.z) > 0.0f) r = false;
-        if (vi.w > 0.0f) r = false;
-        if (below == 1) r = false;
-        if (po && (double)fabsf(cz) < inside_lens) r = false;
-        flagged = r;
-      } else {
-        const uint64_t v = v0 + (uint64_t)g * 64u + lane;
-        flagged = visit_redistributes(a.P, a.lens_length, pz, vi, tr, a.P.inverse_sample_density,
-                                      [&]() { return V.raydir_time[v]; }, V.cam);
+      const bool ask = __ballot((far && a.P.enable_skydome) || below == 2) != 0ull;      // some lane needs the function
+      // open: nothing the depth decides has turned the visit off (far here is far without a skydome, unless `ask`).  The full
+      // body only counts its open groups, to pick the next tile's body: there the two masks it has anyway will do (a visit
+      // that `never` or the inside-the-lens test turns off counts as open: the wave stays in the full body a little longer)
+      bool open = !far && below != 1;
+      if (lean) open = open && !never && !(po && (double)fabsf(cz) < inside_lens);
+      const bool group_open = ask || __ballot(open) != 0ull;
+      if (group_open) ++open_groups;
+      bool flagged = false;
+      if (!lean || group_open) {
+        const uint64_t vg = v0 + (uint64_t)g * 64u, v = vg + lane;
+        if (lean) global_read_2f4_untracked(V.volume_ignore + vg, V.transmission + vg, lane16, vi, tr);
+        if (!ask) {
+          bool r = !never && !far;
+          if (fmaxf(fmaxf(vi.x, vi.y), vi.z) > 0.0f) r = false;
+          if (!a.P.enable_bidir_transmission && fmaxf(fmaxf(tr.x, tr.y), tr.z) > 0.0f) r = false;
+          if (vi.w > 0.0f) r = false;
+          if (below == 1) r = false;
+          if (po && (double)fabsf(cz) < inside_lens) r = false;
+          flagged = r;
+        } else {
+          flagged = visit_redistributes(a.P, a.lens_length, pz, vi, tr, a.P.inverse_sample_density,
+                                        [&]() { return V.raydir_time[v]; }, still);
+        }
       }
       if (__ballot(flagged)) {
         // a few visits in 10^5: the draw count (same function as the draw kernels use); the visit adds nothing to its
@@ -1117,13 +1178,18 @@ __global__ __launch_bounds__(256) void scan_dma2_kernel(ScanArgs a) {
         const uint64_t v = v0 + e;
         int samples = 0;
         if (flagged) {
-          samples = visit_prologue(a.P, a.lens_length, lds_read_f4(srgba + e), pz, V.raydir_time[v], vi, tr, a.P.inverse_sample_density, V.cam).samples;
+          samples = visit_prologue(a.P, a.lens_length, lds_read_f4(srgba + e), pz, V.raydir_time[v], vi, tr, a.P.inverse_sample_density, still).samples;
           srgba[e] = make_float4(0.f, 0.f, 0.f, 0.f);
           atomicAdd(&nskip[e / M], 1u);
         }
         wq.push(flagged, (uint32_t)v, (uint32_t)samples, a);
       }
     }
+    // The sums read this tile's whole rgba column, asked for group by group during the tile before.  Where D < M its last
+    // group was issued ahead of the pos_z of this tile's last group and has landed with it.  Where D == M the two went out in
+    // the same step, pos_z first: behind that rgba group lie the two loads of each of this tile's M steps (no next tile:
+    // nothing).
+    if (lean && D == M) wait_vmcnt_lean(has_next ? 2u * M : 0u);
     // ---- the ordered sums of the tile's 64 pixels (filter_and_add_to_buffer_new, src/lentil.h:938-955)
     typedef float v2f __attribute__((ext_vector_type(2)));
     v2f s01 = {0.f, 0.f}, s23 = {0.f, 0.f};
@@ -1170,6 +1236,17 @@ __global__ __launch_bounds__(256) void scan_dma2_kernel(ScanArgs a) {
       __builtin_amdgcn_wave_barrier();
       wq.end_tile(a);
     }
+    return open_groups;
+  };
+  // the ring's first groups of a tile, for the body that will run it (the caller waits)
+  auto prime_ring = [&](bool for_lean, uint64_t v0, uint32_t par) {
+    if (for_lean) {
+      for (uint32_t g = 0; g < D; ++g) dma2_col(V.pos_z + v0 + (uint64_t)g * 64u, lane16, ring + (size_t)g * 64u);
+      ls = 0;
+    } else {
+      issue_ring(v0, par);
+      if (M > 1u) issue_ring(v0 + 64u, par ^ 1u);
+    }
   };
 
   // ---- a wave's tiles: runs of four, claimed from DevCounters::tile_next in SEQUENCES that shrink as the scan goes on
@@ -1193,6 +1270,8 @@ __global__ __launch_bounds__(256) void scan_dma2_kernel(ScanArgs a) {
   auto run_first = [&](uint32_t r) { return a.tile_begin + (uint64_t)(a.outside_in ? ((r & 1u) ? n_runs - 1u - (r >> 1) : (r >> 1)) : r) * 4u; };
   auto run_len = [&](uint64_t first) { return (uint32_t)(full_end - first < 4u ? full_end - first : 4u); };
   uint32_t buf = 0, par = 0;
+  bool lean = true;             // the body this wave's next tile runs in
+  uint32_t quiet = 0;           // full body: tiles in a row that were not busy
   while (true) {
     // the next sequence of runs (nothing of this wave's is in flight here: the returning atomic does not disturb the
     // counted waits inside a sequence)
@@ -1213,12 +1292,11 @@ __global__ __launch_bounds__(256) void scan_dma2_kernel(ScanArgs a) {
     }
     uint64_t tile = run_first(r);
     uint32_t left = run_len(tile);
-    // prologue: this tile's rgba and first two ring groups, and everything landed
+    // prologue: this tile's rgba and first ring groups, and everything landed
     {
       const uint64_t v0 = tile * TV;
       for (uint32_t g = 0; g < M; ++g) dma2_col(V.rgba + v0 + (uint64_t)g * 64u, lane16, rg + (size_t)buf * M * 64u + (size_t)g * 64u);
-      issue_ring(v0, par);
-      if (M > 1u) issue_ring(v0 + 64u, par ^ 1u);
+      prime_ring(lean, v0, par);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     while (true) {
@@ -1232,10 +1310,25 @@ __global__ __launch_bounds__(256) void scan_dma2_kernel(ScanArgs a) {
         next_tile = run_first(r + stride);
         next_left = run_len(next_tile);
       }
-      do_tile(tile, has_next, next_tile, buf, par);
+      const uint32_t open_groups = do_tile(lean, tile, has_next, next_tile, buf, par);
       if (lane == 0) tl_add(TL_SCAN_TILES, 1u);
       buf ^= 1u;
       par = (par + M) & 1u;
+      // which body next: full after a busy tile, lean again after kQuietTiles in a row that were not
+      const bool busy = open_groups >= kBusyGroups;
+      quiet = busy ? 0u : quiet + 1u;
+      const bool next_lean = lean ? !busy : quiet >= kQuietTiles;
+      if (next_lean != lean) {
+        lean = next_lean;
+        quiet = 0u;
+        if (has_next) {
+          // the ring holds (or is about to receive) the next tile's first groups as the other body wants them: let them
+          // land, ask for them anew, wait -- one latency per switch.  (The next tile's rgba is the same for both.)
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          prime_ring(lean, next_tile * TV, par);
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+      }
       if (left == 1u) { r += stride; --runs_left; }
       if (!has_next) break;
       tile = next_tile; left = next_left;
@@ -1326,6 +1419,15 @@ LD_DEV float4 global_read_f4_untracked(const float4 *p) {
   v4f x;
   asm volatile("global_load_dwordx4 %0, %1, off\n\ts_waitcnt vmcnt(0)" : "=&v"(x) : "v"(p) : "memory");
   return make_float4(x.x, x.y, x.z, x.w);
+}
+// two of them with one wait, at wave-uniform bases (scalar registers) plus the lane's byte offset (scan_dma2_kernel's lean
+// body: the veto columns of a group the depth leaves open)
+LD_DEV void global_read_2f4_untracked(const float4 *p, const float4 *q, uint32_t lane16, float4 &x, float4 &y) {
+  typedef float v4f __attribute__((ext_vector_type(4)));
+  v4f u, v;
+  asm volatile("global_load_dwordx4 %0, %4, %2\n\tglobal_load_dwordx4 %1, %4, %3\n\ts_waitcnt vmcnt(0)"
+               : "=&v"(u), "=&v"(v) : "s"(p), "s"(q), "v"(lane16) : "memory");
+  x = make_float4(u.x, u.y, u.z, u.w); y = make_float4(v.x, v.y, v.z, v.w);
 }
 constexpr uint32_t kDmaMultiRun = 16;      // groups a wave draws at a time
 // A column of a slot is 64 float4 and one of padding: columns 1 KiB apart would put the sum lanes of one pixel -- same
