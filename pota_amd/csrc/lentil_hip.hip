@@ -1798,6 +1798,13 @@ static uint64_t chunk_units(const lentil_params &P, uint64_t nch, uint64_t sum_s
   return nch * (4 * sum_samples + (3 * retries + 32) * n_items);
 }
 
+// Polynomial optics with vignetting_retries < 0: the reference's `tries <= vignetting_retries` (src/lentil.h:592) is false
+// before the first try, so no attempt of any item ever succeeds -- each item uses up its 5 x samples attempts and adds
+// nothing to the frame.  (vignetting_retries = 0 is one try per attempt.)  Such a pass is its scan and this figure: it takes
+// the chunked route, whose chunks read their scan's counters on the host, and launches no draw kernels.
+static bool no_tries(const lentil_params &P) { return P.cameraType == LENTIL_POLYNOMIAL_OPTICS && P.vignetting_retries < 0; }
+__global__ void no_tries_kernel(DevCounters *c) { c->attempted = 5ull * c->sum_samples; }
+
 // Blind mode: buffers and grids from what the previous pass found in this chunk (with headroom); the stream
 // waits for the chunk's scan on the device, the host does not.  prep_items_kernel reads the real item count and
 // raises DevCounters::fallback -- emitting nothing -- when it does not fit.
@@ -1805,6 +1812,7 @@ static int enqueue_chunk_draws_blind(lentil_hip_ctx *ctx, int ci, DrawArgs &da, 
   lentil_hip_ctx::Chunk &ch = ctx->chunks[ci];
   *done = false;
   if (!ch.have_est) return LENTIL_OK;
+  if (no_tries(ctx->P)) return LENTIL_OK;       // (enqueue_chunk_draws knows what such a pass is)
   const uint64_t cap = ch.v_end - ch.v_begin;
   uint64_t items = ch.est_items + ch.est_items / 4 + 1024;
   if (items > cap) items = cap;
@@ -1847,6 +1855,12 @@ static int enqueue_chunk_draws(lentil_hip_ctx *ctx, int ci, DrawArgs &da, int bl
   ch.was_blind = false;
   ch.have_est = true; ch.est_items = n_items; ch.est_sum = c.sum_samples;
   if (n_items == 0) return LENTIL_OK;
+  if (no_tries(P)) {
+    hipLaunchKernelGGL(no_tries_kernel, dim3(1), dim3(1), 0, ch.stream, dctr);
+    HIP_TRY(ctx, hipGetLastError());
+    ch.n_items = 0;       // complete: nothing left for the continuation loop
+    return LENTIL_OK;
+  }
   const bool po = P.cameraType == LENTIL_POLYNOMIAL_OPTICS;
   const uint32_t retries = po ? (uint32_t)(P.vignetting_retries < 0 ? 0 : P.vignetting_retries) : 0u;
   da.ctr = dctr;
@@ -2587,7 +2601,8 @@ static int redistribute_streamed(lentil_hip_ctx *ctx, bool *streamed, bool *defe
   if (!ctx->stream_mode || P.cameraType != LENTIL_POLYNOMIAL_OPTICS || !ctx->have_total_est || ctx->V.n == 0)
     return LENTIL_OK;
   if (ctx->V.n > 0xFFFFFFF0ull) return LENTIL_OK;
-  if (ctx->probe_fn) return LENTIL_OK;       // (occlusion probes: the host answers between a round's solves and its accept -- the round-by-round form)
+  if (no_tries(P)) return LENTIL_OK;         // (vignetting_retries < 0: a scan and a count, enqueue_chunk_draws)
+  if (ctx->probe_fn) return LENTIL_OK;      // (occlusion probes: the host answers between a round's solves and its accept -- the round-by-round form)
   // Only into a frame that has been cleared since its last pass (every caller's order: clear, redistribute, resolve): a
   // streamed pass whose waves give up waiting after draws have been accepted is recovered by wiping the frame and running
   // the pass again, which must not cost an earlier pass's sums.  A second pass into the same frame takes the chunked form,
