@@ -637,8 +637,48 @@ typedef struct lentil_probe_segment {
 } lentil_probe_segment;
 typedef void (*lentil_probe_fn)(void *user, uint64_t n, const lentil_probe_segment *segments, uint8_t *occluded);
 int lentil_hip_set_occlusion_probe(lentil_hip_ctx *ctx, lentil_probe_fn fn, void *user, const float *camera_to_world);
-/* stats[0] segments handed to the callback since the context was created, [1] of them answered "occluded", [2] callback calls */
+/* stats[0] segments handed to the callback since the context was created, [1] of them answered "occluded", [2] callback calls.
+ * Under a device callback (below) segments and occluded answers are counted on the device and read when the call observes the
+ * context; [2] counts the callback's calls, and a round enqueued blind calls even when its list turns out empty. */
 int lentil_hip_probe_stats(lentil_hip_ctx *ctx, uint64_t stats[3]);
+
+/* Occlusion probes answered on the GPU.  A renderer whose scene lives in device memory needs neither the list's trip over PCIe
+ * nor the host waits around it: the segments are written in device memory, the renderer's own kernels answer them there, and
+ * the library's apply kernel reads the answers there.  The list is the host form's list, segment for segment; so are the
+ * results.
+ *   fn(user, hip_stream, capacity, d_n, d_segments, d_occluded)
+ *   When and where: on the thread that runs the pass -- the caller of lentil_hip_redistribute, or the call that observes the pass
+ *     and finishes it --, once per list.
+ *   What it receives: d_n, d_segments and d_occluded are device memory of the context's GPU.  The list has min(*d_n, capacity)
+ *     entries.  *d_n is final only once the work already enqueued on hip_stream has run: the callback must not read it on the
+ *     host.
+ *   What it must do: ENQUEUE its work on hip_stream (a hipStream_t) and return.  hip_stream is the chunk's stream, not necessarily
+ *     lentil_hip_stream(ctx): chunks run on streams of their own.  d_occluded[0 .. capacity) is zero on entry; the callback writes
+ *     non-zero for an occluded segment.  It must not call into the context.  It may synchronise the stream: legal, and it costs
+ *     the overlap.
+ *   Errors and switching: a non-zero return fails the pass with LENTIL_ERR_INVALID, the code in the message; the context stays
+ *     usable.  Host and device callbacks are mutually exclusive: setting either replaces the other, fn == NULL on either setter
+ *     switches probing off.  camera_to_world means what it means for the host setter.
+ *   With a device callback the rounds of polynomial optics (abb_chromatic == 0) and of the plain thin lens are enqueued without
+ *   any host wait or copy.  Every chunk's lists are made with the capacity of the chunk's result pool, which bounds every round's
+ *   list whatever the renderer answers (29 B of list per result slot).  A list that does not fit all the same (LENTIL_PROBE_DEVICE_CAP)
+ *   is detected on the device: nothing of that round is accepted, the chunk's draws are redone with every list counted on
+ *   the host first (one 4-byte read-back per round; lentil_counters::fallback_chunks, lentil_hip_last_redo_note), and an overflow
+ *   the redo cannot cover -- in a later round, after the chunk has accepted draws -- fails the pass with LENTIL_ERR_NOMEM; the
+ *   next pass is sized afresh.  Thin lens with abb_chromatic > 0 keeps two 4-byte read-backs per
+ *   turn of its loop (the list's length, the occluded count).  A probed pass, host or device, does not stream.
+ * probe_device_stats, since the context was created: [0] lists handed to the device callback, [1] host waits the library made
+ *   on behalf of probes under a device callback, [2] lists that did not fit their buffers, [3] the longest list so far.
+ * lentil_hip_test_sphere_occluder_device (lentil_hip_test_* family): a lentil_probe_device_fn -- one lane per segment, the
+ *   analytic sphere test of the tests' CPU occluder (fp32 in, fp64 operations in the same order, no contraction: the same answers
+ *   bit for bit).  user: four host floats {cx, cy, cz, r}, read at call time; user == NULL returns 1 and enqueues nothing.
+ * LENTIL_PROBE_DEVICE_CAP (read at lentil_hip_create): caps a blind pass's list capacity -- a test hook. */
+typedef int (*lentil_probe_device_fn)(void *user, void *hip_stream, uint32_t capacity, const uint32_t *d_n,
+                                      const lentil_probe_segment *d_segments, uint8_t *d_occluded);
+int lentil_hip_set_occlusion_probe_device(lentil_hip_ctx *ctx, lentil_probe_device_fn fn, void *user, const float *camera_to_world);
+int lentil_hip_probe_device_stats(lentil_hip_ctx *ctx, uint64_t stats[4]);
+int lentil_hip_test_sphere_occluder_device(void *user, void *hip_stream, uint32_t capacity, const uint32_t *d_n,
+                                           const lentil_probe_segment *d_segments, uint8_t *d_occluded);
 
 /* The asynchronous end of a pass (round 6).  lentil_hip_redistribute no longer ends with the host waiting for the device: a
  * streamed pass returns once its kernels are enqueued, and whether it needs more work (buffers that were too small, a draw

@@ -23,7 +23,8 @@ EXPORTS = [
     "lentil_hip_touched_rows", "lentil_hip_merge_rows", "lentil_hip_resolve_rows",
     "lentil_hip_pack_rows", "lentil_hip_merge_packed_rows", "lentil_hip_compact_rows", "lentil_hip_merge_sparse",
     "lentil_hip_get_counters", "lentil_hip_last_timing", "lentil_hip_last_launches", "lentil_hip_set_draw_log",
-    "lentil_hip_batch_model_stats", "lentil_hip_process_stats", "lentil_hip_process_stall_notes", "lentil_hip_set_async", "lentil_hip_pass_totals", "lentil_hip_set_occlusion_probe", "lentil_hip_probe_stats", "lentil_hip_debug_batch_estimate", "lentil_hip_box_probe",
+    "lentil_hip_batch_model_stats", "lentil_hip_process_stats", "lentil_hip_process_stall_notes", "lentil_hip_set_async", "lentil_hip_pass_totals", "lentil_hip_set_occlusion_probe", "lentil_hip_probe_stats",
+    "lentil_hip_set_occlusion_probe_device", "lentil_hip_probe_device_stats", "lentil_hip_test_sphere_occluder_device", "lentil_hip_debug_batch_estimate", "lentil_hip_box_probe",
     "lentil_hip_lens_jit_status", "lentil_hip_lens_jit_wait", "lentil_hip_debug_lens_jit_source", "lentil_hip_debug_lens_jit_compile",
     "lentil_hip_download_draw_log", "lentil_hip_test_lt_sample_aperture",
     "lentil_hip_test_trace_bw_po", "lentil_hip_test_aperture_sample", "lentil_hip_debug_scan_bands", "lentil_hip_debug_scan_lean_counts", "lentil_hip_debug_last_scan",
@@ -157,6 +158,9 @@ def load_library():
         "lentil_hip_set_async": (i, [vp, i]),
         "lentil_hip_set_occlusion_probe": (i, [vp, vp, vp, vp]),
         "lentil_hip_probe_stats": (i, [vp, C.POINTER(C.c_uint64)]),
+        "lentil_hip_set_occlusion_probe_device": (i, [vp, vp, vp, vp]),
+        "lentil_hip_probe_device_stats": (i, [vp, C.POINTER(C.c_uint64)]),
+        "lentil_hip_test_sphere_occluder_device": (i, [vp, vp, u32, vp, vp, vp]),
         "lentil_hip_pass_totals": (i, [vp, C.POINTER(_abi.PassTotals), i]),
         "lentil_hip_box_probe": (i, [vp, C.POINTER(C.c_double)]),
         "lentil_hip_lens_jit_status": (i, [vp, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
@@ -211,6 +215,12 @@ def load_library():
         raise RuntimeError("liblentil_hip.so ABI version mismatch")
     _lib = lib
     return lib
+
+
+def sphere_occluder_device():
+    """address of lentil_hip_test_sphere_occluder_device, the library's analytic lentil_probe_device_fn: user -> four host
+    floats (centre, radius)"""
+    return C.cast(load_library().lentil_hip_test_sphere_occluder_device, C.c_void_p).value
 
 
 def host_alloc(nbytes):
@@ -625,6 +635,19 @@ class Context:
         """(segments probed, of them occluded, callback calls) since the context was created"""
         n = (C.c_uint64 * 3)()
         self._chk(self.lib.lentil_hip_probe_stats(self.h, n))
+        return tuple(int(x) for x in n)
+
+    def set_occlusion_probe_device(self, fn, user=None, camera_to_world=None):
+        """fn: address of a lentil_probe_device_fn, which enqueues the renderer's answers on the stream it is given (None switches
+        probing off; replaces a host callback); user and camera_to_world as for set_occlusion_probe"""
+        self._probe_keep = (np.ascontiguousarray(camera_to_world, np.float32) if camera_to_world is not None else None)
+        self._chk(self.lib.lentil_hip_set_occlusion_probe_device(self.h, fn, user, self._probe_keep.ctypes.data if self._probe_keep is not None else None))
+
+    def probe_device_stats(self):
+        """(lists handed to the device callback, host waits made for such lists, lists that did not fit their buffers, the longest
+        list) since the context was created"""
+        n = (C.c_uint64 * 4)()
+        self._chk(self.lib.lentil_hip_probe_device_stats(self.h, n))
         return tuple(int(x) for x in n)
 
     def set_async(self, on):

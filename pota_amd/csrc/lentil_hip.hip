@@ -52,6 +52,32 @@ struct StreamTail {
   bool did_more = false;              // streamed_finish had to enqueue more work (rounds, a redo): the frame moved on
 };
 
+// One list of occlusion probes at a time: segments, result slots, answers and the list's counter on the device; pinned host
+// copies where the host callback reads and fills them.  Every chunk has its own (and the thin-lens abb_chromatic > 0 pass a
+// sixth): chunks probe on streams of their own, and nothing orders one chunk's apply against the next chunk's list.
+struct ProbeBuf {
+  lentil_probe_segment *seg = nullptr, *h_seg = nullptr;
+  uint32_t *idx = nullptr;
+  uint8_t *occ = nullptr, *h_occ = nullptr;
+  unsigned int *count = nullptr;
+  uint64_t cap = 0, h_cap = 0;
+  bool occ_dirty = true;       // the answer bytes may be non-zero (device form: zeroed before the next list)
+};
+
+// the list's arrays go (to be allocated larger); the counter stays
+static void probe_buf_release(ProbeBuf &pb) {
+  (void)hipFree(pb.seg); (void)hipFree(pb.idx); (void)hipFree(pb.occ);
+  if (pb.h_seg) (void)hipHostFree(pb.h_seg);
+  if (pb.h_occ) (void)hipHostFree(pb.h_occ);
+  pb.seg = nullptr; pb.idx = nullptr; pb.occ = nullptr; pb.h_seg = nullptr; pb.h_occ = nullptr;
+  pb.cap = pb.h_cap = 0;
+}
+static void probe_buf_free(ProbeBuf &pb) {
+  probe_buf_release(pb);
+  (void)hipFree(pb.count);
+  pb = ProbeBuf{};
+}
+
 struct lentil_hip_ctx {
   HostTrace trace;
   int device = 0;
@@ -146,6 +172,11 @@ struct lentil_hip_ctx {
     bool heavy_pending = false;    // this pass: the chunk's first solve round fills the chip; `done` marks its end
     uint64_t est_items = 0, est_sum = 0;
     int est_rounds = 3;            // rounds the chunk's items needed (DevCounters::rounds_used)
+    // occlusion probes: this chunk's lists; under a device callback the capacity this pass's lists are made with, and whether
+    // the host counts each list first (the redo of a chunk whose list did not fit)
+    ProbeBuf pb;
+    bool probe_counted = false;
+    uint64_t probe_cap_now = 0;
   };
   std::vector<Chunk> chunks;
   int n_chunks = 2;
@@ -327,19 +358,21 @@ struct lentil_hip_ctx {
   lentil_pass_totals totals{};
   std::vector<std::string> notes;     // redo notes since the totals were last reset (at most 8 kept)
   // occlusion probes (lentil_hip_set_occlusion_probe): the renderer's callback, AiCameraToWorldMatrix (given, or the fp64 inverse of the
-  // world-to-camera matrix / of every motion key), the list buffers (device, and pinned host copies the callback reads and fills)
+  // world-to-camera matrix / of every motion key); the list buffers are the chunks' (ProbeBuf)
   lentil_probe_fn probe_fn = nullptr;
   void *probe_user = nullptr;
   bool probe_c2w_given = false;
   float probe_c2w[16];
   std::vector<float> h_cam_keys;              // lentil_hip_set_camera_motion's keys, kept for their inverses
   float *d_c2w_keys = nullptr;
-  lentil_probe_segment *d_probe_seg = nullptr, *h_probe_seg = nullptr;
-  uint32_t *d_probe_idx = nullptr;
-  uint8_t *d_probe_occ = nullptr, *h_probe_occ = nullptr;
-  unsigned int *d_probe_count = nullptr;
-  uint64_t probe_cap = 0;
+  bool c2w_keys_valid = false;                // d_c2w_keys holds the inverses of the keys as they stand
+  ProbeBuf tlc_pb;                            // the lists of a thin-lens abb_chromatic > 0 pass (tl_chroma_probe; the chunks have their own)
   uint64_t n_probes = 0, n_probes_occluded = 0, n_probe_calls = 0;     // since the context was created (lentil_hip_probe_stats)
+  // ... answered on the device (lentil_hip_set_occlusion_probe_device): the renderer's callback; lists handed to it, host waits made
+  // for such lists, lists that did not fit, the longest list (lentil_hip_probe_device_stats)
+  lentil_probe_device_fn probe_dev_fn = nullptr;
+  uint64_t n_dev_lists = 0, n_dev_waits = 0, n_dev_overflows = 0, dev_longest = 0;
+  uint64_t probe_dev_cap = 0;                 // LENTIL_PROBE_DEVICE_CAP: a blind pass's list capacity at most (0: no cap; tests)
   struct LentilUpload *upload = nullptr;   // lentil_upload.h: the visit stream handed over piece by piece
   struct LentilComm *comm = nullptr; // lentil_comm.h: this context's RCCL communicator, if one was asked for
   struct LentilCrypto *crypto = nullptr;   // lentil_crypto.h: cryptomatte AOVs, if any were allocated
@@ -408,7 +441,7 @@ static int fail(lentil_hip_ctx *ctx, int code, const std::string &msg) {
       return fail(ctx, LENTIL_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));   \
   } while (0)
 static int settle(lentil_hip_ctx *ctx);
-static int probe_round(lentil_hip_ctx *ctx, const DrawArgs &da, hipStream_t st);
+static int probe_round(lentil_hip_ctx *ctx, int ci, const DrawArgs &da, hipStream_t st);
 static int join_clear(lentil_hip_ctx *ctx);
 static void harvest_ready(lentil_hip_ctx *ctx);
 static int resolve_range(lentil_hip_ctx *ctx, uint64_t p_begin, uint64_t p_end);
@@ -613,6 +646,7 @@ LENTIL_API int lentil_hip_create(int device, lentil_hip_ctx **out_ctx) {
   HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_crypto, hipEventDisableTiming));
   { const int rc = pick_concurrent_streams(ctx); if (rc) return rc; }
   if (const char *e = getenv("LENTIL_INJECT_STALL")) ctx->inject_stall_at = atoi(e);
+  if (const char *e = getenv("LENTIL_PROBE_DEVICE_CAP")) { const long long v = atoll(e); ctx->probe_dev_cap = v > 0 ? (uint64_t)v : 0; }
   if (const char *ft = getenv("LENTIL_FORCE_TABLES")) ctx->use_generated = !(ft[0] == '1');
   if (const char *fc = getenv("LENTIL_FIRST_CHUNK_FRAC")) {
     const double f = atof(fc);
@@ -783,10 +817,9 @@ LENTIL_API int lentil_hip_destroy(lentil_hip_ctx *ctx) {
   if (ctx->ev_crypto) (void)hipEventDestroy(ctx->ev_crypto);
   (void)hipFree(ctx->d_ctr);
   (void)hipFree(ctx->d_ranges);
-  (void)hipFree(ctx->d_c2w_keys); (void)hipFree(ctx->d_probe_seg); (void)hipFree(ctx->d_probe_idx); (void)hipFree(ctx->d_probe_occ);
-  (void)hipFree(ctx->d_probe_count);
-  if (ctx->h_probe_seg) (void)hipHostFree(ctx->h_probe_seg);
-  if (ctx->h_probe_occ) (void)hipHostFree(ctx->h_probe_occ);
+  (void)hipFree(ctx->d_c2w_keys);
+  probe_buf_free(ctx->tlc_pb);
+  for (auto &ch : ctx->chunks) probe_buf_free(ch.pb);
   if (ctx->jit_module) (void)hipModuleUnload(ctx->jit_module);
   (void)hipFree(ctx->d_bm_land); (void)hipFree(ctx->d_bm_box); (void)hipFree(ctx->d_bm_npass);
   (void)hipFree(ctx->d_xor); (void)hipFree(ctx->d_tlc_res); (void)hipFree(ctx->d_tlc_off); (void)hipFree(ctx->d_tlc_tasks);
@@ -1211,6 +1244,7 @@ LENTIL_API int lentil_hip_set_camera_motion(lentil_hip_ctx *ctx, uint32_t n_keys
     HIP_TRY(ctx, hipMemcpy(ctx->d_cam_keys, w2c, sizeof(float) * 16 * n_keys, hipMemcpyHostToDevice));
     ctx->n_cam_keys = n_keys;
     ctx->h_cam_keys.assign(w2c, w2c + (size_t)16 * n_keys);       // (the occlusion probe's camera-to-world keys are their inverses)
+    ctx->c2w_keys_valid = false;
   }
   apply_camera_motion(ctx);
   return LENTIL_OK;
@@ -1246,6 +1280,17 @@ static void invert4x4(const float m_[16], float out[16]) {
 LENTIL_API int lentil_hip_set_occlusion_probe(lentil_hip_ctx *ctx, lentil_probe_fn fn, void *user, const float *camera_to_world) {
   CHECK_CTX(ctx);
   ctx->probe_fn = fn;
+  ctx->probe_dev_fn = nullptr;       // (host and device callbacks are mutually exclusive)
+  ctx->probe_user = user;
+  ctx->probe_c2w_given = fn != nullptr && camera_to_world != nullptr;
+  if (ctx->probe_c2w_given) memcpy(ctx->probe_c2w, camera_to_world, sizeof ctx->probe_c2w);
+  return LENTIL_OK;
+}
+
+LENTIL_API int lentil_hip_set_occlusion_probe_device(lentil_hip_ctx *ctx, lentil_probe_device_fn fn, void *user, const float *camera_to_world) {
+  CHECK_CTX(ctx);
+  ctx->probe_dev_fn = fn;
+  ctx->probe_fn = nullptr;
   ctx->probe_user = user;
   ctx->probe_c2w_given = fn != nullptr && camera_to_world != nullptr;
   if (ctx->probe_c2w_given) memcpy(ctx->probe_c2w, camera_to_world, sizeof ctx->probe_c2w);
@@ -1259,89 +1304,220 @@ LENTIL_API int lentil_hip_probe_stats(lentil_hip_ctx *ctx, uint64_t stats[3]) {
   return LENTIL_OK;
 }
 
-// What every list of probes needs: AiCameraToWorldMatrix (and its motion keys, on the device) and the list's counter.
+LENTIL_API int lentil_hip_probe_device_stats(lentil_hip_ctx *ctx, uint64_t stats[4]) {
+  CHECK_CTX(ctx);
+  if (!stats) return fail(ctx, LENTIL_ERR_INVALID, "stats is null");
+  stats[0] = ctx->n_dev_lists; stats[1] = ctx->n_dev_waits; stats[2] = ctx->n_dev_overflows; stats[3] = ctx->dev_longest;
+  return LENTIL_OK;
+}
+
+// The analytic sphere occluder of the tests as a device callback (include/lentil_hip.h): test_sphere_occluder_kernel on the
+// list's stream, with the sphere as the host holds it now.
+LENTIL_API int lentil_hip_test_sphere_occluder_device(void *user, void *hip_stream, uint32_t capacity, const uint32_t *d_n,
+                                                      const lentil_probe_segment *d_segments, uint8_t *d_occluded) {
+  if (!user) return 1;
+  const float *sp = static_cast<const float *>(user);
+  if (!capacity) return 0;
+  const unsigned blocks = (unsigned)(((uint64_t)capacity + 255u) / 256u < 1024u ? ((uint64_t)capacity + 255u) / 256u : 1024u);
+  hipLaunchKernelGGL(test_sphere_occluder_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(hip_stream), sp[0], sp[1], sp[2], sp[3],
+                     capacity, d_n, d_segments, d_occluded);
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+static bool probing(const lentil_hip_ctx *ctx) { return ctx->probe_fn != nullptr || ctx->probe_dev_fn != nullptr; }
+
+// What every list of probes needs: AiCameraToWorldMatrix (and its motion keys, on the device -- uploaded once per set of keys,
+// with one host wait then: the chunks' streams all read them).
 static int probe_prepare(lentil_hip_ctx *ctx, ProbeArgs &pr, hipStream_t st) {
   if (ctx->probe_c2w_given) memcpy(pr.c2w, ctx->probe_c2w, sizeof pr.c2w);
   else invert4x4(&ctx->P.world_to_camera[0][0], &pr.c2w[0][0]);
   if (ctx->n_cam_keys >= 2 && ctx->h_cam_keys.size() == (size_t)16 * ctx->n_cam_keys) {
-    float inv[16 * LENTIL_MAX_MOTION_KEYS];
-    for (uint32_t k = 0; k < ctx->n_cam_keys; ++k) invert4x4(&ctx->h_cam_keys[(size_t)16 * k], inv + 16 * k);
-    if (!ctx->d_c2w_keys) HIP_TRY(ctx, hipMalloc(&ctx->d_c2w_keys, sizeof(float) * 16 * LENTIL_MAX_MOTION_KEYS));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_c2w_keys, inv, sizeof(float) * 16 * ctx->n_cam_keys, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));       // (`inv` is on this function's stack)
+    if (!ctx->c2w_keys_valid) {
+      float inv[16 * LENTIL_MAX_MOTION_KEYS];
+      for (uint32_t k = 0; k < ctx->n_cam_keys; ++k) invert4x4(&ctx->h_cam_keys[(size_t)16 * k], inv + 16 * k);
+      if (!ctx->d_c2w_keys) HIP_TRY(ctx, hipMalloc(&ctx->d_c2w_keys, sizeof(float) * 16 * LENTIL_MAX_MOTION_KEYS));
+      for (auto &ch : ctx->chunks) if (ch.stream) HIP_TRY(ctx, hipStreamSynchronize(ch.stream));        // (no list kernel of another chunk is reading the old ones)
+      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->d_c2w_keys, inv, sizeof(float) * 16 * ctx->n_cam_keys, hipMemcpyHostToDevice, st));
+      HIP_TRY(ctx, hipStreamSynchronize(st));       // (`inv` is on this function's stack)
+      ctx->c2w_keys_valid = true;
+    }
     pr.c2w_keys = ctx->d_c2w_keys;
   }
-  if (!ctx->d_probe_count) HIP_TRY(ctx, hipMalloc(&ctx->d_probe_count, sizeof(unsigned int)));
   return LENTIL_OK;
 }
 
-static int probe_alloc(lentil_hip_ctx *ctx, uint64_t cap) {
-  HIP_TRY(ctx, hipMalloc(&ctx->d_probe_seg, cap * sizeof(lentil_probe_segment)));
-  HIP_TRY(ctx, hipMalloc(&ctx->d_probe_idx, cap * sizeof(uint32_t)));
-  HIP_TRY(ctx, hipMalloc(&ctx->d_probe_occ, cap));
-  HIP_TRY(ctx, hipHostMalloc((void **)&ctx->h_probe_seg, cap * sizeof(lentil_probe_segment), hipHostMallocDefault));
-  HIP_TRY(ctx, hipHostMalloc((void **)&ctx->h_probe_occ, cap, hipHostMallocDefault));
-  ctx->probe_cap = cap;
+// room for `cap` segments (never shrinks, never more than 0xFFFFFFF0: a list's length and capacity are 32-bit on the device);
+// `host`: and pinned copies of the same size for the host callback
+static int probe_buf_reserve(lentil_hip_ctx *ctx, ProbeBuf &pb, uint64_t cap, bool host) {
+  if (!pb.count) HIP_TRY(ctx, hipMalloc(&pb.count, sizeof(unsigned int)));
+  if (cap > 0xFFFFFFF0ull) cap = 0xFFFFFFF0ull;
+  if (cap < 64) cap = 64;
+  if (pb.cap < cap) {
+    probe_buf_release(pb);
+    HIP_TRY(ctx, hipMalloc(&pb.seg, cap * sizeof(lentil_probe_segment)));
+    HIP_TRY(ctx, hipMalloc(&pb.idx, cap * sizeof(uint32_t)));
+    HIP_TRY(ctx, hipMalloc(&pb.occ, cap));
+    pb.cap = cap;
+    pb.occ_dirty = true;
+  }
+  if (host && pb.h_cap < pb.cap) {
+    if (pb.h_seg) (void)hipHostFree(pb.h_seg);
+    if (pb.h_occ) (void)hipHostFree(pb.h_occ);
+    pb.h_seg = nullptr; pb.h_occ = nullptr; pb.h_cap = 0;
+    HIP_TRY(ctx, hipHostMalloc((void **)&pb.h_seg, pb.cap * sizeof(lentil_probe_segment), hipHostMallocDefault));
+    HIP_TRY(ctx, hipHostMalloc((void **)&pb.h_occ, pb.cap, hipHostMallocDefault));
+    pb.h_cap = pb.cap;
+  }
   return LENTIL_OK;
 }
 
-// One list of probes and the renderer's answers: `launch_list(pr)` enqueues the kernel that fills pr.seg / pr.idx and counts
+// A list's first buffers where nothing sizes them beforehand (the host form, the thin-lens abb_chromatic > 0 loop): every chunk
+// has its own since nothing orders the chunks' lists, so they start small -- 1.9 MB on the device and 1.6 MB pinned -- and a
+// list that outgrows them is counted, given buffers of n + n/4 + 4096 and made once more.
+static constexpr uint64_t kProbeFirstCap = 1ull << 16;
+
+static void probe_bind(const ProbeBuf &pb, uint64_t cap, ProbeArgs &pr) {
+  pr.seg = pb.seg; pr.idx = pb.idx; pr.cap = (uint32_t)cap;       // (at most pb.cap: probe_buf_reserve keeps that below 2^32)
+  pr.count = pb.count; pr.occluded = pb.occ;
+}
+
+// One list of probes and the host callback's answers: `launch_list(pr)` enqueues the kernel that fills pr.seg / pr.idx and counts
 // in pr.count (a list that outgrew the buffers is made once more, into larger ones); the callback, on the calling thread;
 // the answers in pr.occluded on the device when some segment is occluded.  *n: segments asked; *occ: of them occluded --
 // the caller applies those.  The host waits twice: for the list and, inside the callback, for the renderer.
+// `pb` is the asking chunk's own.  (Until the device callback came there was one set of buffers for the context, and this
+// function returns with the upload of the answers -- and its caller with the kernel that applies them -- only ENQUEUED on the
+// chunk's stream: the next chunk's list kernel, on another stream with nothing ordering the two, wrote the same index and
+// answer arrays, and its memset of the pinned answers could precede the upload's read of them.)
 template <class LaunchList>
-static int probe_ask(lentil_hip_ctx *ctx, ProbeArgs &pr, hipStream_t st, LaunchList launch_list, unsigned int *n_out, uint64_t *occ_out) {
+static int probe_ask(lentil_hip_ctx *ctx, ProbeBuf &pb, ProbeArgs &pr, hipStream_t st, LaunchList launch_list, unsigned int *n_out, uint64_t *occ_out) {
   *n_out = 0; *occ_out = 0;
   for (int attempt = 0; attempt < 2; ++attempt) {
-    if (ctx->probe_cap == 0) { const int rc = probe_alloc(ctx, 1ull << 20); if (rc) return rc; }
-    pr.seg = ctx->d_probe_seg; pr.idx = ctx->d_probe_idx; pr.cap = (uint32_t)(ctx->probe_cap < 0xFFFFFFF0ull ? ctx->probe_cap : 0xFFFFFFF0ull);
-    pr.count = ctx->d_probe_count; pr.occluded = ctx->d_probe_occ;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_probe_count, 0, sizeof(unsigned int), st));
+    { const int rc = probe_buf_reserve(ctx, pb, pb.cap ? pb.cap : kProbeFirstCap, true); if (rc) return rc; }
+    probe_bind(pb, pb.cap, pr);
+    pb.occ_dirty = true;
+    HIP_TRY(ctx, hipMemsetAsync(pb.count, 0, sizeof(unsigned int), st));
     launch_list(pr);
     HIP_TRY(ctx, hipGetLastError());
     unsigned int n = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&n, ctx->d_probe_count, sizeof n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(&n, pb.count, sizeof n, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
-    if ((uint64_t)n > ctx->probe_cap) {
+    if ((uint64_t)n > pb.cap) {
       // the list did not fit: buffers for what the kernel counted, and once more
       if (attempt) return fail(ctx, LENTIL_ERR_NOMEM, "occlusion probes: the list outgrew its buffers twice");
-      (void)hipFree(ctx->d_probe_seg); (void)hipFree(ctx->d_probe_idx); (void)hipFree(ctx->d_probe_occ);
-      (void)hipHostFree(ctx->h_probe_seg); (void)hipHostFree(ctx->h_probe_occ);
-      ctx->d_probe_seg = nullptr; ctx->d_probe_idx = nullptr; ctx->d_probe_occ = nullptr; ctx->h_probe_seg = nullptr; ctx->h_probe_occ = nullptr;
-      ctx->probe_cap = 0;
-      const int rc = probe_alloc(ctx, (uint64_t)n + (uint64_t)n / 4 + 4096);
+      const int rc = probe_buf_reserve(ctx, pb, (uint64_t)n + (uint64_t)n / 4 + 4096, true);
       if (rc) return rc;
       continue;
     }
     if (n == 0) return LENTIL_OK;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_probe_seg, ctx->d_probe_seg, (size_t)n * sizeof(lentil_probe_segment), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(pb.h_seg, pb.seg, (size_t)n * sizeof(lentil_probe_segment), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
-    memset(ctx->h_probe_occ, 0, n);
-    ctx->probe_fn(ctx->probe_user, n, ctx->h_probe_seg, ctx->h_probe_occ);
+    memset(pb.h_occ, 0, n);
+    ctx->probe_fn(ctx->probe_user, n, pb.h_seg, pb.h_occ);
     uint64_t occ = 0;
-    for (unsigned int i = 0; i < n; ++i) occ += ctx->h_probe_occ[i] ? 1u : 0u;
+    for (unsigned int i = 0; i < n; ++i) occ += pb.h_occ[i] ? 1u : 0u;
     ctx->n_probes += n; ctx->n_probes_occluded += occ; ++ctx->n_probe_calls;
-    if (occ) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_probe_occ, ctx->h_probe_occ, n, hipMemcpyHostToDevice, st));
+    if (occ) HIP_TRY(ctx, hipMemcpyAsync(pb.occ, pb.h_occ, n, hipMemcpyHostToDevice, st));
     *n_out = n; *occ_out = occ;
     return LENTIL_OK;
   }
   return LENTIL_OK;
 }
 
+// A probed pass ends in an error: what it has enqueued on the context's streams is waited for (the next pass finds them
+// empty), every list's answer bytes may hold what a callback wrote and no apply kernel zeroed, and the next pass reads
+// every chunk's scan back and sizes its lists from that.
+static void probe_abandon(lentil_hip_ctx *ctx) {
+  for (auto &ch : ctx->chunks) {
+    if (ch.stream) (void)hipStreamSynchronize(ch.stream);
+    ch.pb.occ_dirty = true;
+    ch.have_est = false;
+  }
+  (void)hipStreamSynchronize(ctx->stream);
+  ctx->tlc_pb.occ_dirty = true;
+}
+
+// The device callback on one list: `cap` entries at most, the length in pb.count once the stream has come this far.  A non-zero
+// return fails the pass: what the pass has enqueued so far is waited for (the next pass finds the streams empty), and the
+// callback may have written answers.
+static int probe_call_device(lentil_hip_ctx *ctx, ProbeBuf &pb, uint64_t cap, hipStream_t st) {
+  ++ctx->n_probe_calls; ++ctx->n_dev_lists;
+  const int code = ctx->probe_dev_fn(ctx->probe_user, (void *)st, (uint32_t)cap, pb.count, pb.seg, pb.occ);
+  if (code) {
+    probe_abandon(ctx);
+    return fail(ctx, LENTIL_ERR_INVALID, "occlusion probes: the device callback returned " + std::to_string(code));
+  }
+  return LENTIL_OK;
+}
+
+// One round's probes under a device callback, enqueued on the round's stream with no host wait and no copy: counter reset,
+// probe_list_kernel, the renderer's callback, probe_apply_device_kernel -- always, nobody here knows whether anything is
+// occluded.  The list is made with the capacity the chunk's draws were sized with (Chunk::probe_cap_now); one that does not
+// fit is the apply kernel's to detect.  `probe_counted` (the redo of a chunk whose list did not fit): the host reads the
+// list's length first -- 4 bytes, one wait -- grows the buffers where needed and has the list made again.
+static int probe_round_device(lentil_hip_ctx *ctx, lentil_hip_ctx::Chunk &ch, const DrawArgs &da, hipStream_t st) {
+  ProbeBuf &pb = ch.pb;
+  ProbeArgs pr{};
+  int rc;
+  if ((rc = probe_prepare(ctx, pr, st))) return rc;
+  const dim3 grid((unsigned)ctx->num_cu * 4u), block(256);
+  if (!pb.cap && (rc = probe_buf_reserve(ctx, pb, 4096, false))) return rc;
+  uint64_t cap = ch.probe_counted || ch.probe_cap_now > pb.cap ? pb.cap : ch.probe_cap_now;
+  for (int attempt = 0;; ++attempt) {
+    if (pb.occ_dirty) { HIP_TRY(ctx, hipMemsetAsync(pb.occ, 0, pb.cap, st)); pb.occ_dirty = false; }
+    probe_bind(pb, cap, pr);
+    HIP_TRY(ctx, hipMemsetAsync(pb.count, 0, sizeof(unsigned int), st));
+    hipLaunchKernelGGL(probe_list_kernel, grid, block, 0, st, da, pr);
+    HIP_TRY(ctx, hipGetLastError());
+    if (!ch.probe_counted) break;
+    unsigned int n = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&n, pb.count, sizeof n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    ++ctx->n_dev_waits;
+    if ((uint64_t)n <= cap) break;
+    if (attempt) return fail(ctx, LENTIL_ERR_NOMEM, "occlusion probes: the list outgrew its buffers twice");
+    if ((rc = probe_buf_reserve(ctx, pb, (uint64_t)n + (uint64_t)n / 4 + 4096, false))) return rc;
+    cap = ch.probe_cap_now = pb.cap;
+  }
+  if ((rc = probe_call_device(ctx, pb, cap, st))) return rc;
+  hipLaunchKernelGGL(probe_apply_device_kernel, grid, block, 0, st, da, pr, pb.occ);
+  HIP_TRY(ctx, hipGetLastError());
+  return LENTIL_OK;
+}
+
 // One round's probes, between its solves (and stragglers) and its accept, on the round's stream: list, callback, apply.
-static int probe_round(lentil_hip_ctx *ctx, const DrawArgs &da, hipStream_t st) {
-  if (!ctx->probe_fn) return LENTIL_OK;
+static int probe_round(lentil_hip_ctx *ctx, int ci, const DrawArgs &da, hipStream_t st) {
+  if (!probing(ctx)) return LENTIL_OK;
+  lentil_hip_ctx::Chunk &ch = ctx->chunks[ci];
+  if (ctx->probe_dev_fn) return probe_round_device(ctx, ch, da, st);
   ProbeArgs pr{};
   int rc;
   if ((rc = probe_prepare(ctx, pr, st))) return rc;
   const dim3 grid((unsigned)ctx->num_cu * 4u), block(256);
   unsigned int n = 0;
   uint64_t occ = 0;
-  if ((rc = probe_ask(ctx, pr, st, [&](const ProbeArgs &q) { hipLaunchKernelGGL(probe_list_kernel, grid, block, 0, st, da, q); }, &n, &occ))) return rc;
+  if ((rc = probe_ask(ctx, ch.pb, pr, st, [&](const ProbeArgs &q) { hipLaunchKernelGGL(probe_list_kernel, grid, block, 0, st, da, q); }, &n, &occ))) return rc;
   if (occ) {
     hipLaunchKernelGGL(probe_apply_kernel, grid, block, 0, st, da, pr, (uint32_t)n);
     HIP_TRY(ctx, hipGetLastError());
   }
+  return LENTIL_OK;
+}
+
+// The capacity a chunk's lists are made with in this pass, under a device callback: the chunk's result pool's.  A round's list
+// has at most one segment per result slot of the round, and the pool holds any round's results -- sized from the scan's
+// read-back, or, in a pass enqueued blind, from the last pass's figures with prep_items_kernel checking on the device that the
+// real ones fit (DevCounters::fallback otherwise) --, so no round's list can outgrow it, whatever the renderer answers from one
+// pass to the next.  LENTIL_PROBE_DEVICE_CAP caps a blind pass's capacity (tests: the overflow and its redo).
+static int probe_size_chunk(lentil_hip_ctx *ctx, lentil_hip_ctx::Chunk &ch, bool blind) {
+  if (!ctx->probe_dev_fn) return LENTIL_OK;
+  if (ch.probe_counted) { ch.probe_cap_now = ch.pb.cap; return LENTIL_OK; }        // (every list is counted first and the buffers grown to it)
+  uint64_t need = ch.pool_cap;
+  if (blind && ctx->probe_dev_cap && need > ctx->probe_dev_cap) need = ctx->probe_dev_cap;
+  const int rc = probe_buf_reserve(ctx, ch.pb, need, false);
+  if (rc) return rc;
+  ch.probe_cap_now = blind && ctx->probe_dev_cap && ch.pb.cap > ctx->probe_dev_cap ? ctx->probe_dev_cap : ch.pb.cap;
   return LENTIL_OK;
 }
 
@@ -1718,7 +1894,7 @@ static int finish_rounds(lentil_hip_ctx *ctx, int ci, DrawArgs &da, int first_ro
     if (n_act == 0) break;
     da.parity = round & 1; da.round = round;
     launch_solve(ctx, da, ch.stream, 256);
-    { const int rcp = probe_round(ctx, da, ch.stream); if (rcp) return rcp; }
+    { const int rcp = probe_round(ctx, ci, da, ch.stream); if (rcp) return rcp; }
     hipLaunchKernelGGL(accept_kernel<0>, dim3(n_act < 512u ? n_act : 512u), dim3(256), 0, ch.stream, da);
     HIP_TRY(ctx, hipGetLastError());
   }
@@ -1778,7 +1954,7 @@ static int launch_chunk_rounds(lentil_hip_ctx *ctx, int ci, DrawArgs &da, uint64
     // full grid it reaches the CUs first and the solve kernel's blocks are placed around it -- the slow start that
     // costs that kernel 10 % for its whole life (see above).  A quarter block per CU trickles along beside the solve
     // instead and is done before it (heavy regime: 119.2 -> 114.5 ms per frame).
-    { const int rcp = probe_round(ctx, da, ch.stream); if (rcp) return rcp; }      // (occlusion probes: the host answers between the solves and the accept)
+    { const int rcp = probe_round(ctx, ci, da, ch.stream); if (rcp) return rcp; }      // (occlusion probes: the host answers between the solves and the accept)
     unsigned ab = accept_blocks;
     if (round == 0 && heavy && ci + 1 < ctx->n_chunks) {
       const unsigned lim = (unsigned)ctx->num_cu / 4u > 0u ? (unsigned)ctx->num_cu / 4u : 1u;
@@ -1822,6 +1998,7 @@ static int enqueue_chunk_draws_blind(lentil_hip_ctx *ctx, int ci, DrawArgs &da, 
   if (units > ctx->max_pool_units || items == 0) return LENTIL_OK;
   int rc;
   if ((rc = size_chunk_buffers(ctx, ch, items, units))) return rc;
+  if ((rc = probe_size_chunk(ctx, ch, true))) return rc;
   bind_chunk_buffers(ch, da);
   const bool po = ctx->P.cameraType == LENTIL_POLYNOMIAL_OPTICS;
   da.ctr = ctx->d_ctr + ci;
@@ -1878,6 +2055,7 @@ static int enqueue_chunk_draws(lentil_hip_ctx *ctx, int ci, DrawArgs &da, int bl
     uint64_t units_h = chunk_units(P, nch, c.sum_samples + c.sum_samples / 4 + 65536, items_h);
     if (units_h > ctx->max_pool_units) { units_h = units; items_h = n_items; }
     if ((rc = size_chunk_buffers(ctx, ch, items_h, units_h))) return rc;
+    if ((rc = probe_size_chunk(ctx, ch, false))) return rc;
     bind_chunk_buffers(ch, da);
     da.work = ctx->d_work + ch.v_begin;
     da.n_items = n_items;
@@ -1891,6 +2069,7 @@ static int enqueue_chunk_draws(lentil_hip_ctx *ctx, int ci, DrawArgs &da, int bl
   for (uint64_t i0 = 0; i0 < n_items; i0 += batch_items) {
     const uint64_t ni = n_items - i0 < batch_items ? n_items - i0 : batch_items;
     if ((rc = size_chunk_buffers(ctx, ch, ni, ni * per_item))) return rc;
+    if ((rc = probe_size_chunk(ctx, ch, false))) return rc;
     bind_chunk_buffers(ch, da);
     // fresh queues for this batch
     HIP_TRY(ctx, hipMemsetAsync((char *)dctr + offsetof(DevCounters, n_tasks), 0,
@@ -1901,7 +2080,7 @@ static int enqueue_chunk_draws(lentil_hip_ctx *ctx, int ci, DrawArgs &da, int bl
     hipLaunchKernelGGL(prep_items_kernel, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, ch.stream, da);
     launch_solve(ctx, da, ch.stream, (unsigned)max_blocks);
     if (i0 == 0) HIP_TRY(ctx, hipStreamWaitEvent(ch.stream, ctx->scans_done, 0));   // see launch_chunk_rounds
-    if ((rc = probe_round(ctx, da, ch.stream))) return rc;
+    if ((rc = probe_round(ctx, ci, da, ch.stream))) return rc;
     hipLaunchKernelGGL(accept_kernel<0>, dim3((unsigned)ctx->num_cu * 2), dim3(256), 0, ch.stream, da);
     HIP_TRY(ctx, hipGetLastError());
     int rounds = 0;
@@ -2417,7 +2596,7 @@ static int streamed_finish(lentil_hip_ctx *ctx, StreamTail &t, const DevCounters
   if (c.fallback || c.stuck) {
     {
       // what made the pass give up, kept for lentil_hip_last_redo_note(): `fallback` bits 1 items, 2 result pool, 4 task queue,
-      // 8 a wave's pending flushes, 16 range queue, 32 the blind preparation's bounds; `stuck` = (ticket << 2) | who waited (1 a
+      // 8 a wave's pending flushes, 16 range queue, 32 the blind preparation's bounds (64, chunked passes only: a list of occlusion probes); `stuck` = (ticket << 2) | who waited (1 a
       // publisher, 2 a resident solve wave, 3 a straggler wave)
       char note[768];
       snprintf(note, sizeof note,
@@ -2602,7 +2781,7 @@ static int redistribute_streamed(lentil_hip_ctx *ctx, bool *streamed, bool *defe
     return LENTIL_OK;
   if (ctx->V.n > 0xFFFFFFF0ull) return LENTIL_OK;
   if (no_tries(P)) return LENTIL_OK;         // (vignetting_retries < 0: a scan and a count, enqueue_chunk_draws)
-  if (ctx->probe_fn) return LENTIL_OK;      // (occlusion probes: the host answers between a round's solves and its accept -- the round-by-round form)
+  if (probing(ctx)) return LENTIL_OK;      // (occlusion probes, host or device callback: answered between a round's solves and its accept -- the round-by-round form)
   // Only into a frame that has been cleared since its last pass (every caller's order: clear, redistribute, resolve): a
   // streamed pass whose waves give up waiting after draws have been accepted is recovered by wiping the frame and running
   // the pass again, which must not cost an earlier pass's sums.  A second pass into the same frame takes the chunked form,
@@ -3238,33 +3417,74 @@ static int tl_chroma_probe(lentil_hip_ctx *ctx, const TlChromaArgs &ta, uint64_t
   TlChromaProbe b{};
   b.bound = ctx->d_tlc_bound; b.probed = ctx->d_tlc_probed;
   HIP_TRY(ctx, hipMemsetAsync(ctx->d_tlc_probed, 0, (size_t)ta.n_items * sizeof(uint32_t), st));
+  ProbeBuf &pb = ctx->tlc_pb;
+  // the slots of `occ` more occluded attempts fit behind those kept so far (which move into a larger buffer)
+  auto reserve_kept = [&](uint64_t occ) -> int {
+    if (ctx->tlc_occ_n + occ <= ctx->tlc_occ_cap) return LENTIL_OK;
+    const uint64_t cap = ctx->tlc_occ_n + occ + (ctx->tlc_occ_n + occ) / 2 + 4096;
+    uint32_t *grown = nullptr;
+    HIP_TRY(ctx, hipMalloc(&grown, cap * sizeof(uint32_t)));
+    hipError_t e = hipSuccess;
+    if (ctx->tlc_occ_n) e = hipMemcpyAsync(grown, ctx->d_tlc_occ, ctx->tlc_occ_n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { (void)hipFree(grown); HIP_TRY(ctx, e); }
+    (void)hipFree(ctx->d_tlc_occ);
+    ctx->d_tlc_occ = grown;
+    ctx->tlc_occ_cap = cap;
+    return LENTIL_OK;
+  };
   for (;;) {
     hipLaunchKernelGGL(tl_chroma_probe_bound_kernel, items_grid, block, 0, st, ta, b);
     HIP_TRY(ctx, hipGetLastError());
     unsigned int n = 0;
     uint64_t occ = 0;
-    if ((rc = probe_ask(ctx, pr, st, [&](const ProbeArgs &q) { hipLaunchKernelGGL(tl_chroma_probe_list_kernel, items_grid, block, 0, st, ta, b, q); },
-                        &n, &occ)))
-      return rc;
-    if (!n) break;
-    if (occ) {
-      if (ctx->tlc_occ_n + occ > ctx->tlc_occ_cap) {      // (the slots kept so far move into the larger buffer)
-        const uint64_t cap = ctx->tlc_occ_n + occ + (ctx->tlc_occ_n + occ) / 2 + 4096;
-        uint32_t *grown = nullptr;
-        HIP_TRY(ctx, hipMalloc(&grown, cap * sizeof(uint32_t)));
-        hipError_t e = hipSuccess;
-        if (ctx->tlc_occ_n) e = hipMemcpyAsync(grown, ctx->d_tlc_occ, ctx->tlc_occ_n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) { (void)hipFree(grown); HIP_TRY(ctx, e); }
-        (void)hipFree(ctx->d_tlc_occ);
-        ctx->d_tlc_occ = grown;
-        ctx->tlc_occ_cap = cap;
+    if (ctx->probe_dev_fn) {
+      // Device callback: the loop needs the list's length and the occluded count on the host -- two 4-byte read-backs per turn --,
+      // but the segments stay where they are, the renderer answers them there, and the apply kernel counts what it failed.
+      for (int attempt = 0;; ++attempt) {
+        if ((rc = probe_buf_reserve(ctx, pb, pb.cap ? pb.cap : kProbeFirstCap, false))) return rc;
+        probe_bind(pb, pb.cap, pr);
+        HIP_TRY(ctx, hipMemsetAsync(pb.count, 0, sizeof(unsigned int), st));
+        hipLaunchKernelGGL(tl_chroma_probe_list_kernel, items_grid, block, 0, st, ta, b, pr);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(&n, pb.count, sizeof n, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        ++ctx->n_dev_waits;
+        if ((uint64_t)n <= pb.cap) break;
+        ++ctx->n_dev_overflows;
+        if (attempt) return fail(ctx, LENTIL_ERR_NOMEM, "occlusion probes: the list outgrew its buffers twice");
+        if ((rc = probe_buf_reserve(ctx, pb, (uint64_t)n + (uint64_t)n / 4 + 4096, false))) return rc;
       }
-      HIP_TRY(ctx, hipMemsetAsync(ctx->d_probe_count, 0, sizeof(unsigned int), st));
+      if (!n) break;
+      if (n > ctx->dev_longest) ctx->dev_longest = n;
+      if (pb.occ_dirty) { HIP_TRY(ctx, hipMemsetAsync(pb.occ, 0, pb.cap, st)); pb.occ_dirty = false; }
+      if ((rc = probe_call_device(ctx, pb, pb.cap, st))) return rc;
+      if ((rc = reserve_kept(n))) return rc;        // (at most all of them)
+      HIP_TRY(ctx, hipMemsetAsync(pb.count, 0, sizeof(unsigned int), st));       // (behind the callback's work, which reads the length there)
       hipLaunchKernelGGL(tl_chroma_probe_apply_kernel, grid, block, 0, st, ta.res, (const uint32_t *)pr.idx, pr.occluded, (uint32_t)n,
-                         ctx->d_tlc_occ + ctx->tlc_occ_n, ctx->d_probe_count);
+                         ctx->d_tlc_occ + ctx->tlc_occ_n, pb.count);
       HIP_TRY(ctx, hipGetLastError());
+      HIP_TRY(ctx, hipMemsetAsync(pb.occ, 0, n, st));        // (the next list's answers start from zero)
+      unsigned int kept = 0;
+      HIP_TRY(ctx, hipMemcpyAsync(&kept, pb.count, sizeof kept, hipMemcpyDeviceToHost, st));
+      HIP_TRY(ctx, hipStreamSynchronize(st));
+      ++ctx->n_dev_waits;
+      occ = kept;
+      ctx->n_probes += n; ctx->n_probes_occluded += occ;
       ctx->tlc_occ_n += occ;
+    } else {
+      if ((rc = probe_ask(ctx, pb, pr, st, [&](const ProbeArgs &q) { hipLaunchKernelGGL(tl_chroma_probe_list_kernel, items_grid, block, 0, st, ta, b, q); },
+                          &n, &occ)))
+        return rc;
+      if (!n) break;
+      if (occ) {
+        if ((rc = reserve_kept(occ))) return rc;
+        HIP_TRY(ctx, hipMemsetAsync(pb.count, 0, sizeof(unsigned int), st));
+        hipLaunchKernelGGL(tl_chroma_probe_apply_kernel, grid, block, 0, st, ta.res, (const uint32_t *)pr.idx, pr.occluded, (uint32_t)n,
+                           ctx->d_tlc_occ + ctx->tlc_occ_n, pb.count);
+        HIP_TRY(ctx, hipGetLastError());
+        ctx->tlc_occ_n += occ;
+      }
     }
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tlc_probed, ctx->d_tlc_bound, (size_t)ta.n_items * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
     if (!occ) break;       // (nothing failed: the bounds stand)
@@ -3373,7 +3593,7 @@ static int redistribute_tl_chroma(lentil_hip_ctx *ctx) {
     hipLaunchKernelGGL(tl_chroma_solve_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, ta);
     HIP_TRY(ctx, hipGetLastError());
   }
-  if (ctx->probe_fn && (rc = tl_chroma_probe(ctx, ta, slots, ctx->pass_rerun))) return rc;      // (this rank's own items; a rank without any goes on to the collective)
+  if (probing(ctx) && (rc = tl_chroma_probe(ctx, ta, slots, ctx->pass_rerun))) return rc;      // (this rank's own items; a rank without any goes on to the collective)
   if (!ctx->comm) {
     hipLaunchKernelGGL(tl_chroma_walk_kernel, dim3(1), dim3(256), 0, ctx->stream, ta);
     HIP_TRY(ctx, hipGetLastError());
@@ -3782,7 +4002,7 @@ static int redistribute_pass(lentil_hip_ctx *ctx) {
   for (uint32_t k = 1; k < ctx->F.n_aovs; ++k)
     if (ctx->V.n && !ctx->V.extra[k - 1] && !(ctx->F.debug_mask & (1u << k)))
       return fail(ctx, LENTIL_ERR_INVALID, "an extra AOV column is null");
-  if (ctx->probe_fn && P.cameraType == LENTIL_POLYNOMIAL_OPTICS && P.abb_chromatic != 0.0f)
+  if (probing(ctx) && P.cameraType == LENTIL_POLYNOMIAL_OPTICS && P.abb_chromatic != 0.0f)
     return fail(ctx, LENTIL_ERR_UNSUPPORTED, "occlusion probes with polynomial optics and abb_chromatic != 0 (three wavelengths per attempt, "
                                              "src/lentil_filter.cpp:248-299): not built; the thin lens is probed with any abb_chromatic");
   if (ctx->F.debug_mask && ctx->closest_deferred && !ctx->comm)
@@ -3807,7 +4027,7 @@ static int redistribute_pass(lentil_hip_ctx *ctx) {
   ctx->h_ctr_valid = false;
   ctx->last_blind = ctx->last_fallback = 0;
   ctx->last_streamed = 0;
-  for (auto &ch : ctx->chunks) ch.heavy_pending = false;
+  for (auto &ch : ctx->chunks) { ch.heavy_pending = false; ch.probe_counted = false; }
   ctx->last_scan_launches = 0;
   bool streamed = false, deferred = false;
   const bool tl_chroma = P.cameraType == LENTIL_THINLENS && P.abb_chromatic > 0.0f;
@@ -3917,6 +4137,25 @@ static int redistribute_pass(lentil_hip_ctx *ctx) {
       const DevCounters c = ctx->h_ctr[(size_t)ci];
       if (c.fallback) {
         ctx->h_ctr_valid = false;
+        if (c.fallback & 64ull) {
+          // a list of occlusion probes outgrew the chunk's buffers (probe_apply_device_kernel): in the first round nothing of the
+          // chunk has been accepted, and its draws are redone with every list counted on the host first
+          char note[256];
+          snprintf(note, sizeof note, "chunk %d: a list of %u occlusion probes did not fit its buffers (%llu): the chunk's draws were redone with counted lists",
+                   ci, c.probe_max, (unsigned long long)ch.probe_cap_now);
+          ctx->redo_note = note;
+          if (c.rounds_used) {
+            // (in a later round the chunk has accepted draws: not redone.  Lists are made with the result pool's capacity, which
+            // bounds every round's; only LENTIL_PROBE_DEVICE_CAP brings a pass here.  The next pass is sized from its scans.)
+            probe_abandon(ctx);
+            return fail(ctx, LENTIL_ERR_NOMEM, "occlusion probes: a list of " + std::to_string(c.probe_max) + " segments in a later round did not fit buffers capped at " +
+                                                   std::to_string(ch.probe_cap_now) + ": the frame is incomplete");
+          }
+          ch.probe_counted = true;
+          ch.pb.occ_dirty = true;
+          ctx->n_dev_overflows += c.probe_over;       // (the redo's counters start from zero below)
+          HIP_TRY(ctx, hipMemsetAsync((char *)(ctx->d_ctr + ci) + offsetof(DevCounters, probe_n), 0, offsetof(DevCounters, reserved_) - offsetof(DevCounters, probe_n), ch.stream));
+        }
         ++ctx->last_fallback;
         // the empty rounds left their queue cursors behind: fresh queues, then the chunk again with exact sizes
         HIP_TRY(ctx, hipMemsetAsync((char *)(ctx->d_ctr + ci) + offsetof(DevCounters, n_tasks), 0,
@@ -4005,6 +4244,15 @@ static int pass_finish(lentil_hip_ctx *ctx) {
       HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
       ctx->h_ctr.assign(ctx->h_ctr_pinned, ctx->h_ctr_pinned + C);
       ctx->h_ctr_valid = true;
+    }
+    if (ctx->probe_dev_fn) {
+      // occlusion probes under a device callback: what the apply kernels counted in this pass
+      for (size_t ci = 0; ci < ctx->h_ctr.size(); ++ci) {
+        const DevCounters &k = ctx->h_ctr[ci];
+        ctx->n_probes += k.probe_n; ctx->n_probes_occluded += k.probe_occ; ctx->n_dev_overflows += k.probe_over;
+        if (k.probe_max > ctx->dev_longest) ctx->dev_longest = k.probe_max;
+        if (k.fallback & 64ull) { probe_abandon(ctx); return fail(ctx, LENTIL_ERR_NOMEM, "occlusion probes: a list of " + std::to_string(k.probe_max) + " segments did not fit its buffers: the frame is incomplete"); }
+      }
     }
     unsigned long long dropped = 0;
     for (const DevCounters &k : ctx->h_ctr) dropped += k.overflow;

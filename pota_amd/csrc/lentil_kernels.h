@@ -51,9 +51,13 @@ struct DevCounters {
   unsigned int stuck, tile_next;       // a wave gave up waiting for its queue slot (kStuckTicks): the pass is void; scan_dma_kernel's tile cursor
   // a candidate for a closest-filtered AOV came with |Z| == 0 or NaN (closest_key_of): the pass is refused, see there
   unsigned int degenerate_depth, pad_;
+  // occlusion probes under a device callback (probe_apply_device_kernel): segments listed and of them occluded in this pass,
+  // the longest list, lists that did not fit their buffers
+  unsigned long long probe_n, probe_occ;
+  unsigned int probe_max, probe_over;
   // (unused: keeps the words below at the offsets they have always had -- which of the atomically updated counters share a
   // cache line moves with them)
-  unsigned int reserved_[8];
+  unsigned int reserved_[2];
   // diagnostics of a stall (lentil_hip_last_redo_note): accept blocks that have begun, per round parity; what the wave that
   // gave up first saw -- round, parity, the queue's n_tasks, accept_done[0], accept_started[0], its slot's tag word, block
   unsigned int accept_started[2];
@@ -4162,6 +4166,60 @@ __global__ __launch_bounds__(256) void probe_apply_kernel(DrawArgs a, ProbeArgs 
   const uint32_t stride = gridDim.x * blockDim.x;
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
     if (pr.occluded[i]) res[pr.idx[i]] = kCodeFail;
+}
+
+// Under a device callback (lentil_hip_set_occlusion_probe_device) nobody on the host knows the list's length or whether anything
+// is occluded: this kernel always follows the callback's work, takes n from the list's counter, fails the occluded tries and
+// keeps the pass's totals (DevCounters::probe_*; occluded entries by wave ballot, one atomic per wave).  It leaves the answer
+// bytes zero, as the next list's callback is promised them.  A list that outgrew its buffers (*count > cap: probe_list_kernel
+// wrote the first cap segments only) raises DevCounters::fallback bit 64 instead and applies nothing: the round's accept and
+// every later one of the chunk then accept nothing, and the host redoes the chunk's draws with counted lists.
+__global__ __launch_bounds__(256) void probe_apply_device_kernel(DrawArgs a, ProbeArgs pr, uint8_t *answers) {
+  DevCounters *c = a.ctr;
+  if (c->fallback) return;
+  const uint32_t n = *pr.count;
+  if (n > pr.cap) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      atomicOr(&c->fallback, 64ull);
+      atomicAdd(&c->probe_over, 1u);
+      atomicMax(&c->probe_max, n);
+    }
+    return;
+  }
+  uint32_t *res = a.pool[(uint32_t)a.parity];
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  const uint64_t n_up = ((uint64_t)n + 63u) & ~63ull;       // (whole waves go round the loop together)
+  uint32_t wave_occ = 0;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_up; i += stride) {
+    const bool occ = i < n && answers[i] != 0;
+    if (occ) { res[pr.idx[i]] = kCodeFail; answers[i] = 0; }
+    wave_occ += (uint32_t)__builtin_popcountll(__ballot(occ));
+  }
+  if ((threadIdx.x & 63u) == 0u && wave_occ) atomicAdd(&c->probe_occ, (unsigned long long)wave_occ);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    atomicAdd(&c->probe_n, (unsigned long long)n);
+    atomicMax(&c->probe_max, n);
+  }
+}
+
+// lentil_hip_test_sphere_occluder_device: one lane per segment of the list, whose length is read from the device.  Does the
+// segment come within r of the sphere's centre?  fp32 in, every operation in fp64 and in the order of the tests' CPU occluder.
+__global__ __launch_bounds__(256) void test_sphere_occluder_kernel(float cx, float cy, float cz, float r, uint32_t capacity, const uint32_t *d_n,
+                                                                   const lentil_probe_segment *seg, uint8_t *occluded) {
+  const uint32_t n_raw = *d_n;
+  const uint32_t n = n_raw < capacity ? n_raw : capacity;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const lentil_probe_segment s = seg[i];
+    const double o[3] = {s.origin[0], s.origin[1], s.origin[2]};
+    const double d[3] = {s.target[0] - o[0], s.target[1] - o[1], s.target[2] - o[2]};
+    const double cc[3] = {cx - o[0], cy - o[1], cz - o[2]};
+    const double dd = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+    double t = dd > 0.0 ? (cc[0] * d[0] + cc[1] * d[1] + cc[2] * d[2]) / dd : 0.0;
+    t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
+    const double q[3] = {cc[0] - t * d[0], cc[1] - t * d[1], cc[2] - t * d[2]};
+    if ((q[0] * q[0] + q[1] * q[1] + q[2] * q[2]) < (double)r * (double)r) occluded[i] = 1;
+  }
 }
 
 // ---------------------------------------------------------------------------------------
