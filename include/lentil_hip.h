@@ -743,6 +743,64 @@ int lentil_hip_camera_rays(lentil_hip_ctx *ctx, const lentil_camera_ray_batch *b
  * rate has been measured against the interpreter's).  lentil_hip_set_lens_mode(ctx, 1) forces path 1 too. */
 int lentil_hip_camera_rays_path(lentil_hip_ctx *ctx, int *path);
 
+/* --- scene points traced backward through the lens in batches --------------------------
+ * The backward counterpart of lentil_hip_camera_rays: for a camera-space point and a draw number, where on the sensor a draw
+ * of the redistribution pass puts it -- for a renderer that keeps its own film (another reconstruction filter, a tiled or
+ * spectral film, deep output, light-tracing connections) and wants the library's lens, not its frame.  Uses the context's
+ * parameters, the table of set_lens (polynomial optics) and the tables of set_bokeh (bokeh_enable_image); needs no frame and
+ * no visits, touches no accumulator, and does not consult an occlusion probe.
+ * Queries: n_points * attempts of them, point-major: query q is point q / attempts, attempt number
+ * first_attempt[point] + q % attempts (the reference's total_samples_taken of that draw).  The draws are seeded as the pass
+ * seeds them, tea<8>(px * py + px, attempt + tries) with (px, py) the point's source pixel, so query (point, m) is what the
+ * pass computes for the m-th attempt of a visit at that point and pixel.
+ *   Polynomial optics: target = -cs * 10 in fp64 (src/lentil_filter.cpp:271), Camera::trace_ray_bw_po with
+ *     vignetting_retries + 1 tries at seeds attempt + tries (src/lentil.h:573-661), then the sensor -> pixel mapping of
+ *     src/lentil_filter.cpp:276-290; operation for operation, fp64.  vignetting_retries < 0: no try is made, every query is
+ *     LENTIL_POINT_VIGNETTED.  lambda (micrometres) is the wavelength the polynomials are evaluated at; 0: params.lambda_bw.
+ *   Thin lens: the draw of src/lentil_filter.cpp:311-434 at the unshifted focus distance -- what the pass computes for
+ *     abb_chromatic == 0.  With abb_chromatic > 0 the points are projected the same way: the per-channel shift of the focus
+ *     plane follows the pass's xor128 order, which a batch does not have, and is NOT offered.  One try per attempt
+ *     (out_tries 0); lambda is ignored.
+ *   out_pixel   the linear pixel ix + iy * xres, or LENTIL_POINT_VIGNETTED (every try failed in the lens), or
+ *               LENTIL_POINT_OUTSIDE (through the lens, outside the frame; a NaN coordinate counts as outside)
+ *   out_xy      optional: the continuous pixel coordinates before floor (pixel0, pixel1: fp64 for polynomial optics, the thin
+ *               lens's fp32 values widened) -- also for LENTIL_POINT_OUTSIDE, so a caller can clip to a window of its own; two
+ *               quiet NaNs for LENTIL_POINT_VIGNETTED
+ *   out_sensor  optional, polynomial optics: sensor x, y (mm) after sensor_shift; NaNs for LENTIL_POINT_VIGNETTED and for
+ *               the thin lens
+ *   out_tries   optional: the vignetted tries before the one that got through (all of them for LENTIL_POINT_VIGNETTED)
+ * flags: LENTIL_POINTS_DEVICE_POINTERS: every pointer of the batch is device memory of the context's GPU; the call enqueues
+ * its kernel on lentil_hip_stream(ctx) and returns (order it with lentil_hip_sync or the stream).  Without it they are host
+ * memory and the call returns when the outputs are filled.  A batch's results do not depend on how it is split into calls,
+ * by points or by attempts.
+ * The call observes the context (a pass in flight is finished first) and takes no part in the streamed passes' turns.
+ * LENTIL_ERR_INVALID: no parameters, polynomial optics without a lens, bokeh_enable_image without tables, cs / pixel /
+ * out_pixel NULL with n_points > 0, attempts == 0, n_points * attempts >= 2^32, a point whose first_attempt + attempts +
+ * max(vignetting_retries, 0) does not fit 32 bits (checked for host pointers; with device pointers it is the caller's duty:
+ * the seeds wrap).  n_points == 0 launches nothing. */
+#define LENTIL_POINTS_DEVICE_POINTERS 1u
+#define LENTIL_POINT_VIGNETTED 0xFFFFFFFFu   /* every try of the attempt failed in the lens */
+#define LENTIL_POINT_OUTSIDE   0xFFFFFFFEu   /* got through the lens, landed outside the frame (or NaN) */
+typedef struct lentil_point_batch {
+  uint64_t n_points;
+  uint32_t attempts;             /* K >= 1: attempts per point; query q = point q / K, attempt first_attempt[point] + q % K */
+  uint32_t flags;                /* LENTIL_POINTS_DEVICE_POINTERS: every pointer is device memory of the context's GPU */
+  const float *cs;               /* [n_points][3] camera space, cm, z < 0 in front: the reference's camera_space_sample_position */
+  const uint32_t *pixel;         /* [n_points] px | py << 16: the source pixel whose seed (px * py + px) the draws use */
+  const uint32_t *first_attempt; /* optional [n_points]; NULL: 0.  attempt = the reference's total_samples_taken */
+  double lambda;                 /* polynomial optics, micrometres; 0: params.lambda_bw */
+  uint32_t *out_pixel;           /* [n_points * K] linear pixel (ix + iy * xres) or one of the two codes */
+  double *out_xy;                /* optional [n_points * K][2]: continuous pixel coordinates before floor */
+  double *out_sensor;            /* optional, polynomial optics only: sensor x, y (mm) after sensor_shift */
+  int32_t *out_tries;            /* optional: vignetted tries before the one that got through (thin lens: 0) */
+} lentil_point_batch;
+int lentil_hip_trace_points(lentil_hip_ctx *ctx, const lentil_point_batch *batch);
+/* What the last lentil_hip_trace_points call of this context ran: *path 0 the thin lens (or no call yet), 1 the table
+ * interpreter, 2 the straight-line kernel of a compiled-in lens -- the default for the shipped lenses, the polynomials the
+ * passes run for them by default too.  A table compiled at run time (lentil_hip_lens_jit_status) is served by the
+ * interpreter; lentil_hip_set_lens_mode(ctx, 1) forces the interpreter.  The results are the same bit for bit. */
+int lentil_hip_trace_points_path(lentil_hip_ctx *ctx, int *path);
+
 /* --- single-function device tests (parity of the optics primitives) -----------------
  * Runs n independent evaluations on the GPU; host pointers in/out.
  * lt_sample_aperture: Camera::lens_lt_sample_aperture (src/lentil.h:1296-1313) for

@@ -11,6 +11,9 @@ OK, ERR_INVALID, ERR_HIP, ERR_UNSUPPORTED, ERR_NOMEM = 0, -1, -2, -3, -4
 RAYS_DEVICE_POINTERS, RAYS_NO_DIFFERENTIALS = 1, 2
 RAY_IN_FLOATS, RAY_OUT_FLOATS = 6, 21
 RAYS_PATH_THIN_LENS, RAYS_PATH_INTERPRETER, RAYS_PATH_COMPILED_IN, RAYS_PATH_RUN_TIME = 0, 1, 2, 3      # lentil_hip_camera_rays_path
+POINTS_DEVICE_POINTERS = 1
+POINT_VIGNETTED, POINT_OUTSIDE = 0xFFFFFFFF, 0xFFFFFFFE                                                # lentil_point_batch.out_pixel
+POINTS_PATH_THIN_LENS, POINTS_PATH_INTERPRETER, POINTS_PATH_COMPILED_IN = 0, 1, 2                     # lentil_hip_trace_points_path
 
 
 class Params(C.Structure):
@@ -111,3 +114,10 @@ class CameraRayBatch(C.Structure):
     _fields_ = [("n", C.c_uint64), ("first_ray", C.c_uint64),
                 ("inp", C.c_void_p), ("out", C.c_void_p), ("tries", C.c_void_p),
                 ("lam", C.c_double), ("exposure", C.c_float), ("rng_seed", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class PointBatch(C.Structure):
+    _fields_ = [("n_points", C.c_uint64), ("attempts", C.c_uint32), ("flags", C.c_uint32),
+                ("cs", C.c_void_p), ("pixel", C.c_void_p), ("first_attempt", C.c_void_p),
+                ("lam", C.c_double),
+                ("out_pixel", C.c_void_p), ("out_xy", C.c_void_p), ("out_sensor", C.c_void_p), ("out_tries", C.c_void_p)]

@@ -30,6 +30,7 @@ EXPORTS = [
     "lentil_hip_test_trace_bw_po", "lentil_hip_test_aperture_sample", "lentil_hip_debug_scan_bands", "lentil_hip_debug_scan_lean_counts", "lentil_hip_debug_last_scan",
     "lentil_hip_lens_is_compiled", "lentil_hip_set_lens_mode",
     "lentil_hip_focus_search", "lentil_hip_test_y0_intersection", "lentil_hip_camera_rays", "lentil_hip_camera_rays_path",
+    "lentil_hip_trace_points", "lentil_hip_trace_points_path",
     "lentil_hip_set_xor128_state", "lentil_hip_get_xor128_state", "lentil_hip_tl_chroma_stats", "lentil_hip_test_xor128_jump",
     "lentil_hip_host_alloc", "lentil_hip_host_free", "lentil_hip_visits_begin", "lentil_hip_visits_append",
     "lentil_hip_visits_wait", "lentil_hip_visits_end",
@@ -186,6 +187,8 @@ def load_library():
         "lentil_hip_focus_search": (i, [vp, C.c_double, C.c_double, C.POINTER(C.c_double)]),
         "lentil_hip_camera_rays": (i, [vp, C.POINTER(_abi.CameraRayBatch)]),
         "lentil_hip_camera_rays_path": (i, [vp, C.POINTER(C.c_int)]),
+        "lentil_hip_trace_points": (i, [vp, C.POINTER(_abi.PointBatch)]),
+        "lentil_hip_trace_points_path": (i, [vp, C.POINTER(C.c_int)]),
         "lentil_hip_set_xor128_state": (i, [vp, C.POINTER(C.c_uint32)]),
         "lentil_hip_get_xor128_state": (i, [vp, C.POINTER(C.c_uint32)]),
         "lentil_hip_tl_chroma_stats": (i, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
@@ -495,6 +498,76 @@ class Context:
         LENTIL_RAYS_COMPILED=1 in the environment when the context is created; the default is the interpreter."""
         path = C.c_int()
         self._chk(self.lib.lentil_hip_camera_rays_path(self.h, C.byref(path)))
+        return path.value
+
+    def trace_points(self, cs, pixel, attempts, first_attempt=None, lam=0.0, want_xy=True, want_sensor=False, want_tries=False):
+        """Scene points traced backward through the lens in a batch (lentil_hip_trace_points): for every point (cs fp32 [n, 3],
+        camera space, cm; pixel uint32 [n] = px | py << 16, the source pixel that seeds the draws) and every attempt
+        first_attempt[point] ... + attempts - 1 (uint32 [n]; None: from 0), where a draw of the pass puts it.
+        -> a dict: "pixel" uint32 [n, attempts] (the linear pixel, _abi.POINT_VIGNETTED or _abi.POINT_OUTSIDE; a torch tensor holds the
+        same bits as int32: the two codes read -1 and -2) and, as asked for,
+        "xy" fp64 [n, attempts, 2] (continuous pixel coordinates, NaN where vignetted), "sensor" fp64 [n, attempts, 2]
+        (polynomial optics: mm on the sensor) and "tries" int32 [n, attempts].  lam: micrometres, 0 = params.lambda_bw.
+        numpy in: host pointers, numpy out, complete on return.  Contiguous torch tensors on this context's device: device
+        pointers, torch tensors out, enqueued on the context's stream (stream()) without waiting; the caller orders both ends as
+        for camera_rays, and with device pointers the seeds first_attempt + attempts + vignetting_retries must fit 32 bits."""
+        b = _abi.PointBatch()
+        attempts = int(attempts)
+        if isinstance(cs, np.ndarray) or not hasattr(cs, "data_ptr"):
+            a = np.ascontiguousarray(cs, np.float32)
+            if a.ndim != 2 or a.shape[1] != 3:
+                raise ValueError("trace_points: cs must be [n, 3]")
+            n = a.shape[0]
+            px = np.ascontiguousarray(pixel, np.uint32)
+            fa = None if first_attempt is None else np.ascontiguousarray(first_attempt, np.uint32)
+            if px.shape != (n,) or (fa is not None and fa.shape != (n,)):
+                raise ValueError("trace_points: pixel and first_attempt must be [n]")
+            k = max(attempts, 0)
+            out = {"pixel": np.empty((n, k), np.uint32)}
+            if want_xy:
+                out["xy"] = np.empty((n, k, 2), np.float64)
+            if want_sensor:
+                out["sensor"] = np.empty((n, k, 2), np.float64)
+            if want_tries:
+                out["tries"] = np.empty((n, k), np.int32)
+            ptr = lambda t: None if t is None else t.ctypes.data      # noqa: E731
+            flags = 0
+        else:
+            import torch
+            if cs.dtype != torch.float32 or cs.dim() != 2 or cs.shape[1] != 3:
+                raise ValueError("trace_points: cs must be a float32 [n, 3] tensor")
+            n = cs.shape[0]
+            a, px, fa = cs, pixel, first_attempt
+            for name, t in (("cs", a), ("pixel", px), ("first_attempt", fa)):
+                if t is None:
+                    continue
+                if not t.is_cuda or t.device.index != self.device:
+                    raise ValueError("trace_points: %s is on %s, the context on GPU %d" % (name, t.device, self.device))
+                if not t.is_contiguous():      # (a copy here would run on torch's stream, unordered with the context's)
+                    raise ValueError("trace_points: %s must be contiguous" % name)
+                if t is not a and (t.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or tuple(t.shape) != (n,)):
+                    raise ValueError("trace_points: %s must be a 32-bit integer [n] tensor" % name)
+            k = max(attempts, 0)
+            out = {"pixel": torch.empty((n, k), dtype=torch.int32, device=a.device)}      # (the bits of a uint32)
+            if want_xy:
+                out["xy"] = torch.empty((n, k, 2), dtype=torch.float64, device=a.device)
+            if want_sensor:
+                out["sensor"] = torch.empty((n, k, 2), dtype=torch.float64, device=a.device)
+            if want_tries:
+                out["tries"] = torch.empty((n, k), dtype=torch.int32, device=a.device)
+            ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+            flags = _abi.POINTS_DEVICE_POINTERS
+        b.n_points, b.attempts, b.flags, b.lam = n, attempts & 0xFFFFFFFF, flags, float(lam)
+        if n:
+            b.cs, b.pixel, b.first_attempt = ptr(a), ptr(px), ptr(fa)
+            b.out_pixel, b.out_xy, b.out_sensor, b.out_tries = (ptr(out.get(key)) for key in ("pixel", "xy", "sensor", "tries"))
+        self._chk(self.lib.lentil_hip_trace_points(self.h, C.byref(b)))
+        return out
+
+    def trace_points_path(self):
+        """What the last trace_points call ran: one of _abi.POINTS_PATH_* (lentil_hip_trace_points_path)."""
+        path = C.c_int()
+        self._chk(self.lib.lentil_hip_trace_points_path(self.h, C.byref(path)))
         return path.value
 
     def test_y0_intersection(self, sensor_shift, lam):

@@ -597,6 +597,23 @@ LD_DEV bool po_sensor_to_pixel(const lentil_params &P, double sx, double sy, uin
   pixelnumber = (uint32_t)(ix + (iy * (int)P.xres));
   return true;
 }
+// ... and its sibling for lentil_hip_trace_points: the same operations, and the continuous pixel coordinates come out too --
+// whether they lie in the frame or not
+LD_DEV bool po_sensor_to_pixel_xy(const lentil_params &P, double sx, double sy, uint32_t &pixelnumber, double &pixel0,
+                                  double &pixel1) {
+  const double xres = (double)P.xres, yres = (double)P.yres;
+  const double aspect = (double)P.xres_without_region / (double)P.yres_without_region;
+  const double s0 = sx / (P.sensor_width * 0.5);
+  const double s1 = sy / (P.sensor_width * 0.5) * aspect;
+  pixel0 = (((s0 + 1.0) / 2.0) * P.xres_without_region) - P.region_min_x;
+  pixel1 = (((-s1 + 1.0) / 2.0) * P.yres_without_region) - P.region_min_y;
+  if ((pixel0 >= xres) || (pixel0 < 0) || (pixel1 >= yres) || (pixel1 < 0) || (pixel0 != pixel0) ||
+      (pixel1 != pixel1))
+    return false;
+  const int ix = (int)floor(pixel0), iy = (int)floor(pixel1);
+  pixelnumber = (uint32_t)(ix + (iy * (int)P.xres));
+  return true;
+}
 
 // ---------------------------------------------------------------------------------------
 // a3/a4/a5 -- scalar helpers of the visit prologue
@@ -945,6 +962,38 @@ LD_DEV bool thinlens_project(const lentil_params &P, const TlRay &ray, float ima
   const float pixel_y = (float)((((-s1 + 1.0) / 2.0) * P.yres_without_region) - P.region_min_y);
   const double xres = (double)P.xres, yres = (double)P.yres;
   if (((double)pixel_x >= xres) || (pixel_x < 0) || ((double)pixel_y >= yres) || (pixel_y < 0)) return false;
+  const int ix = (int)floorf(pixel_x), iy = (int)floorf(pixel_y);
+  pixelnumber = (uint32_t)(ix + (iy * (int)P.xres));
+  return true;
+}
+
+// ... and its sibling for lentil_hip_trace_points: the same operations, and the continuous pixel coordinates (fp32, as the
+// reference has them) come out too -- whether they lie in the frame or not.  A NaN coordinate, which no comparison of the
+// reference's test catches, counts as outside here.
+LD_DEV bool thinlens_project_xy(const lentil_params &P, const TlRay &ray, float image_dist_focusdist, uint32_t &pixelnumber,
+                                float &pixel_x, float &pixel_y) {
+  const float f = P.focal_length;
+  const float lx = ray.lx, ly = ray.ly, lz = 0.0f, dlx = ray.dlx, dly = ray.dly, dlz = ray.dlz;
+  const float fi = fabsf(image_dist_focusdist / dlz);
+  const float fx = lx + dlx * fi, fy = ly + dly * fi, fz = lz + dlz * fi;
+  float spx = fx / fz, spy = fy / fz;
+  const float div = (float)((P.sensor_width * 0.5) / (double)-f);
+  { const float inv = 1.0f / div; spx *= inv; spy *= inv; }
+  if (P.abb_distortion > 0.0f) {
+    const double b = (double)P.abb_distortion;
+    const float l = sqrtf(spx * spx + spy * spy);
+    const double bl = (double)l;
+    const float x0 = (float)pow(9. * b * b * bl + sqrt(3.) * sqrt(27. * b * b * b * b * bl * bl + 4. * b * b * b), 1. / 3.);
+    const float xx = (float)((double)x0 / (pow(2., 1. / 3.) * pow(3., 2. / 3.) * b) - pow(2. / 3., 1. / 3.) / (double)x0);
+    spx = spx * (xx / l); spy = spy * (xx / l);
+  }
+  const double aspect = (double)P.xres_without_region / (double)P.yres_without_region;
+  const double s0 = (double)spx, s1 = (double)spy * aspect;
+  pixel_x = (float)((((s0 + 1.0) / 2.0) * P.xres_without_region) - P.region_min_x);
+  pixel_y = (float)((((-s1 + 1.0) / 2.0) * P.yres_without_region) - P.region_min_y);
+  const double xres = (double)P.xres, yres = (double)P.yres;
+  if (((double)pixel_x >= xres) || (pixel_x < 0) || ((double)pixel_y >= yres) || (pixel_y < 0)) return false;
+  if (pixel_x != pixel_x || pixel_y != pixel_y) return false;
   const int ix = (int)floorf(pixel_x), iy = (int)floorf(pixel_y);
   pixelnumber = (uint32_t)(ix + (iy * (int)P.xres));
   return true;

@@ -20,6 +20,7 @@
 #include "lentil_tl_chroma_mgpu.h"
 #include "lentil_lens_jit.h"
 #include "lentil_camera_rays.h"
+#include "lentil_trace_points.h"
 #include "generated/embedded_sources.inc"
 
 #define LENTIL_API extern "C" __attribute__((visibility("default")))
@@ -108,6 +109,7 @@ struct lentil_hip_ctx {
   // the default: the compiled kernels' rate against the interpreter's has not been measured on an MI355X)
   bool rays_compiled = false;
   int rays_path = 0;                  // what the last lentil_hip_camera_rays call ran (lentil_hip_camera_rays_path)
+  int points_path = 0;                // ... the last lentil_hip_trace_points call (lentil_hip_trace_points_path)
 
   DevBokeh bokeh{};
   bool have_bokeh = false;
@@ -5166,6 +5168,92 @@ LENTIL_API int lentil_hip_camera_rays_path(lentil_hip_ctx *ctx, int *path) {
   CHECK_CTX(ctx);
   if (!path) return fail(ctx, LENTIL_ERR_INVALID, "path is null");
   *path = ctx->rays_path;
+  return LENTIL_OK;
+}
+
+// ---- scene points traced backward in batches (lentil_trace_points.h) ----------------------------------------------------
+LENTIL_API int lentil_hip_trace_points(lentil_hip_ctx *ctx, const lentil_point_batch *batch) {
+  CHECK_CTX(ctx);
+  if (!batch) return fail(ctx, LENTIL_ERR_INVALID, "batch is null");
+  if (!ctx->have_params) return fail(ctx, LENTIL_ERR_INVALID, "set_params first");
+  const bool po = ctx->P.cameraType == LENTIL_POLYNOMIAL_OPTICS;
+  if (po && !ctx->have_lens) return fail(ctx, LENTIL_ERR_INVALID, "a polynomial-optics camera needs set_lens first");
+  if (ctx->P.bokeh_enable_image && !ctx->have_bokeh) return fail(ctx, LENTIL_ERR_INVALID, "bokeh_enable_image needs set_bokeh first");
+  if (!batch->attempts) return fail(ctx, LENTIL_ERR_INVALID, "attempts is 0");
+  const uint64_t np = batch->n_points, K = batch->attempts;
+  if (np >= (1ull << 32) || np * K >= (1ull << 32)) return fail(ctx, LENTIL_ERR_INVALID, "n_points * attempts must be below 2^32");
+  if (!np) return LENTIL_OK;
+  if (!batch->cs || !batch->pixel || !batch->out_pixel) return fail(ctx, LENTIL_ERR_INVALID, "cs / pixel / out_pixel is null");
+  const bool device = (batch->flags & LENTIL_POINTS_DEVICE_POINTERS) != 0u;
+  // the seeds of a point's tries, first_attempt ... first_attempt + attempts - 1 + retries, must not wrap
+  const uint64_t reach = K + (uint64_t)(ctx->P.vignetting_retries > 0 ? ctx->P.vignetting_retries : 0);
+  if (reach >= (1ull << 32)) return fail(ctx, LENTIL_ERR_INVALID, "attempts + vignetting_retries does not fit 32 bits");
+  if (!device && batch->first_attempt)
+    for (uint64_t i = 0; i < np; ++i)
+      if ((uint64_t)batch->first_attempt[i] + reach >= (1ull << 32))
+        return fail(ctx, LENTIL_ERR_INVALID, "first_attempt + attempts + vignetting_retries of point " + std::to_string(i) + " does not fit 32 bits");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const uint64_t nq = np * K;
+  TracePointArgs a{};
+  a.P = ctx->P; a.lens = po ? ctx->d_lens : nullptr; a.terms = po ? ctx->d_terms : nullptr; a.bokeh = ctx->bokeh;
+  a.attempts = (uint32_t)K;
+  a.slabs_per_point = (uint32_t)((K + kTpSlab - 1) / kTpSlab);
+  a.n_slabs = (uint32_t)(np * a.slabs_per_point);              // <= n_points * attempts < 2^32
+  a.lambda = batch->lambda != 0.0 ? batch->lambda : (double)ctx->P.lambda_bw;
+  TmpFree tf;
+  float *d_cs = nullptr;
+  uint32_t *d_pixel = nullptr, *d_first = nullptr, *d_out = nullptr;
+  double *d_xy = nullptr, *d_sensor = nullptr;
+  int32_t *d_tries = nullptr;
+  if (device) {
+    a.cs = batch->cs; a.pixel = batch->pixel; a.first_attempt = batch->first_attempt;
+    a.out_pixel = batch->out_pixel; a.out_xy = batch->out_xy; a.out_sensor = batch->out_sensor; a.out_tries = batch->out_tries;
+  } else {
+    int rc;
+    if ((rc = dev_copy_in(ctx, batch->cs, (size_t)np * 3, &d_cs, tf.v))) return rc;
+    if ((rc = dev_copy_in(ctx, batch->pixel, (size_t)np, &d_pixel, tf.v))) return rc;
+    if ((rc = dev_copy_in(ctx, batch->first_attempt, (size_t)np, &d_first, tf.v))) return rc;
+    if ((rc = dev_alloc(ctx, (size_t)nq, &d_out, tf.v))) return rc;
+    if (batch->out_xy && (rc = dev_alloc(ctx, (size_t)nq * 2, &d_xy, tf.v))) return rc;
+    if (batch->out_sensor && (rc = dev_alloc(ctx, (size_t)nq * 2, &d_sensor, tf.v))) return rc;
+    if (batch->out_tries && (rc = dev_alloc(ctx, (size_t)nq, &d_tries, tf.v))) return rc;
+    a.cs = d_cs; a.pixel = d_pixel; a.first_attempt = d_first;
+    a.out_pixel = d_out; a.out_xy = d_xy; a.out_sensor = d_sensor; a.out_tries = d_tries;
+  }
+  // a slab per wave, four waves per block; no more blocks than the device holds at once (eight waves per SIMD at the most)
+  const uint64_t want = ((uint64_t)a.n_slabs + kTpBlock / 64 - 1) / (kTpBlock / 64), cap = (uint64_t)ctx->num_cu * 8u;
+  const dim3 grid((unsigned)(want < cap ? want : cap));
+  int path = 0;
+  if (po) {
+#define LENTIL_LAUNCH_GEN(NAME)                                                                              \
+    if (!path && ctx->use_generated && ctx->lens_hash == gen::Lens_##NAME::kTableHash) {                      \
+      hipLaunchKernelGGL((trace_points_kernel<GenLens<gen::Lens_##NAME>, false, true>), grid, dim3(kTpBlock), 0, ctx->stream, a); \
+      path = 2;                                                                                              \
+    }
+    LENTIL_GENERATED_LENSES(LENTIL_LAUNCH_GEN)
+#undef LENTIL_LAUNCH_GEN
+    if (!path) {
+      hipLaunchKernelGGL((trace_points_kernel<LdsLens, true, true>), grid, dim3(kTpBlock), 0, ctx->stream, a);
+      path = 1;
+    }
+  } else {
+    hipLaunchKernelGGL((trace_points_kernel<LdsLens, false, false>), grid, dim3(kTpBlock), 0, ctx->stream, a);
+  }
+  ctx->points_path = path;
+  HIP_TRY(ctx, hipGetLastError());
+  if (device) return LENTIL_OK;
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  HIP_TRY(ctx, hipMemcpy(batch->out_pixel, d_out, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (batch->out_xy) HIP_TRY(ctx, hipMemcpy(batch->out_xy, d_xy, (size_t)nq * 2 * sizeof(double), hipMemcpyDeviceToHost));
+  if (batch->out_sensor) HIP_TRY(ctx, hipMemcpy(batch->out_sensor, d_sensor, (size_t)nq * 2 * sizeof(double), hipMemcpyDeviceToHost));
+  if (batch->out_tries) HIP_TRY(ctx, hipMemcpy(batch->out_tries, d_tries, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return LENTIL_OK;
+}
+
+LENTIL_API int lentil_hip_trace_points_path(lentil_hip_ctx *ctx, int *path) {
+  CHECK_CTX(ctx);
+  if (!path) return fail(ctx, LENTIL_ERR_INVALID, "path is null");
+  *path = ctx->points_path;
   return LENTIL_OK;
 }
 
