@@ -801,6 +801,96 @@ int lentil_hip_trace_points(lentil_hip_ctx *ctx, const lentil_point_batch *batch
  * interpreter; lentil_hip_set_lens_mode(ctx, 1) forces the interpreter.  The results are the same bit for bit. */
 int lentil_hip_trace_points_path(lentil_hip_ctx *ctx, int *path);
 
+/* --- a visit range's plan and its accepted draws, for a renderer with its own film ---------------
+ * lentil_hip_trace_points answers where attempt m of a point lands.  These two calls answer what the pass makes of the
+ * context's bound visit stream (upload_visits / bind_visits / visits_end), so that a caller never restates the visit prologue
+ * (src/lentil_filter.cpp:105-240) or the draw loop's selection (:249-300, :311-447):
+ *   plan_visits  per visit, what the prologue decides: whether the visit is redistributed, its camera-space position, its
+ *                draw count, fitted_bidir_add_energy and what one contribution of it weighs;
+ *   list_draws   per accepted draw of the redistributed visits, the visit, the attempt, the pixel and the continuous
+ *                pixel coordinates -- the draw list of the reference's pass, record for record.
+ * Both use the context's parameters, the bound visits, the table of set_lens, the tables of set_bokeh, the camera motion keys
+ * and the shutter.  A visit's source pixel and inverse density are derived as the pass derives them: from pixel_x0 / pixel_y0 /
+ * pixel_row_stride / pixels_per_row and params.inverse_sample_density for a uniform stream, from the pixel and inv_density
+ * columns for a ragged one.  Neither needs a frame, touches an accumulator, a cryptomatte table, the counter block
+ * (lentil_hip_get_counters) or the xor128 state, or consults an occlusion probe.  Both observe the context (a pass in flight is
+ * finished first) and take no part in the streamed passes' turns.  Visits are numbered as in the bound stream; a range is
+ * [first_visit, first_visit + n_visits), and must lie inside the stream and below 2^32.
+ *
+ * lentil_hip_plan_visits: one kernel, one record per visit of the range, out[i] for visit first_visit + i.
+ *   cs          camera_space_sample_position: world position (or the skydome substitute) through the world-to-camera matrix at
+ *               the visit's time, times the unit scale -- what lentil_hip_trace_points takes as cs
+ *   add_energy  fitted_bidir_add_energy; 0 for a visit that stays in its pixel (the reference adds none there)
+ *   weight      what one contribution of this visit weighs, formed in fp32 as the pass forms it: inv_density for a visit that
+ *               stays, 1.0f * inv_density * inv_samples (inv_samples = 1.0 / (float)samples, rounded to fp32) for a
+ *               redistributed one
+ *   samples     the draw count (src/lentil_filter.cpp:177-202), computed for every visit as upstream computes it
+ *   pixel       px | py << 16: the region-relative source pixel (the px, py of the draws' seed)
+ *   flags       LENTIL_PLAN_REDISTRIBUTE: the visit is redistributed
+ *   totals      optional, host memory: [0] visits in the range, [1] redistributed ones, [2] the sum of their samples -- an
+ *               upper bound on what list_draws finds for the same range: size its `out` with it.
+ *   flags LENTIL_PLAN_DEVICE_POINTERS: `out` is device memory of the context's GPU.  With it and totals == NULL the call
+ *   only enqueues on lentil_hip_stream(ctx); in every other case it returns when out / totals are filled.
+ *
+ * lentil_hip_list_draws: polynomial optics with abb_chromatic == 0 and the thin lens with abb_chromatic <= 0.
+ *   A redistributed visit contributes one record for each of the first `samples` attempts n < 5 * samples whose trace is a
+ *   pixel -- the attempts the reference's loop accepts before it stops.  The trace of attempt n is
+ *   lentil_hip_trace_points' for (plan.cs, plan.pixel, n), the arithmetic is trace_points_kernel's operation for operation:
+ *   polynomial optics use vignetting_retries + 1 tries at seeds n + tries (vignetting_retries < 0: no try is made, no
+ *   records), the thin lens one try.  lambda: as in lentil_point_batch.
+ *   visit / attempt / pixel  equal the draw log of the reference's pass over these visits (lentil_hip_set_draw_log's records)
+ *   tries                    the vignetted tries before the one that got through (thin lens: 0)
+ *   xy                       the continuous pixel coordinates before floor (trace_points' out_xy)
+ *   The order of the records is unspecified.  Their content is not: the list, as a set, does not depend on the grid, on the
+ *   capacity or on how a stream is split into visit ranges.
+ *   capacity / out   records `out` holds.  *n_draws (host memory, required) is the number of accepted draws found; where it
+ *                    exceeds capacity, `capacity` records were written, nothing beyond out[capacity - 1], and the caller asks
+ *                    again with more room (the records written are some `capacity` of the list).  n_draws is read back, so
+ *                    the call returns when the list is complete -- with LENTIL_DRAWS_DEVICE_POINTERS (`out` is device memory
+ *                    of the context's GPU) too.
+ *   attempts         optional, host memory: the attempts made -- the reference's attempted_draws for these visits
+ *   LENTIL_ERR_UNSUPPORTED, with a message: polynomial optics with abb_chromatic != 0 (three traces per attempt under another
+ *   counting rule), the thin lens with abb_chromatic > 0 (the channels follow the pass's xor128 order; trace_points does not
+ *   offer it either).
+ * LENTIL_ERR_INVALID (both calls): no parameters or no visits, polynomial optics without a lens, bokeh_enable_image without
+ * tables (list_draws), a range outside the stream or beyond 2^32, out NULL with n_visits > 0 (plan) or capacity > 0 (list),
+ * n_draws NULL.  n_visits == 0 launches nothing (zero totals, zero n_draws).
+ * lentil_hip_list_draws_path: what the last list_draws call of this context ran, as lentil_hip_trace_points_path: 0 the thin
+ * lens (or no call yet), 1 the table interpreter (also a table compiled at run time, and lentil_hip_set_lens_mode(ctx, 1)),
+ * 2 the straight-line kernel of a compiled-in lens.  The lists are the same bit for bit. */
+#define LENTIL_PLAN_DEVICE_POINTERS 1u
+#define LENTIL_PLAN_REDISTRIBUTE    1u      /* lentil_visit_plan::flags bit 0 */
+typedef struct lentil_visit_plan {          /* 32 bytes, one per visit */
+  float cs[3];        /* camera space after unit scaling: camera_space_sample_position (what trace_points takes as cs) */
+  float add_energy;   /* fitted_bidir_add_energy (0 for a visit that stays in its pixel) */
+  float weight;       /* what one contribution of this visit weighs (see above) */
+  uint32_t samples;   /* the draw count (computed for every visit, as upstream) */
+  uint32_t pixel;     /* px | py << 16, region-relative source pixel (the seed's px, py) */
+  uint32_t flags;     /* LENTIL_PLAN_REDISTRIBUTE */
+} lentil_visit_plan;
+int lentil_hip_plan_visits(lentil_hip_ctx *ctx, uint64_t first_visit, uint64_t n_visits, lentil_visit_plan *out,
+                           uint32_t flags, uint64_t totals[3] /* optional: visits, redistributed, sum of their samples */);
+
+#define LENTIL_DRAWS_DEVICE_POINTERS 1u
+typedef struct lentil_draw {                /* 32 bytes */
+  uint32_t visit;     /* index into the bound stream */
+  uint32_t attempt;   /* the reference's total_samples_taken of the draw */
+  uint32_t pixel;     /* linear pixel ix + iy * xres */
+  int32_t  tries;     /* vignetted tries before the one that got through (thin lens: 0) */
+  double   xy[2];     /* continuous pixel coordinates before floor (trace_points' out_xy) */
+} lentil_draw;
+typedef struct lentil_draw_list {
+  uint64_t first_visit, n_visits;
+  uint32_t flags;
+  uint64_t capacity;      /* records `out` holds */
+  lentil_draw *out;
+  double lambda;          /* polynomial optics, micrometres; 0: params.lambda_bw */
+  uint64_t *n_draws;      /* host: accepted draws found; > capacity: nothing beyond capacity was written, ask again */
+  uint64_t *attempts;     /* optional, host: attempts made (the reference's attempted_draws for these visits) */
+} lentil_draw_list;
+int lentil_hip_list_draws(lentil_hip_ctx *ctx, const lentil_draw_list *list);
+int lentil_hip_list_draws_path(lentil_hip_ctx *ctx, int *path);   /* 0 thin lens / none yet, 1 interpreter, 2 compiled-in lens */
+
 /* --- single-function device tests (parity of the optics primitives) -----------------
  * Runs n independent evaluations on the GPU; host pointers in/out.
  * lt_sample_aperture: Camera::lens_lt_sample_aperture (src/lentil.h:1296-1313) for

@@ -14,6 +14,9 @@ RAYS_PATH_THIN_LENS, RAYS_PATH_INTERPRETER, RAYS_PATH_COMPILED_IN, RAYS_PATH_RUN
 POINTS_DEVICE_POINTERS = 1
 POINT_VIGNETTED, POINT_OUTSIDE = 0xFFFFFFFF, 0xFFFFFFFE                                                # lentil_point_batch.out_pixel
 POINTS_PATH_THIN_LENS, POINTS_PATH_INTERPRETER, POINTS_PATH_COMPILED_IN = 0, 1, 2                     # lentil_hip_trace_points_path
+PLAN_DEVICE_POINTERS, PLAN_REDISTRIBUTE = 1, 1                                                         # lentil_hip_plan_visits flags, lentil_visit_plan.flags
+DRAWS_DEVICE_POINTERS = 1
+DRAWS_PATH_THIN_LENS, DRAWS_PATH_INTERPRETER, DRAWS_PATH_COMPILED_IN = 0, 1, 2                        # lentil_hip_list_draws_path
 
 
 class Params(C.Structure):
@@ -121,3 +124,24 @@ class PointBatch(C.Structure):
                 ("cs", C.c_void_p), ("pixel", C.c_void_p), ("first_attempt", C.c_void_p),
                 ("lam", C.c_double),
                 ("out_pixel", C.c_void_p), ("out_xy", C.c_void_p), ("out_sensor", C.c_void_p), ("out_tries", C.c_void_p)]
+
+
+class DrawList(C.Structure):
+    _fields_ = [("first_visit", C.c_uint64), ("n_visits", C.c_uint64), ("flags", C.c_uint32), ("capacity", C.c_uint64),
+                ("out", C.c_void_p), ("lam", C.c_double), ("n_draws", C.POINTER(C.c_uint64)), ("attempts", C.POINTER(C.c_uint64))]
+
+
+def _record_dtypes():
+    """lentil_visit_plan and lentil_draw as numpy structured dtypes, 32 bytes each (numpy is imported here, not by the module:
+    the layout mirror itself needs none)"""
+    import numpy as np
+    plan = np.dtype({"names": ["cs", "add_energy", "weight", "samples", "pixel", "flags"],
+                     "formats": [(np.float32, (3,)), np.float32, np.float32, np.uint32, np.uint32, np.uint32],
+                     "offsets": [0, 12, 16, 20, 24, 28], "itemsize": 32})
+    draw = np.dtype({"names": ["visit", "attempt", "pixel", "tries", "xy"],
+                     "formats": [np.uint32, np.uint32, np.uint32, np.int32, (np.float64, (2,))],
+                     "offsets": [0, 4, 8, 12, 16], "itemsize": 32})
+    return plan, draw
+
+
+VisitPlan, Draw = _record_dtypes()

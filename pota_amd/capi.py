@@ -31,6 +31,7 @@ EXPORTS = [
     "lentil_hip_lens_is_compiled", "lentil_hip_set_lens_mode",
     "lentil_hip_focus_search", "lentil_hip_test_y0_intersection", "lentil_hip_camera_rays", "lentil_hip_camera_rays_path",
     "lentil_hip_trace_points", "lentil_hip_trace_points_path",
+    "lentil_hip_plan_visits", "lentil_hip_list_draws", "lentil_hip_list_draws_path",
     "lentil_hip_set_xor128_state", "lentil_hip_get_xor128_state", "lentil_hip_tl_chroma_stats", "lentil_hip_test_xor128_jump",
     "lentil_hip_host_alloc", "lentil_hip_host_free", "lentil_hip_visits_begin", "lentil_hip_visits_append",
     "lentil_hip_visits_wait", "lentil_hip_visits_end",
@@ -189,6 +190,9 @@ def load_library():
         "lentil_hip_camera_rays_path": (i, [vp, C.POINTER(C.c_int)]),
         "lentil_hip_trace_points": (i, [vp, C.POINTER(_abi.PointBatch)]),
         "lentil_hip_trace_points_path": (i, [vp, C.POINTER(C.c_int)]),
+        "lentil_hip_plan_visits": (i, [vp, u64, u64, vp, C.c_uint32, C.POINTER(u64)]),
+        "lentil_hip_list_draws": (i, [vp, C.POINTER(_abi.DrawList)]),
+        "lentil_hip_list_draws_path": (i, [vp, C.POINTER(C.c_int)]),
         "lentil_hip_set_xor128_state": (i, [vp, C.POINTER(C.c_uint32)]),
         "lentil_hip_get_xor128_state": (i, [vp, C.POINTER(C.c_uint32)]),
         "lentil_hip_tl_chroma_stats": (i, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
@@ -568,6 +572,67 @@ class Context:
         """What the last trace_points call ran: one of _abi.POINTS_PATH_* (lentil_hip_trace_points_path)."""
         path = C.c_int()
         self._chk(self.lib.lentil_hip_trace_points_path(self.h, C.byref(path)))
+        return path.value
+
+    def _visit_range(self, first, n):
+        first = int(first)
+        if n is None:
+            n = max(int(self.counters().visits) - first, 0)
+        return first, int(n)
+
+    def _device_records(self, n):
+        """n 32-byte records on this context's GPU, as a uint8 [n, 32] torch tensor"""
+        import torch
+        return torch.empty((n, 32), dtype=torch.uint8, device="cuda:%d" % self.device)
+
+    def plan_visits(self, first=0, n=None, device=False, totals=True):
+        """What the visit prologue decides for the bound visits first ... first + n - 1 (n None: to the stream's end)
+        (lentil_hip_plan_visits) -> (records, totals): records a numpy array of _abi.VisitPlan, one per visit (cs, add_energy,
+        weight, samples, pixel = px | py << 16, flags & _abi.PLAN_REDISTRIBUTE); totals (visits, redistributed visits, the sum of
+        their samples -- an upper bound on what list_draws finds for the range), or None with totals=False.
+        device=True: the records stay on the GPU, a uint8 [n, 32] torch tensor (.cpu().numpy().view(_abi.VisitPlan) reads it);
+        with totals=False as well the call only enqueues on the context's stream (stream()), the caller orders it (sync())."""
+        first, n = self._visit_range(first, n)
+        tot = (C.c_uint64 * 3)() if totals else None
+        if device:
+            out = self._device_records(n)
+            ptr, flags = (out.data_ptr() if n else None), _abi.PLAN_DEVICE_POINTERS
+        else:
+            out = np.empty(n, _abi.VisitPlan)
+            ptr, flags = (out.ctypes.data if n else None), 0
+        self._chk(self.lib.lentil_hip_plan_visits(self.h, first, n, ptr, flags, tot))
+        return out, (tuple(int(t) for t in tot) if totals else None)
+
+    def list_draws(self, first=0, n=None, capacity=None, lam=0.0, device=False):
+        """The accepted draws of the bound visits first ... first + n - 1 (lentil_hip_list_draws) -> (records, n_draws,
+        attempts): records a numpy array of _abi.Draw (visit, attempt, pixel, tries, xy), in no particular order, the first
+        min(n_draws, capacity) of it filled and returned; n_draws the accepted draws found (above capacity: ask again with more
+        room); attempts the attempts made.  capacity None: sized from plan_visits' totals[2], which always suffices.
+        lam: micrometres, 0 = params.lambda_bw.  device=True: the records stay on the GPU, a uint8 [capacity, 32] torch tensor,
+        whole (the call returns when it is filled)."""
+        first, n = self._visit_range(first, n)
+        if capacity is None:
+            capacity = self.plan_visits(first, n)[1][2] if n else 0
+        capacity = int(capacity)
+        nd, att = C.c_uint64(), C.c_uint64()
+        b = _abi.DrawList()
+        b.first_visit, b.n_visits, b.capacity, b.lam = first, n, capacity, float(lam)
+        b.n_draws, b.attempts = C.pointer(nd), C.pointer(att)
+        if device:
+            out = self._device_records(capacity)
+            b.out, b.flags = (out.data_ptr() if capacity else None), _abi.DRAWS_DEVICE_POINTERS
+        else:
+            out = np.empty(capacity, _abi.Draw)
+            b.out, b.flags = (out.ctypes.data if capacity else None), 0
+        self._chk(self.lib.lentil_hip_list_draws(self.h, C.byref(b)))
+        if not device:
+            out = out[:min(nd.value, capacity)]
+        return out, nd.value, att.value
+
+    def list_draws_path(self):
+        """What the last list_draws call ran: one of _abi.DRAWS_PATH_* (lentil_hip_list_draws_path)."""
+        path = C.c_int()
+        self._chk(self.lib.lentil_hip_list_draws_path(self.h, C.byref(path)))
         return path.value
 
     def test_y0_intersection(self, sensor_shift, lam):

@@ -21,6 +21,7 @@
 #include "lentil_lens_jit.h"
 #include "lentil_camera_rays.h"
 #include "lentil_trace_points.h"
+#include "lentil_list_draws.h"
 #include "generated/embedded_sources.inc"
 
 #define LENTIL_API extern "C" __attribute__((visibility("default")))
@@ -110,6 +111,9 @@ struct lentil_hip_ctx {
   bool rays_compiled = false;
   int rays_path = 0;                  // what the last lentil_hip_camera_rays call ran (lentil_hip_camera_rays_path)
   int points_path = 0;                // ... the last lentil_hip_trace_points call (lentil_hip_trace_points_path)
+  int draws_path = 0;                 // ... the last lentil_hip_list_draws call (lentil_hip_list_draws_path)
+  // lentil_hip_plan_visits / lentil_hip_list_draws: [0..2] the plan's totals, [4] the list's ticket, [5] its draws, [6] its attempts
+  unsigned long long *d_list_ctr = nullptr;
 
   DevBokeh bokeh{};
   bool have_bokeh = false;
@@ -781,6 +785,7 @@ LENTIL_API int lentil_hip_destroy(lentil_hip_ctx *ctx) {
   (void)hipFree(ctx->d_terms);
   (void)hipFree(ctx->d_blade_sc);
   (void)hipFree(ctx->d_cam_keys);
+  (void)hipFree(ctx->d_list_ctr);
   (void)hipFree(ctx->d_dummy);
   (void)hipFree(ctx->F.acc);
   (void)hipFree(ctx->F.zkey);
@@ -5254,6 +5259,120 @@ LENTIL_API int lentil_hip_trace_points_path(lentil_hip_ctx *ctx, int *path) {
   CHECK_CTX(ctx);
   if (!path) return fail(ctx, LENTIL_ERR_INVALID, "path is null");
   *path = ctx->points_path;
+  return LENTIL_OK;
+}
+
+// ---- a visit range's plan and its accepted draws (lentil_list_draws.h) ----------------------------------------------------
+static int list_range_check(lentil_hip_ctx *ctx, uint64_t first, uint64_t n) {
+  if (!ctx->have_params) return fail(ctx, LENTIL_ERR_INVALID, "set_params first");
+  if (!ctx->have_visits) return fail(ctx, LENTIL_ERR_INVALID, "no visits bound");
+  if (ctx->P.cameraType == LENTIL_POLYNOMIAL_OPTICS && !ctx->have_lens)
+    return fail(ctx, LENTIL_ERR_INVALID, "a polynomial-optics camera needs set_lens first");
+  if (first > ctx->V.n || n > ctx->V.n - first)
+    return fail(ctx, LENTIL_ERR_INVALID, "visits " + std::to_string(first) + " + " + std::to_string(n) + " lie outside the stream of " + std::to_string(ctx->V.n));
+  if (first + n > (1ull << 32)) return fail(ctx, LENTIL_ERR_INVALID, "the visit range must lie below 2^32");
+  if (!ctx->d_list_ctr) HIP_TRY(ctx, hipMalloc(&ctx->d_list_ctr, 8 * sizeof(unsigned long long)));
+  return LENTIL_OK;
+}
+
+LENTIL_API int lentil_hip_plan_visits(lentil_hip_ctx *ctx, uint64_t first_visit, uint64_t n_visits, lentil_visit_plan *out,
+                                      uint32_t flags, uint64_t totals[3]) {
+  CHECK_CTX(ctx);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int rc;
+  if ((rc = list_range_check(ctx, first_visit, n_visits))) return rc;
+  if (totals) totals[0] = totals[1] = totals[2] = 0;
+  if (!n_visits) return LENTIL_OK;
+  if (!out) return fail(ctx, LENTIL_ERR_INVALID, "out is null");
+  const bool device = (flags & LENTIL_PLAN_DEVICE_POINTERS) != 0u;
+  PlanArgs a{};
+  a.P = ctx->P; a.V = ctx->V; a.lens_length = ctx->have_lens ? ctx->hlens.length : 0.0;
+  a.v_begin = first_visit; a.v_end = first_visit + n_visits;
+  TmpFree tf;
+  lentil_visit_plan *d_out = out;
+  if (!device && (rc = dev_alloc(ctx, (size_t)n_visits, &d_out, tf.v))) return rc;
+  a.out = d_out;
+  if (totals) {
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_list_ctr, 0, 3 * sizeof(unsigned long long), ctx->stream));
+    a.totals = ctx->d_list_ctr;
+  }
+  // 64 visits per wave and step, four waves per block; no more blocks than the device holds at once
+  const uint64_t want = (n_visits + kLdBlock - 1) / kLdBlock, cap = (uint64_t)ctx->num_cu * 8u;
+  hipLaunchKernelGGL(plan_visits_kernel, dim3((unsigned)(want < cap ? want : cap)), dim3(kLdBlock), 0, ctx->stream, a);
+  HIP_TRY(ctx, hipGetLastError());
+  if (device && !totals) return LENTIL_OK;
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (!device) HIP_TRY(ctx, hipMemcpy(out, d_out, (size_t)n_visits * sizeof(lentil_visit_plan), hipMemcpyDeviceToHost));
+  if (totals) HIP_TRY(ctx, hipMemcpy(totals, ctx->d_list_ctr, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return LENTIL_OK;
+}
+
+LENTIL_API int lentil_hip_list_draws(lentil_hip_ctx *ctx, const lentil_draw_list *list) {
+  CHECK_CTX(ctx);
+  if (!list) return fail(ctx, LENTIL_ERR_INVALID, "list is null");
+  if (!list->n_draws) return fail(ctx, LENTIL_ERR_INVALID, "n_draws is null");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int rc;
+  if ((rc = list_range_check(ctx, list->first_visit, list->n_visits))) return rc;
+  const bool po = ctx->P.cameraType == LENTIL_POLYNOMIAL_OPTICS;
+  if (ctx->P.bokeh_enable_image && !ctx->have_bokeh) return fail(ctx, LENTIL_ERR_INVALID, "bokeh_enable_image needs set_bokeh first");
+  if (po && ctx->P.abb_chromatic != 0.0f)
+    return fail(ctx, LENTIL_ERR_UNSUPPORTED, "list_draws: polynomial optics with abb_chromatic != 0 trace three channels per attempt under another counting rule");
+  if (!po && ctx->P.abb_chromatic > 0.0f)
+    return fail(ctx, LENTIL_ERR_UNSUPPORTED, "list_draws: the thin lens with abb_chromatic > 0 draws its channels in the pass's xor128 order");
+  if (list->capacity && !list->out) return fail(ctx, LENTIL_ERR_INVALID, "out is null with capacity > 0");
+  *list->n_draws = 0;
+  if (list->attempts) *list->attempts = 0;
+  if (!list->n_visits) return LENTIL_OK;
+  const bool device = (list->flags & LENTIL_DRAWS_DEVICE_POINTERS) != 0u;
+  ListDrawArgs a{};
+  a.P = ctx->P; a.V = ctx->V; a.lens_length = ctx->have_lens ? ctx->hlens.length : 0.0;
+  a.lens = po ? ctx->d_lens : nullptr; a.terms = po ? ctx->d_terms : nullptr; a.bokeh = ctx->bokeh;
+  a.v_begin = list->first_visit; a.v_end = list->first_visit + list->n_visits;
+  a.capacity = list->capacity;
+  a.lambda = list->lambda != 0.0 ? list->lambda : (double)ctx->P.lambda_bw;
+  TmpFree tf;
+  lentil_draw *d_out = list->out;
+  if (!device && list->capacity && (rc = dev_alloc(ctx, (size_t)list->capacity, &d_out, tf.v))) return rc;
+  a.out = d_out;
+  a.ctr = ctx->d_list_ctr + 4;
+  HIP_TRY(ctx, hipMemsetAsync(a.ctr, 0, 3 * sizeof(unsigned long long), ctx->stream));
+  // a wave takes 64 visits per ticket: no more waves than tickets, no more blocks than the device holds at once
+  const uint64_t tickets = (list->n_visits + 63) / 64;
+  const uint64_t want = (tickets + kLdBlock / 64 - 1) / (kLdBlock / 64), cap = (uint64_t)ctx->num_cu * 8u;
+  const dim3 grid((unsigned)(want < cap ? want : cap));
+  int path = 0;
+  if (po) {
+#define LENTIL_LAUNCH_GEN(NAME)                                                                              \
+    if (!path && ctx->use_generated && ctx->lens_hash == gen::Lens_##NAME::kTableHash) {                      \
+      hipLaunchKernelGGL((list_draws_kernel<GenLens<gen::Lens_##NAME>, false, true>), grid, dim3(kLdBlock), 0, ctx->stream, a); \
+      path = 2;                                                                                              \
+    }
+    LENTIL_GENERATED_LENSES(LENTIL_LAUNCH_GEN)
+#undef LENTIL_LAUNCH_GEN
+    if (!path) {
+      hipLaunchKernelGGL((list_draws_kernel<LdsLens, true, true>), grid, dim3(kLdBlock), 0, ctx->stream, a);
+      path = 1;
+    }
+  } else {
+    hipLaunchKernelGGL((list_draws_kernel<LdsLens, false, false>), grid, dim3(kLdBlock), 0, ctx->stream, a);
+  }
+  ctx->draws_path = path;
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  unsigned long long h[3] = {0, 0, 0};
+  HIP_TRY(ctx, hipMemcpy(h, a.ctr, sizeof h, hipMemcpyDeviceToHost));
+  *list->n_draws = h[1];
+  if (list->attempts) *list->attempts = h[2];
+  const uint64_t written = h[1] < list->capacity ? h[1] : list->capacity;
+  if (!device && written) HIP_TRY(ctx, hipMemcpy(list->out, d_out, (size_t)written * sizeof(lentil_draw), hipMemcpyDeviceToHost));
+  return LENTIL_OK;
+}
+
+LENTIL_API int lentil_hip_list_draws_path(lentil_hip_ctx *ctx, int *path) {
+  CHECK_CTX(ctx);
+  if (!path) return fail(ctx, LENTIL_ERR_INVALID, "path is null");
+  *path = ctx->draws_path;
   return LENTIL_OK;
 }
 
