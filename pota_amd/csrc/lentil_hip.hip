@@ -2215,315 +2215,8 @@ static int prepare_direct(lentil_hip_ctx *ctx, const lentil_hip_ctx::DirRegion *
   return LENTIL_OK;
 }
 
-// Where get_coc_thinlens(P, cz) < 0.4f (lentil_device.h; src/lentil.h:674-692, src/lentil_filter.cpp:185-190) is decided by cz
-// alone, for scan_dma2_kernel.  The kernel computes, in fp32, ifd = (-f * -fd) / (-f + -fd), isp = (-f * z) / (-f + z),
-// coc = |A (isp - ifd) / isp|.  In exact arithmetic 1 / isp = 1 / z - 1 / f, so coc = |A| |c0 - c1 / z| with c0 = 1 + ifd / f,
-// c1 = ifd: in u = 1 / z the set {coc < t} is ONE interval around the focus plane.  The fp32 evaluation differs from that by
-// a few 1e-7 relative, times |A| / 0.4 near the threshold (the subtraction isp - ifd carries isp's rounding): with
-// eps = 1e-3 + 1e-5 |A| the comparison with 0.4 (1 - eps) / 0.4 (1 + eps) is certain, and the strip in between -- a
-// few visits in 10^4 -- is left to the function.  Interval ends are rounded towards the uncertain side; |z| > 1e30 (where
-// -f * z overflows and the function returns NaN) is never "certainly below".
-static ScanBands scan_bands(const lentil_params &P) {
-  ScanBands B;
-  for (int i = 0; i < 2; ++i) { B.in_lo[i] = 1.0f; B.in_hi[i] = -1.0f; B.out_lo[i] = 1.0f; B.out_hi[i] = -1.0f; }
-  B.out_lo[0] = -INFINITY; B.out_hi[0] = INFINITY;       // nothing usable: every finite depth asks the function
-  float fd = (float)P.focus_distance, A = (float)P.aperture_radius;
-  if (P.cameraType == LENTIL_POLYNOMIAL_OPTICS) fd = (float)((double)fd / 10.0);
-  else A = (float)((double)A * 10.0);
-  const float f = P.focal_length;
-  const float ifd = (-f * -fd) / (-f + -fd);
-  const double a = std::fabs((double)A), c0 = 1.0 + (double)ifd / (double)f, c1 = (double)ifd;
-  if (!(a > 0.0) || !std::isfinite(a) || !std::isfinite(c0) || !std::isfinite(c1) || c1 == 0.0 || !(f > 0.0f)) return B;
-  const double eps = 1e-3 + 1e-5 * a;
-  if (!(eps < 0.25)) return B;
-  auto up = [](double v) { float r = (float)v; if ((double)r < v) r = std::nextafter(r, INFINITY); return r; };       // smallest float >= v
-  auto down = [](double v) { float r = (float)v; if ((double)r > v) r = std::nextafter(r, -INFINITY); return r; };    // largest float <= v
-  // z-intervals of {coc <= t}: u in [ua, ub], z = 1 / u
-  auto pieces = [&](double t, bool inner, float lo[2], float hi[2]) {
-    double ua = (c0 - t / a) / c1, ub = (c0 + t / a) / c1;
-    if (ua > ub) std::swap(ua, ub);
-    lo[0] = lo[1] = 1.0f; hi[0] = hi[1] = -1.0f;
-    const double big = inner ? 1e30 : (double)INFINITY;
-    if (ua > 0.0 || ub < 0.0) {
-      const double zl = 1.0 / ub, zh = 1.0 / ua;
-      lo[0] = inner ? up(std::max(zl, -big)) : down(zl);
-      hi[0] = inner ? down(std::min(zh, big)) : up(zh);
-    } else {
-      // the interval holds u = 0: everything beyond 1 / ua on the negative side, beyond 1 / ub on the positive side
-      if (ua < 0.0) { lo[0] = inner ? (float)-big : -INFINITY; hi[0] = inner ? down(1.0 / ua) : up(1.0 / ua); }
-      if (ub > 0.0) { lo[1] = inner ? up(1.0 / ub) : down(1.0 / ub); hi[1] = inner ? (float)big : INFINITY; }
-      if (!inner && (ua == 0.0 || ub == 0.0)) { lo[0] = -INFINITY; hi[0] = INFINITY; }
-    }
-  };
-  ScanBands R = B;
-  pieces(0.4 * (1.0 - eps), true, R.in_lo, R.in_hi);
-  pieces(0.4 * (1.0 + eps), false, R.out_lo, R.out_hi);
-  for (int i = 0; i < 2; ++i)
-    if (std::isnan(R.in_lo[i]) || std::isnan(R.in_hi[i]) || std::isnan(R.out_lo[i]) || std::isnan(R.out_hi[i])) return B;
-  return R;
-}
+#include "lentil_scan.h"
 
-// test hook (no GPU needed): the intervals scan_dma2_kernel would use for these parameters -- in_lo[2], in_hi[2], out_lo[2], out_hi[2]
-LENTIL_API int lentil_hip_debug_scan_bands(const lentil_params *P, float out[8]) {
-  if (!P || !out) return LENTIL_ERR_INVALID;
-  const ScanBands B = scan_bands(*P);
-  for (int i = 0; i < 2; ++i) { out[i] = B.in_lo[i]; out[2 + i] = B.in_hi[i]; out[4 + i] = B.out_lo[i]; out[6 + i] = B.out_hi[i]; }
-  return LENTIL_OK;
-}
-
-// test hook (no GPU needed): scan_dma2_kernel's lean ring slots, the open groups that make a tile busy, the quiet tiles before
-// a wave returns to the lean body (kLeanRing, kBusyGroups, kQuietTiles)
-LENTIL_API int lentil_hip_debug_scan_lean_counts(uint32_t out[3]) {
-  if (!out) return LENTIL_ERR_INVALID;
-  out[0] = kLeanRing; out[1] = kBusyGroups; out[2] = kQuietTiles;
-  return LENTIL_OK;
-}
-
-// How the bound visit stream is scanned: kernel, tile size, LDS.
-struct ScanPlan {
-  ScanArgs sa{};
-  size_t lds = 0;
-  uint64_t n_tiles = 0;
-  bool multi = false;
-  bool dma = false;       // scan_dma_kernel (beauty only, uniform weights)
-  bool dma2 = false;      // ... its pipelined form, scan_dma2_kernel (one block per CU)
-  bool dma_multi = false; // scan_dma_multi_kernel (extra gaussian AOVs, uniform weights)
-  uint32_t M = 0;
-};
-
-// slots per wave (LENTIL_DMA_MULTI_RING: 2 or 3; no difference measured, the waves are not short of bytes in flight)
-static uint32_t dma_multi_ring(const lentil_hip_ctx *) {
-  static const int forced = getenv("LENTIL_DMA_MULTI_RING") ? atoi(getenv("LENTIL_DMA_MULTI_RING")) : 0;
-  return forced == 3 ? 3u : 2u;
-}
-// blocks per CU (LENTIL_DMA_MULTI_BLOCKS): two where the CU's LDS holds them and two solve blocks beside them
-static uint32_t dma_multi_blocks_per_cu(const lentil_hip_ctx *ctx) {
-  static const int forced = getenv("LENTIL_DMA_MULTI_BLOCKS") ? atoi(getenv("LENTIL_DMA_MULTI_BLOCKS")) : 0;
-  if (forced >= 1 && forced <= 4) return (uint32_t)forced;
-  const size_t one = (size_t)4 * dma_multi_wave_f4(ctx->V.n_extra, dma_multi_ring(ctx)) * 16 + 4 * kWaveQueueLds * sizeof(uint2);
-  return 2u * one + 2u * 10u * 1024u <= 160u * 1024u ? 2u : 1u;
-}
-static size_t dma_multi_lds(const lentil_hip_ctx *ctx) {
-  return (size_t)4 * dma_multi_wave_f4(ctx->V.n_extra, dma_multi_ring(ctx)) * 16 + 4 * kWaveQueueLds * sizeof(uint2);
-}
-
-// scan_dma_multi_kernel takes the stream: whole pixels of M <= 64 visits, uniform weights, gaussian AOVs only
-static bool dma_multi_applies(const lentil_hip_ctx *ctx) {
-  static const bool allowed = !(getenv("LENTIL_SCAN_DMA_MULTI") && getenv("LENTIL_SCAN_DMA_MULTI")[0] == '0');
-  const uint32_t M = ctx->V.visits_per_pixel;
-  return allowed && ctx->scan_dma && M > 0 && M <= 64 && ctx->V.n_extra > 0 && !ctx->V.inv_density && !ctx->F.zkey && !ctx->F.zkey_dbg &&
-         ctx->F.closest_mask == 0 && ctx->V.cam.n < 2 && ctx->V.n % M == 0 && dma_multi_lds(ctx) <= 160u * 1024u;
-}
-
-// static LDS of one resident solve block of a streamed pass (solve_po_kernel<.., kStream>; tools/kernel_resources.py): 28.2 KB for a
-// lens that runs as straight-line code -- built into the library, or specialised at run time once its code object is there --,
-// 52.2 KB with the table interpreter
-static size_t solve_block_lds(lentil_hip_ctx *ctx) {
-  const bool straight = ctx->use_generated && (lentil_hip_lens_is_compiled(ctx) || jit_function(ctx, false, true) != nullptr);
-  return straight ? 29184u : 53760u;
-}
-
-static int plan_scan(lentil_hip_ctx *ctx, ScanPlan &pl) {
-  ScanArgs &sa = pl.sa;
-  sa.P = ctx->P;
-  sa.lens_length = ctx->have_lens ? ctx->hlens.length : 0.0;
-  sa.V = ctx->V;
-  sa.F = ctx->F;
-  const uint32_t M = ctx->V.visits_per_pixel;
-  pl.M = M;
-  if (M) {
-    // staging: 20 B per visit per wave, 4 waves per block, keep a block under ~48 KiB
-    uint32_t ppt = 64;
-    // extra AOV columns are streamed one at a time: more, smaller tiles keep enough loads in flight
-    // (beauty only: 64-pixel tiles, three blocks per CU.  32-pixel tiles / four blocks per CU are 3 % faster for a
-    // scan that has the chip to itself -- 0.946 against 0.972 ms -- and 20 % slower beside the first chunk's solve
-    // kernel, which then does not get its wave per SIMD until scan blocks retire)
-    uint64_t lds_budget = (ctx->V.n_extra ? 24ull : 48ull) * 1024ull;
-    if (const char *e = getenv("LENTIL_SCAN_LDS_KB")) lds_budget = strtoull(e, nullptr, 10) * 1024ull;
-    while (ppt > 1 && (uint64_t)ppt * M * 20ull * 4ull > lds_budget) ppt >>= 1;
-    if ((uint64_t)ppt * M * 20ull * 4ull > 150ull * 1024ull)
-      return fail(ctx, LENTIL_ERR_UNSUPPORTED, "visits_per_pixel too large for the LDS staging area");
-    sa.ppt = ppt;
-    sa.tv_pad = ppt * M;
-    pl.lds = (size_t)sa.tv_pad * 20 * 4 + 4 * kWaveQueueLds * sizeof(uint2);
-    // frames with extra AOVs: all columns of a visit in flight at once, one step = 64 / M whole pixels
-    pl.multi = ctx->V.n_extra > 0 && M <= 64 && !getenv("LENTIL_SCAN_SINGLE_COLUMN");
-    if (pl.multi) {
-      ppt = 64 / M;
-      sa.ppt = ppt;
-      sa.tv_pad = ppt * M;
-      const size_t wave_f4 = (size_t)ctx->F.n_aovs * kMultiPlane + 16 + (size_t)ppt * (ctx->F.stride / 4);
-      pl.lds = 4 * wave_f4 * 16 + 4 * kWaveQueueLds * sizeof(uint2);
-    }
-    // ring slots of scan_dma_kernel (LENTIL_DMA_RING; a streamed pass has one scan block per CU and LDS to spare)
-    uint32_t dma_ring = kDmaRing;
-    if (const char *e = getenv("LENTIL_DMA_RING")) { const int r = atoi(e); if (r >= 2 && r <= 8) dma_ring = (uint32_t)r; }
-    const size_t dma_lds = (size_t)4 * dma_wave_f4(M, dma_ring) * 16 + 4 * kWaveQueueLds * sizeof(uint2);
-    pl.dma = ctx->scan_dma && ctx->V.n_extra == 0 && !ctx->V.inv_density && !ctx->F.zkey && !ctx->F.zkey_dbg && ctx->V.cam.n < 2 &&
-             ctx->V.n % M == 0 && dma_lds <= 80u * 1024u;
-    if (pl.dma) {
-      ppt = 64;
-      sa.ring = dma_ring;
-      sa.ppt = ppt;
-      sa.tv_pad = ppt * M;
-      pl.lds = dma_lds;
-      pl.multi = false;
-      // scan_dma2_kernel: tiles pipelined into one another (two rgba buffers per wave), one block per CU.  In a streamed pass
-      // the block must fit beside the resident solve blocks, or neither it nor they would ever end (LENTIL_SCAN_DMA2=0: never)
-      static const bool dma2_allowed = !(getenv("LENTIL_SCAN_DMA2") && getenv("LENTIL_SCAN_DMA2")[0] == '0');
-      const size_t dma2_lds = (size_t)4 * dma2_wave_f4(M) * 16 + 4 * kWaveQueueLds * sizeof(uint2);
-      // (static LDS of solve_po_kernel<.., kStream>, tools/kernel_resources.py: 28.2 KB compiled, 52.2 KB with the table interpreter)
-      const size_t solve_lds = (size_t)ctx->stream_blocks * solve_block_lds(ctx);
-      const uint64_t ppr = ctx->V.pixels_per_row;
-      pl.dma2 = dma2_allowed && M >= 2 && ppr >= 2 && ppr < (1ull << 31) && ctx->V.n / M < (1ull << 31) &&
-                dma2_lds + (ctx->stream_mode ? solve_lds : 0) <= 160u * 1024u;
-      if (pl.dma2) {
-        pl.lds = dma2_lds;
-        sa.bands = scan_bands(ctx->P);
-        uint32_t sh = 0;
-        while ((2ull << sh) < ppr) ++sh;                 // 2^sh < ppr <= 2^(sh+1)
-        sa.ppr_shift = sh;
-        sa.ppr_magic = (uint32_t)(((1ull << (32 + sh)) + ppr - 1) / ppr);
-      }
-    }
-    // frames with extra AOVs, all of them gaussian: the LDS-DMA form of the multi-column scan (LENTIL_SCAN_DMA_MULTI=0: never)
-    const size_t dmam_lds = dma_multi_lds(ctx);
-    pl.dma_multi = dma_multi_applies(ctx);
-    if (pl.dma_multi) {
-      ppt = 64 / M;
-      // the sum lanes come in passes of 64 float4 of the group's records: a pixel fewer per group where that saves the
-      // second pass (nine visits, nine AOVs: 7 x 10 float4 = two passes, 6 x 10 = one; 3.19 against 3.39 ms)
-      const uint32_t q = ctx->F.stride / 4;
-      if (ppt * q > 64 && 64 / q >= 1 && 4 * (64 / q) >= 3 * ppt) ppt = 64 / q;
-      if (const char *e = getenv("LENTIL_DMA_MULTI_PPT")) { const uint32_t f = (uint32_t)atoi(e); if (f >= 1 && f <= 64 / M) ppt = f; }
-      sa.ppt = ppt;
-      sa.tv_pad = ppt * M;
-      pl.lds = dmam_lds;
-      pl.multi = false;
-      pl.dma = false;
-      sa.dummy = ctx->d_dummy;
-      // (the column loads without the nontemporal hint: the 54-visit groups of nine-visit pixels do not end on 128-byte lines,
-      // and the line two groups share is then still in L2 for the second -- 3.05 against 3.16 ms alone; LENTIL_DMA_MULTI_NT=1)
-      sa.ring = dma_multi_ring(ctx) | ((getenv("LENTIL_DMA_MULTI_NT") && getenv("LENTIL_DMA_MULTI_NT")[0] == '1') ? 0u : 0x100u);
-    }
-    const uint64_t n_pixels = (ctx->V.n + M - 1) / M;
-    pl.n_tiles = (n_pixels + ppt - 1) / ppt;
-  }
-  lentil_hip_ctx::DirRegion reg;
-  if (pl.dma || pl.dma_multi) {
-    reg.x0 = ctx->V.pixel_x0; reg.y0 = ctx->V.pixel_y0; reg.row_stride = ctx->V.pixel_row_stride; reg.ppr = ctx->V.pixels_per_row;
-    reg.npix = ctx->V.n / M;
-  }
-  const int rc = prepare_direct(ctx, (pl.dma || pl.dma_multi) ? &reg : nullptr);
-  if (rc) return rc;
-  sa.F = ctx->F;
-  return LENTIL_OK;
-}
-
-// one scan launch over a chunk's range of the stream (ch.tile_begin/_end, ch.v_begin/_end) on the main stream
-static int launch_scan(lentil_hip_ctx *ctx, const ScanPlan &pl, const lentil_hip_ctx::Chunk &ch, DevCounters *ctr,
-                       unsigned *blocks_out, bool streamed_pass = false) {
-  ScanArgs sa = pl.sa;
-  // (LENTIL_SCAN_OUTSIDE_IN=1: a streamed pass scans the frame from its top and bottom edge inwards.  Measured neutral,
-  // 2.32-2.33 ms either way: the parked solves of the edge items then come early, but the straggler kernel only gets its
-  // registers when the scan's waves have left, scan_order in lentil_kernels.h)
-  const char *oi = getenv("LENTIL_SCAN_OUTSIDE_IN");
-  const bool outside_in = oi && oi[0] == '1';
-  sa.outside_in = (outside_in && streamed_pass) ? 1u : 0u;
-  sa.work = ctx->d_work + ch.v_begin;
-  sa.work_cap = ch.v_end - ch.v_begin;
-  sa.ctr = ctr;
-  sa.tile_begin = ch.tile_begin; sa.tile_end = ch.tile_end;
-  sa.v_begin = ch.v_begin; sa.v_end = ch.v_end;
-  const uint64_t max_blocks = (uint64_t)ctx->num_cu * 8;
-  uint64_t blocks;
-  unsigned multi_skipped = 0;
-  uint32_t scan_id;       // which kernel, for lentil_hip_debug_last_scan
-  // (a streamed pass's single launch: timed by its own dispatch, lentil_hip_last_timing)
-  const bool own_events = streamed_pass && (pl.dma || pl.dma_multi);
-  ctx->scan_kernel_timed = own_events;
-  if (pl.dma) {
-    // persistent, every wave draws four tiles at a time
-    blocks = (ch.tile_end - ch.tile_begin + 15) / 16;
-    // one block per CU: 1.07 ms alone against 0.98 with two, but a CU then has room (registers, LDS) for three solve
-    // blocks beside it, and a streamed pass ends when its solves do
-    uint64_t per_cu = ctx->stream_mode ? 1 : 2;
-    if (const char *e = getenv("LENTIL_DMA_BLOCKS")) per_cu = strtoull(e, nullptr, 10);
-    if (blocks > (uint64_t)ctx->num_cu * per_cu) blocks = (uint64_t)ctx->num_cu * per_cu;
-    if (blocks < 1) blocks = 1;
-    if (pl.dma2) {
-      blocks = (ch.tile_end - ch.tile_begin + 15) / 16;
-      if (blocks > (uint64_t)ctx->num_cu) blocks = (uint64_t)ctx->num_cu;
-      if (blocks < 1) blocks = 1;
-      // (a streamed pass may leave some CUs without a scanning block: those take a third resident solve block, scan_cus_pct;
-      // the blocks that do not scan are launched all the same and leave at once, see the kernel)
-      sa.skip_blocks = 0;
-      // (only where the pass is bound by its solves: 1080p with 256 draws -- 73 k draws a frame -- is not, 0.74 against 0.71 ms)
-      if (streamed_pass && ctx->scan_cus_pct < 100 && blocks == (uint64_t)ctx->num_cu && ctx->est_sum_total >= (1ull << 19))
-        sa.skip_blocks = (uint32_t)(blocks - ((uint64_t)ctx->num_cu * (uint64_t)ctx->scan_cus_pct + 99) / 100);
-      if (own_events) hipExtLaunchKernelGGL(scan_dma2_kernel, dim3((unsigned)blocks), dim3(256), pl.lds, ctx->stream, ctx->ev_scan_k[0], ctx->ev_scan_k[1], 0, sa);
-      else hipLaunchKernelGGL(scan_dma2_kernel, dim3((unsigned)blocks), dim3(256), pl.lds, ctx->stream, sa);
-      scan_id = LENTIL_SCAN_DMA2;
-    } else {
-      if (own_events) hipExtLaunchKernelGGL(scan_dma_kernel, dim3((unsigned)blocks), dim3(256), pl.lds, ctx->stream, ctx->ev_scan_k[0], ctx->ev_scan_k[1], 0, sa);
-      else hipLaunchKernelGGL(scan_dma_kernel, dim3((unsigned)blocks), dim3(256), pl.lds, ctx->stream, sa);
-      scan_id = LENTIL_SCAN_DMA;
-    }
-  } else if (pl.dma_multi) {
-    // persistent: a wave draws runs of 16 groups
-    blocks = (ch.tile_end - ch.tile_begin + 4 * kDmaMultiRun - 1) / (4 * kDmaMultiRun);
-    if (blocks > (uint64_t)ctx->num_cu * dma_multi_blocks_per_cu(ctx)) blocks = (uint64_t)ctx->num_cu * dma_multi_blocks_per_cu(ctx);
-    if (blocks < 1) blocks = 1;
-    // (scan_cus_pct: this kernel's blocks draw all their tiles from one counter, so fewer of them is all it takes -- the CUs
-    // left alone hold a third resident solve block)
-    multi_skipped = 0;
-    if (streamed_pass && ctx->scan_cus_pct_multi < 100 && blocks == (uint64_t)ctx->num_cu && dma_multi_blocks_per_cu(ctx) == 1) {
-      const uint64_t keep = ((uint64_t)ctx->num_cu * (uint64_t)ctx->scan_cus_pct_multi + 99) / 100;
-      multi_skipped = (unsigned)(blocks - keep);
-      blocks = keep;
-    }
-    if (own_events) hipExtLaunchKernelGGL(scan_dma_multi_kernel, dim3((unsigned)blocks), dim3(256), pl.lds, ctx->stream, ctx->ev_scan_k[0], ctx->ev_scan_k[1], 0, sa);
-    else hipLaunchKernelGGL(scan_dma_multi_kernel, dim3((unsigned)blocks), dim3(256), pl.lds, ctx->stream, sa);
-    scan_id = LENTIL_SCAN_DMA_MULTI;
-  } else if (pl.M) {
-    blocks = (ch.tile_end - ch.tile_begin + 3) / 4;
-    if (blocks > max_blocks) blocks = max_blocks;
-    if (pl.multi) hipLaunchKernelGGL(scan_uniform_multi_kernel, dim3((unsigned)blocks), dim3(256), pl.lds, ctx->stream, sa);
-    else hipLaunchKernelGGL(scan_uniform_kernel, dim3((unsigned)blocks), dim3(256), pl.lds, ctx->stream, sa);
-    scan_id = pl.multi ? LENTIL_SCAN_UNIFORM_MULTI : LENTIL_SCAN_UNIFORM;
-  } else {
-    blocks = (ch.v_end - ch.v_begin + 255) / 256;
-    if (blocks > max_blocks) blocks = max_blocks;
-    // runs of a pixel's visits are summed in their order (LENTIL_SCAN_RUNS=0: an atomic per visit and float, any order)
-    const bool runs = !(getenv("LENTIL_SCAN_RUNS") && getenv("LENTIL_SCAN_RUNS")[0] == '0');       // (read per launch: the tests switch it)
-    if (runs) hipLaunchKernelGGL(scan_runs_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, sa);
-    else hipLaunchKernelGGL(scan_ragged_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, sa);
-    scan_id = runs ? LENTIL_SCAN_RUNS : LENTIL_SCAN_RAGGED;
-  }
-  HIP_TRY(ctx, hipGetLastError());
-  if (blocks_out) *blocks_out = (unsigned)blocks;
-  ctx->last_scan[0] = scan_id;
-  ctx->last_scan[1] = pl.M ? sa.ppt : 0u;
-  ctx->last_scan[2] = pl.M ? (uint32_t)pl.lds : 0u;
-  ctx->last_scan[3] = (uint32_t)blocks;
-  ctx->last_scan_skipped = (pl.dma && pl.dma2) ? sa.skip_blocks : (pl.dma_multi ? multi_skipped : 0u);
-  return LENTIL_OK;
-}
-
-// ---------------------------------------------------------------------------------------
-// Streamed pass.  The chunked pass above cannot start a chunk's solves before the chunk's scan has ended, and
-// every chunk's first solve kernel brings its own ramp-down; solve kernels of several chunks resident at once take
-// the register file from the scan.  Here the whole stream is ONE scan launch that publishes items and first-batch
-// tasks as it finds them (publish_item), and the first round is one task queue followed by persistent solve waves:
-//   stream A (chunk 0's): solve_po_kernel<.., kStream>, `stream_blocks` blocks per CU, resident beside the scan
-//                         from the start of the pass
-//   main stream:          scan, then a second launch of the same kernel on the CUs' remaining room, then -- once
-//                         both have run dry -- the parked stragglers, the first accept and the later rounds
-//                         (ordinary queues written by the accept kernel).
-// Nothing on the device waits for a kernel that has not been submitted before it: under a profiler that runs
-// kernels one at a time, A starts after the scan and finds the queue complete.
-// Buffers are sized from the previous pass (twice what it found); an item that does not fit raises
-// DevCounters::fallback, the accept kernel then does nothing and the host redoes the draws with exact sizes.
 // ---------------------------------------------------------------------------------------
 // ---- first batches from the lens and the frame (lentil_batch_model.h) ---------------------------------------------
 // The calibration: bm_nx x bm_ny x bm_nz targets over the frame's field of view and inverse
@@ -2569,794 +2262,14 @@ static BatchModelDev batch_model_dev(const lentil_hip_ctx *ctx) {
   return m;
 }
 
-// The end of a streamed pass: its counters have arrived in `pinned`.  What they say -- everything fitted?  the lean tail's bet
-// held?  nobody gave up waiting? -- and, where not, the work that is left (can_fix; false for a pass whose frame has been
-// cleared since: its verdict is only counted).  Sizes the next pass from what this one found.
-static int streamed_finish(lentil_hip_ctx *ctx, StreamTail &t, const DevCounters *pinned, bool can_fix, bool *streamed) {
-  const int C = ctx->n_chunks;
-  lentil_hip_ctx::Chunk &ch = ctx->chunks[0];
-  DrawArgs &da = t.da;
-  const bool predicted = t.predicted, lean = t.lean, live = t.live;
-  const int blind_rounds = t.blind_rounds;
-  SlowRec *const slow_base = t.slow_base;
-  const uint32_t slow_cap_all = t.slow_cap_all;
-  const unsigned accept_blocks = t.accept_blocks;
-  int rc;
-  (void)live;
-  ctx->h_ctr.assign(pinned, pinned + C);
-  ctx->h_ctr_valid = true;
-  ctx->last_streamed = 1;
-  const DevCounters c = ctx->h_ctr[0];
-  ch.was_blind = true;
-  if (c.probe_snap[0]) {
-    // LENTIL_DISPATCH_PROBE: the first accept's last item was finished while blocks of its grid had not begun
-    char buf[640];
-    int n = snprintf(buf, sizeof buf, "[probe] epoch %u: accept blocks begun %u of %u when the last item was done; per XCD begun:", ctx->epoch, c.probe_snap[33], c.probe_snap[34]);
-    for (int x = 0; x < 8; ++x) n += snprintf(buf + n, sizeof buf - n, " %u", c.probe_snap[1 + x]);
-    const char *kinds[3] = {"second round's solve waves resident", "second round's straggler waves resident", "first round's straggler waves resident"};
-    for (int k = 0; k < 3; ++k) {
-      n += snprintf(buf + n, sizeof buf - n, " | %s:", kinds[k]);
-      for (int x = 0; x < 8; ++x) n += snprintf(buf + n, sizeof buf - n, " %u", c.probe_snap[9 + 8 * k + x]);
-    }
-    fprintf(stderr, "%s\n", buf);
-  }
-  if (c.fallback || c.stuck) {
-    {
-      // what made the pass give up, kept for lentil_hip_last_redo_note(): `fallback` bits 1 items, 2 result pool, 4 task queue,
-      // 8 a wave's pending flushes, 16 range queue, 32 the blind preparation's bounds (64, chunked passes only: a list of occlusion probes); `stuck` = (ticket << 2) | who waited (1 a
-      // publisher, 2 a resident solve wave, 3 a straggler wave)
-      char note[768];
-      snprintf(note, sizeof note,
-               "epoch %u: fallback 0x%llx stuck 0x%x (timeout %.0f ms)%s%s | items %llu/%u tasks %u/%u pool %llu/%llu ranges %u/%u | "
-               "scan blocks done %u publishers done %u rounds_used %llu | first batches %s, margin16 %u, blind passes before %u | "
-               "the wave that gave up: round %u parity %u, its queue's n_tasks %u head %u, accept blocks done %u begun %u, slot word 0x%x (epoch tag 0x%x), block %u",
-               ctx->epoch, (unsigned long long)c.fallback, c.stuck, (double)t.stuck_ticks * 1.0e-5,
-               c.stuck ? " waited: " : "", c.stuck ? ((c.stuck & 3u) == 1 ? "publisher" : (c.stuck & 3u) == 2 ? "resident solve wave" : "straggler wave") : "",
-               (unsigned long long)c.work_count, t.item_cap, c.n_tasks[0], t.task_cap, (unsigned long long)c.pool_used[0],
-               (unsigned long long)t.pool_cap, c.n_ranges, t.range_cap, c.scan_blocks_done, c.publishers_done,
-               (unsigned long long)c.rounds_used, predicted ? "modelled" : "plain", ctx->bm_margin16, ctx->last_blind - 1u,
-               c.stuck_info[0], c.stuck_info[1], c.stuck_info[2], c.stuck_info[7], c.stuck_info[3], c.stuck_info[4], c.stuck_info[5],
-               c.stuck_info[5] >> kTaskTagShift, c.stuck_info[6]);
-      ctx->redo_note = note;
-      if (c.stuck && (c.stuck & 3u) == 1u && ctx->d_ranges) {
-        // a publisher gave up on its range slot: what the slot holds now (every kernel of the pass has left), the slots around the
-        // cursor and the queue's counters as the host reads them -- a record that IS there was written and not seen
-        const uint32_t tk = c.stuck >> 2;
-        uint64_t w[4] = {0, 0, 0, 0};
-        if ((uint64_t)tk + 2 < ctx->range_cap)
-          (void)hipMemcpy(w, ctx->d_ranges + (tk ? tk - 1 : 0), sizeof w, hipMemcpyDeviceToHost);
-        char more[256];
-        snprintf(more, sizeof more, " | range slots from %u on (host read-back): %016llx %016llx %016llx %016llx, range_head %u",
-                 tk ? tk - 1 : 0, (unsigned long long)w[0], (unsigned long long)w[1], (unsigned long long)w[2], (unsigned long long)w[3], c.range_head);
-        ctx->redo_note += more;
-      }
-      if (getenv("LENTIL_STREAM_DEBUG")) fprintf(stderr, "[stream] note: %s\n", ctx->redo_note.c_str());
-    }
-    if (getenv("LENTIL_STREAM_DEBUG"))
-      fprintf(stderr, "[stream] redo: who %u ticket %u epoch %u range_head %u pubs_done %u scan_done %u | fallback %llu stuck %u | items %llu (cap %u) tasks %u (cap %u) pool %llu (cap %llu) ranges %u (cap %u)\n",
-              c.stuck & 3u, c.stuck >> 2, ctx->epoch, c.range_head, c.publishers_done, c.scan_blocks_done, c.fallback, c.stuck, c.work_count, t.item_cap, c.n_tasks[0], t.task_cap, c.pool_used[0], (unsigned long long)t.pool_cap,
-              c.n_ranges, t.range_cap);
-    if (getenv("LENTIL_STREAM_DEBUG")) {
-      HIP_TRY(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
-      HIP_TRY(ctx, hipEventSynchronize(ctx->ev[2]));
-      float ms_scan = 0.f, ms_all = 0.f;
-      (void)hipEventElapsedTime(&ms_scan, ctx->ev[0], ctx->ev[1]);
-      (void)hipEventElapsedTime(&ms_all, ctx->ev[0], ctx->ev[2]);
-      fprintf(stderr, "[stream] scan %.3f ms, pass until the read-back %.3f ms\n", ms_scan, ms_all);
-    }
-    if (getenv("LENTIL_STREAM_DEBUG"))
-      fprintf(stderr, "[stream] queues: n_tasks %u/%u task_head %u/%u n_active %u/%u active_head %u/%u accept_done %u/%u pool_used %llu/%llu\n",
-              c.n_tasks[0], c.n_tasks[1], c.task_head[0], c.task_head[1], c.n_active[0], c.n_active[1], c.active_head[0], c.active_head[1],
-              c.accept_done[0], c.accept_done[1], c.pool_used[0], c.pool_used[1]);
-    if (getenv("LENTIL_STREAM_DEBUG"))
-      fprintf(stderr, "[stream] stragglers: live %d waves_done %u/%u (round 1: %u) parked %u/%u heads %u/%u cap %u waves %u rounds_used %llu\n", (int)live,
-              c.waves_done[0], c.waves_started[0], c.waves_done[1], c.n_slow[0], c.n_slow[1], c.slow_head[0], c.slow_head[1],
-              da.slow_cap, da.slow_waves, c.rounds_used);
-    if (c.stuck) {
-      g_stat_stuck.fetch_add(1, std::memory_order_relaxed);
-      if (t.inject) g_stat_stuck_injected.fetch_add(1, std::memory_order_relaxed);
-      else {
-        std::lock_guard<std::mutex> lock(g_stall_notes_mutex);
-        if (g_stall_notes.size() < 8) g_stall_notes.push_back(ctx->redo_note + (t.deferred ? " | end deferred" : " | end awaited") + (can_fix ? "" : ", abandoned") +
-                                                              " | frame " + std::to_string(ctx->P.xres) + "x" + std::to_string(ctx->P.yres) + ", " + std::to_string(ctx->V.n) + " visits");
-      }
-    }
-    if (ctx->notes.size() < 8) ctx->notes.push_back(ctx->redo_note);
-    if (!can_fix) {
-      // abandoned: the frame this pass wrote into has been cleared since; what it lacked is counted, not done
-      if (c.stuck) ++ctx->n_stuck;
-      ++ctx->last_fallback;
-      ++ctx->totals.abandoned_incomplete;
-      ctx->last_rounds = (int)c.rounds_used;
-      if (!c.stuck) {
-        // (the scan and the publishers counted everything they met, whether or not it fitted: the next pass is sized from that)
-        const uint64_t n_items = c.work_count < ctx->V.n ? c.work_count : ctx->V.n;
-        ctx->have_total_est = true;
-        ctx->est_items_total = n_items; ctx->est_sum_total = c.sum_samples;
-      }
-      for (int ci = 0; ci < C; ++ci) ctx->chunks[ci].have_est = false;
-      *streamed = true;
-      return LENTIL_OK;
-    }
-    t.did_more = true;
-    if (c.stuck && c.rounds_used) {
-      // Stalled with draws already accepted: the frame holds a part of the pass.  It held nothing before (the gate at the
-      // top), so lentil_hip_redistribute wipes it and runs the whole pass again in the chunked form.
-      ++ctx->n_stuck;
-      ctx->stall_redo = true;
-      ctx->h_ctr_valid = false;
-      ctx->late_resolve_done = false;
-      *streamed = true;
-      return LENTIL_OK;
-    }
-    if (c.stuck) {
-      ++ctx->n_stuck;
-      HIP_TRY(ctx, hipMemsetAsync((char *)ctx->d_ctr + offsetof(DevCounters, stuck), 0, sizeof(unsigned int), ch.stream));
-    }
-    // did not fit: nothing was accepted.  Fresh queues, then the draws again the plain way, sized from the counters
-    ctx->h_ctr_valid = false;
-    ctx->late_resolve_done = false;
-    ++ctx->last_fallback;
-    HIP_TRY(ctx, hipMemsetAsync((char *)ctx->d_ctr + offsetof(DevCounters, n_tasks), 0,
-                                offsetof(DevCounters, inv_row_min) - offsetof(DevCounters, n_tasks), ch.stream));
-    HIP_TRY(ctx, hipMemsetAsync((char *)ctx->d_ctr + offsetof(DevCounters, fallback), 0, sizeof(unsigned long long), ch.stream));
-    DrawArgs db{};
-    init_draw_args(ctx, db);
-    if ((rc = enqueue_chunk_draws(ctx, 0, db, 3))) return rc;
-    HIP_TRY(ctx, hipStreamSynchronize(ch.stream));
-    int rounds = 3;
-    if (ch.n_items) { if ((rc = finish_rounds(ctx, 0, db, 3, &rounds))) return rc; }
-    ch.est_rounds = rounds;
-    ctx->last_rounds = rounds;
-  } else {
-    const uint64_t n_items = c.work_count < ctx->V.n ? c.work_count : ctx->V.n;
-    ch.have_est = true; ch.est_items = n_items; ch.est_sum = c.sum_samples; ch.est_rounds = (int)c.rounds_used;
-    if (c.tries) { ctx->mean_iters = (double)c.newton_iters / (double)c.tries; ctx->parked_frac = (double)c.slow_solves / (double)c.tries; }
-    int rounds = blind_rounds;
-    if (lean) ++ctx->n_lean;
-    // A pass whose first batches came from the model and left an item short all the same: the model's margin widens for the
-    // passes that follow (the item is served by further rounds as ever); with the margin at its cap the context stops
-    // betting on the lean tail until its camera set-up changes.
-    const bool short_after_all = predicted && n_items && (c.n_tasks[1] != 0u || (lean && c.n_active[blind_rounds & 1] != 0u));
-    // (an abandoned pass: what it still needed is counted, not done -- nobody can see its frame any more)
-    const bool open_end = n_items && ((lean && c.n_tasks[1] != 0u) || c.n_active[blind_rounds & 1] != 0);
-    if (open_end && !can_fix) {
-      ++ctx->totals.abandoned_incomplete;
-      if (ctx->notes.size() < 8) ctx->notes.push_back("abandoned before its end was looked at: the first accept had scheduled another round (lean tail's bet lost)");
-    } else if (open_end) {
-      t.did_more = true;
-    }
-    if (short_after_all) {
-      // (a pass that loses only now and then keeps betting: the margin comes back down after 16 passes without a loss)
-      ctx->bm_since_loss = 0;
-      if (ctx->bm_margin16 >= 4u) ctx->lean_ok = false;
-      else ctx->bm_margin16 += 1u;
-    }
-    if (predicted && !short_after_all && ++ctx->bm_since_loss >= 16u && ctx->bm_margin16 > 0u) { --ctx->bm_margin16; ctx->bm_since_loss = 0; }
-    if (!can_fix && open_end) {
-      if (lean) ++ctx->n_lean_lost;
-      rounds = (int)c.rounds_used + 1;
-    } else
-    if (lean && n_items && c.n_tasks[1] != 0u) {
-      // The lean tail's bet was lost: the first accept scheduled tasks, the accept behind it did nothing.  The round the
-      // ordinary way -- its solves (the queue is complete), their stragglers, the accept that was held back -- then whatever
-      // rounds follow.  (Rare: an item whose first batch the model sized too small; ~0.3 ms.)
-      ctx->h_ctr_valid = false;
-      ctx->late_resolve_done = false;
-      da.parity = 1; da.round = 1;
-      da.producers_done = nullptr; da.producers_total = 0;
-      da.slow_live = 0; da.slow_indirect = 0; da.slow_q = -1; da.slow_round = -1; da.slow_close = 1;
-      da.emit_live = 0; da.lean_gate = 0; da.no_reset = 1;
-      {
-        DrawArgs dr = da;       // (its parked solves go to the upper half of the records: the lower half holds the first round's results)
-        if (dr.slow) { dr.slow = slow_base + slow_cap_all / 2u; dr.slow_cap = slow_cap_all - slow_cap_all / 2u; }
-        launch_solve(ctx, dr, ch.stream, (unsigned)ctx->num_cu);
-      }
-      hipLaunchKernelGGL(reset_round_kernel, dim3(1), dim3(1), 0, ch.stream, ctx->d_ctr, 0u, 1u);
-      hipLaunchKernelGGL(accept_kernel<2>, dim3(accept_blocks), dim3(256), 0, ch.stream, da);
-      HIP_TRY(ctx, hipGetLastError());
-      da.no_reset = 0;
-      if ((rc = finish_rounds(ctx, 0, da, 2, &rounds))) return rc;
-      if (rounds > ch.est_rounds) ch.est_rounds = rounds;
-      ++ctx->n_lean_lost;
-    } else
-    if (n_items && c.n_active[blind_rounds & 1] != 0) {
-      ctx->h_ctr_valid = false;
-      ctx->late_resolve_done = false;
-      if ((rc = finish_rounds(ctx, 0, da, blind_rounds, &rounds))) return rc;
-      if (rounds > ch.est_rounds) ch.est_rounds = rounds;
-      if (lean) ++ctx->n_lean_lost;
-    } else if (lean) {
-      rounds = 1;       // one round of solves: the accept behind the first one only waited for that round's parked solves
-    }
-    ctx->last_rounds = rounds;
-  }
-  ctx->have_total_est = true;
-  ctx->est_items_total = ch.est_items; ctx->est_sum_total = ch.est_sum; ctx->est_rounds_total = ch.est_rounds;
-  // (should the next pass run chunked, its chunks look at their scans first: this pass knows nothing about them)
-  for (int ci = 0; ci < C; ++ci) ctx->chunks[ci].have_est = false;
-  *streamed = true;
-  return LENTIL_OK;
+// LENTIL_BLIND_ROUNDS: the solve/accept rounds a pass enqueues without looking, 1..8 (0: not set, the caller's own default)
+static int forced_blind_rounds() {
+  const char *e = getenv("LENTIL_BLIND_ROUNDS");
+  const int n = e ? atoi(e) : 0;
+  return !e ? 0 : (n < 1 ? 1 : (n > 8 ? 8 : n));
 }
 
-
-static int redistribute_streamed(lentil_hip_ctx *ctx, bool *streamed, bool *deferred) {
-  *streamed = false;
-  *deferred = false;
-  const lentil_params &P = ctx->P;
-  if (!ctx->stream_mode || P.cameraType != LENTIL_POLYNOMIAL_OPTICS || !ctx->have_total_est || ctx->V.n == 0)
-    return LENTIL_OK;
-  if (ctx->V.n > 0xFFFFFFF0ull) return LENTIL_OK;
-  if (no_tries(P)) return LENTIL_OK;         // (vignetting_retries < 0: a scan and a count, enqueue_chunk_draws)
-  if (probing(ctx)) return LENTIL_OK;      // (occlusion probes, host or device callback: answered between a round's solves and its accept -- the round-by-round form)
-  // Only into a frame that has been cleared since its last pass (every caller's order: clear, redistribute, resolve): a
-  // streamed pass whose waves give up waiting after draws have been accepted is recovered by wiping the frame and running
-  // the pass again, which must not cost an earlier pass's sums.  A second pass into the same frame takes the chunked form,
-  // whose kernels never wait for one another.
-  if (!ctx->cleared_since_pass) return LENTIL_OK;
-  // A context whose resident waves have given up waiting before (250 ms each time, then the redo) stops trying: at once
-  // where lentil_hip_create found its streams sharing hardware queues (GPU_MAX_HW_QUEUES below 4: a kernel then sits behind
-  // the one it waits for, every pass), after the third time anywhere else (a profiler that serialises kernels, a crowded GPU).
-  if (ctx->n_stuck >= (ctx->streams_concurrent ? 3u : 1u)) return LENTIL_OK;
-  // Streaming pays where the scan is most of the pass.  With many draws the chunked pass is ahead (highlight-heavy
-  // frame: 114 ms against 135 ms; 15 M draws: 16.6 against 18.4 ms -- solve waves placed while the scan's are
-  // resident keep running slower long after those have left, see launch_chunk_rounds), and so it is with extra
-  // AOVs, whose scan kernel leaves the solve waves less room (config 4: 10.8 against 11.5 ms).
-  // (Round 3: ... or below one draw per 24 visits, whichever is more -- what streaming buys is the scan running beside the
-  // solves, and a frame whose scan is long against its draws gains most: BASELINE config 5, 8K with 9.3 M draws, 12.9 ms
-  // streamed against 16.3 chunked; 4K with 3.1 M draws 4.3 against 4.8 ms, with 6-48 M draws within +-5 % either way.)
-  {
-    const uint64_t by_visits = ctx->stream_below_set ? 0ull : ctx->V.n / 24ull;
-    if (ctx->est_sum_total >= (ctx->stream_below > by_visits ? ctx->stream_below : by_visits)) return LENTIL_OK;
-  }
-  if (ctx->V.n_extra && !dma_multi_applies(ctx)) return LENTIL_OK;
-  // ... nor where a scan block could not share a CU's LDS with even one resident solve block (scan_dma_multi_kernel from twelve
-  // extra AOVs on, from nine beside the table interpreter): whichever the dispatcher places first keeps the other out, and where
-  // that is the solve blocks they wait for a scan that cannot start until a publisher gives up -- 250 ms, then the redo
-  // (tests/test_gpu_scan_shapes.py: second passes with 14 and 15 extra AOVs)
-  if (ctx->V.n_extra && dma_multi_lds(ctx) + 512u + solve_block_lds(ctx) > 160u * 1024u) return LENTIL_OK;
-  lentil_hip_ctx::Chunk &ch = ctx->chunks[0];
-  // One streamed pass per device at a time: the resident kernels of two of them could keep each other's scan off the chip.
-  // A context that finds another one's streamed pass in flight does not wait for it: its pass runs in the chunked form,
-  // whose kernels never wait for anything (LENTIL_STREAM_WAIT=1: wait, as rounds 2 did).
-  static const bool wait_for_turn = getenv("LENTIL_STREAM_WAIT") && getenv("LENTIL_STREAM_WAIT")[0] == '1';
-  DeviceTurn turn(ctx);
-  if (!turn.take(wait_for_turn)) return LENTIL_OK;
-  DrawArgs da{};
-  init_draw_args(ctx, da);
-  ++ctx->n_streamed;
-  g_stat_streamed.fetch_add(1, std::memory_order_relaxed);
-  da.inject_stall = (ctx->inject_stall_at > 0 && ctx->n_streamed == (uint64_t)ctx->inject_stall_at) ? 1 : 0;
-  const uint64_t nch = (uint64_t)da.n_channels;
-  uint64_t items = 2 * ctx->est_items_total + 4096;
-  if (items > ctx->V.n) items = ctx->V.n;
-  const uint64_t sum = 2 * ctx->est_sum_total + (1ull << 20);
-  const uint64_t units = chunk_units(P, nch, sum, items);
-  if (units > ctx->max_pool_units) return LENTIL_OK;       // sub-batches: the chunked pass knows how
-  int rc;
-  if ((rc = size_chunk_buffers(ctx, ch, items, units))) return rc;
-  bind_chunk_buffers(ch, da);
-  ScanPlan plan;
-  if ((rc = plan_scan(ctx, plan))) return rc;
-  da.F = ctx->F;                // (plan_scan decides where the direct sums go and whether splats are flagged)
-  // the wipe clear_frame left on the chunk stream (clear_pending) rides beside the scan only where the scan leaves the splat
-  // accumulators alone: own sums to FrameDev::dir, splats flagged
-  if (ctx->clear_pending && !(ctx->F.dir && ctx->F.touched) && (rc = join_clear(ctx))) return rc;
-  ch.tile_begin = 0; ch.tile_end = plan.n_tiles;
-  ch.v_begin = 0; ch.v_end = ctx->V.n;
-  for (int ci = 1; ci < ctx->n_chunks; ++ci) {
-    lentil_hip_ctx::Chunk &o = ctx->chunks[ci];
-    o.tile_begin = o.tile_end = plan.n_tiles; o.v_begin = o.v_end = ctx->V.n; o.n_items = 0;
-  }
-  ctx->epoch = (ctx->epoch + 1u) & 0x3FFFFFu;
-  if (ctx->epoch == 0u) {
-    // the 22-bit tag has come round: wipe what older passes left in the queues
-    ctx->epoch = 1u;
-    HIP_TRY(ctx, hipMemsetAsync(ch.tasks[0], 0, ch.task_cap * sizeof(Task), ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(ch.tasks[1], 0, ch.task_cap * sizeof(Task), ctx->stream));
-    if (ctx->d_ranges) HIP_TRY(ctx, hipMemsetAsync(ctx->d_ranges, 0, ctx->range_cap * sizeof(uint64_t), ctx->stream));
-    if (ch.slow) HIP_TRY(ctx, hipMemsetAsync(ch.slow, 0, ch.slow_cap * sizeof(SlowRec), ctx->stream));
-  }
-  const uint32_t retries = (uint32_t)(P.vignetting_retries < 0 ? 0 : P.vignetting_retries);
-  const bool few = ctx->est_sum_total < ctx->slow_below;
-  // How long a resident wave waits for its queue slot before it declares the pass stuck (the host then redoes the pass the
-  // chunked way).  A wave may rightly wait for a whole scan -- its slot gets its end marker when the scan ends --, so: 250 ms
-  // while nothing is known, else sixteen times the longest pass this context has seen, at least 30 ms (round 5: a stall,
-  // rare as it is, then costs tens of milliseconds and not a quarter of a second; LENTIL_STUCK_MS overrides).
-  uint64_t stuck_ticks = 0;
-  {
-    static const double forced_ms = getenv("LENTIL_STUCK_MS") ? atof(getenv("LENTIL_STUCK_MS")) : 0.0;
-    // (the estimate comes from earlier passes: it holds for a pass no larger than the one that set it -- more visits, or a
-    // quarter more draws expected, and nothing is known again: 250 ms -- and every time-out this context has hit doubles it,
-    // so that a slow box, a shared GPU or a profiler does not turn into a run of false stalls, each a wipe and a chunked redo)
-    double ms = 250.0;
-    if (ctx->longest_pass_ms > 0.0 && ctx->V.n <= ctx->longest_pass_visits &&
-        ctx->est_sum_total <= ctx->longest_pass_sum + ctx->longest_pass_sum / 4) {
-      ms = 16.0 * ctx->longest_pass_ms * (double)(1u << (ctx->n_stuck < 4 ? ctx->n_stuck : 4));
-      if (ms < 30.0) ms = 30.0;
-      if (ms > 250.0) ms = 250.0;
-    }
-    if (forced_ms > 0.0) ms = forced_ms;
-    stuck_ticks = (uint64_t)(ms * 1.0e5);
-  }
-
-  PublishArgs pa{};
-  pa.P = P;
-  pa.V = ctx->V;
-  StreamPub &pub = pa.S;
-  pub.epoch = ctx->epoch;
-  pub.n_channels = (uint32_t)nch;
-  pub.retries = (int32_t)retries;
-  pub.extra_num = ctx->est_sum_total < ctx->extra_below ? ctx->extra_num : 0u;
-  pub.extra_const = ctx->est_sum_total < ctx->extra_below ? ctx->extra_const : 0u;
-  pub.item_cap = (uint32_t)(ch.item_cap < 0xFFFFFFF0ull ? ch.item_cap : 0xFFFFFFF0ull);
-  pub.task_cap = da.task_cap;
-  pub.pool_cap = da.pool_cap;
-  pub.hdr = ch.hdr; pub.prog = ch.prog; pub.active0 = ch.active[0]; pub.tasks0 = ch.tasks[0];
-  // range queue: one record per flush of a wave queue (at most one per 64 visits, plus one per wave and tile)
-  {
-    const uint64_t need = ctx->V.n / 64 + 2 * plan.n_tiles + 65536;
-    if (need > ctx->range_cap) {
-      if ((rc = grow(ctx, &ctx->d_ranges, need))) return rc;
-      ctx->range_cap = need;
-      HIP_TRY(ctx, hipMemsetAsync(ctx->d_ranges, 0, need * sizeof(uint64_t), ctx->stream));
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
-  }
-  plan.sa.ranges = ctx->d_ranges;
-  plan.sa.range_cap = (uint32_t)(ctx->range_cap < 0xFFFFFFF0ull ? ctx->range_cap : 0xFFFFFFF0ull);
-  plan.sa.epoch = ctx->epoch;
-  plan.sa.end_ranges = (uint32_t)ctx->publish_waves;
-  plan.sa.flush_each_tile = ctx->est_items_total < (1u << 16) ? 1u : 0u;
-  pa.ctr = ctx->d_ctr;
-  pa.stuck_ticks = stuck_ticks;
-  da.stuck_ticks = stuck_ticks;
-  pa.work = ctx->d_work;
-  pa.work_cap = ctx->V.n;
-  pa.ranges = ctx->d_ranges;
-  pa.range_cap = plan.sa.range_cap;
-
-  da.ctr = ctx->d_ctr;
-  da.retries = (int32_t)retries;
-  da.work = ctx->d_work;
-  da.work_cap = ctx->V.n;
-  da.blind = 0u;
-  da.n_items = pub.item_cap;
-  da.parity = 0; da.round = 0;
-  da.epoch = ctx->epoch;
-  if (!few) da.slow = nullptr;              // parking is for passes with few draws (DrawArgs::slow_below)
-
-  unsigned scan_blocks = 0;
-  const auto pass_t0 = std::chrono::steady_clock::now();
-  ht_mark(ctx, "first_launch");
-  const bool calibrates_now = ctx->predict && !ctx->bm_valid;       // (this pass's host time holds the calibration kernel's)
-  // the first-batch model's calibration, should the camera set-up have changed: on the main stream, ahead of the event the
-  // publishers (who read the table) wait for
-  if (ctx->predict && nch == 1 && (rc = ensure_batch_model(ctx))) return rc;
-  // (the scan's start for lentil_hip_last_timing: the host work since the pass began -- sizing, the plan -- is not the kernel's)
-  HIP_TRY(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-  if ((rc = launch_scan(ctx, plan, ch, ctx->d_ctr, &scan_blocks, true))) return rc;
-  ctx->last_scan_launches = 1;
-  HIP_TRY(ctx, hipEventRecord(ch.scanned, ctx->stream));
-  HIP_TRY(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-  HIP_TRY(ctx, hipEventRecord(ctx->scans_done, ctx->stream));
-  // cryptomatte AOVs: the adds of the visits that stay in their pixel need the scan's work lists and nothing else of the
-  // pass -- beside the draws, on the spare stream, where the runtime has one (LENTIL_CRYPTO_OVERLAP=0: after the pass)
-  static const bool crypto_overlap = !(getenv("LENTIL_CRYPTO_OVERLAP") && getenv("LENTIL_CRYPTO_OVERLAP")[0] == '0');
-  if (ctx->crypto && ctx->aux_stream && crypto_overlap) {
-    HIP_TRY(ctx, hipStreamWaitEvent(ctx->aux_stream, ctx->scans_done, 0));
-    if ((rc = crypto_enqueue_direct(ctx, ctx->aux_stream))) return rc;
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_crypto, ctx->aux_stream));
-    ctx->crypto_direct_enqueued = true;
-  }
-
-  // The publishers and A, resident beside the scan (the counters they poll were cleared by the memset ahead of
-  // ev[0]).  Submitted AFTER what they wait for -- the scan, then the publishers: should the streams share a
-  // hardware queue, each finds its producer ahead of it there.
-  // As many resident solve blocks per CU as leave a scan block its LDS.  (Round 6: the table interpreter's blocks hold 52 KB each --
-  // two of them and an 80 KB scan_dma_kernel block do not fit a CU's 160 KB, and where the dispatcher placed the solve blocks
-  // first no scan block ever found room: the resident waves waited for a scan that could not start until a publisher gave up,
-  // 250 ms, then the redo.  That was the "odd stalled pass" of small frames run through the interpreter -- every test that runs
-  // its second pass with lentil_hip_set_lens_mode(ctx, 1) --, found when the library began to count its stalls.  plan_scan only
-  // budgeted for scan_dma2_kernel.)
-  unsigned a_per_cu = (unsigned)ctx->stream_blocks;
-  {
-    const size_t solve_lds = solve_block_lds(ctx);
-    while (a_per_cu > 1u && plan.lds + 512u + (size_t)a_per_cu * solve_lds > 160u * 1024u) --a_per_cu;
-  }
-  unsigned a_blocks = (unsigned)ctx->num_cu * a_per_cu;
-  // CUs the scan leaves alone (scan_cus_pct) have registers for one more resident solve block
-  if (ctx->last_scan_skipped && a_per_cu == 2u) a_blocks += ctx->last_scan_skipped;
-  (void)scan_blocks;
-  // Live straggler queue: solve_slow_kernel is launched behind the publishers (who end with the scan) and takes the parked
-  // solves as they come, one wave per CU.  (Round 3, from the timeline: its waves are placed as the first solve waves
-  // leave -- the idle ones do at once when the publishers' end markers arrive --, not in the registers the scan gives
-  // back: a wave's registers are one contiguous range.)
-  const bool live = da.slow != nullptr && P.cameraType == LENTIL_POLYNOMIAL_OPTICS;
-  int blind_rounds = ctx->est_rounds_total < 2 ? 2 : (ctx->est_rounds_total > 6 ? 6 : ctx->est_rounds_total);
-  if (const char *e = getenv("LENTIL_BLIND_ROUNDS")) { blind_rounds = atoi(e); if (blind_rounds < 1) blind_rounds = 1; if (blind_rounds > 8) blind_rounds = 8; }
-  // Second round beside the first accept: the accept kernel hands out the next round's tasks as it goes (tagged slots,
-  // end markers from its last block), a kStream solve kernel -- one block per CU, which fits beside four accept blocks
-  // -- takes them as they come, the straggler kernel beside both.  Launched AFTER the accept, so that a profiler that
-  // serialises kernels runs them in an order that completes.
-  // (Round 4: also in passes that park nothing -- more draws than LENTIL_SLOW_BELOW, BASELINE config 5 on one GPU: 4 560 items
-  // x 2 048 draws --, whose first accept takes 0.65 ms and whose second round used to wait for all of it: 11.7 -> see DESIGN
-  // section 5.  No straggler kernels there, just the accept feeding the resident second-round solves.)
-  const bool overlap_plain = da.slow == nullptr && nch == 1 && P.cameraType == LENTIL_POLYNOMIAL_OPTICS;
-  const bool overlap = (live || overlap_plain) && blind_rounds >= 2;
-  // ... and the first accept does not wait for the first round's stragglers either (accept_item<1> / <2>): one
-  // straggler queue and one solve_slow_kernel launch for both rounds, closed by the second round's solve kernel.
-  const bool decoupled = live && overlap && nch == 1;
-  // (A queue and a solve_slow_kernel launch per round, as ever: ONE kernel for both rounds would wait for end markers from
-  // kernels submitted after it -- the first accept, the second round's solves -- and where two of the pass's streams share
-  // a hardware queue, the default with the runtime's 4, those sit behind it in that queue: 250 ms, then the chunked redo.
-  // The second round parks into the upper half of the record buffer, its kernel follows the first round's on their stream.)
-  SlowRec *const slow_base = da.slow;
-  const uint32_t slow_cap_all = da.slow_cap;
-  da.unknown_credit = ctx->unknown_credit;
-  // (one straggler wave per CU; LENTIL_SLOW_WAVES_PER_CU, up to 4 -- measured on config 4, whose rounds end in hundreds
-  // of parked solves at once: 9.15 / 9.18 / 9.35 / 9.46 ms with 1 / 2 / 3 / 4, the waves take from the solve kernel)
-  const int slow_per_cu = ctx->slow_waves_per_cu;
-  if (ctx->parked_frac > 1.0 / 256.0) ctx->park_dry_seen = true;
-  const bool dry_only = ctx->park_dry_only >= 0 ? ctx->park_dry_only != 0 : ctx->park_dry_seen;
-  // (Round 6: four per CU where parked solves are the outliers they are meant to be -- beauty-only frames, the live queue.  The
-  // straggler kernel had become what the pass ends on: 2 300 parked solves of a headline frame, 27 000 iterations at ~3 us each,
-  // are 320 us of work for 256 waves and half of it was still to do when the solve kernel's last wave left; with 1 024 waves
-  // it ends with the solve kernel but for the solves that run all 100 iterations.  2.011 -> 1.989 ms, eight interleaved runs of
-  // 60 steps each, gpurun_out/r06s05.  Config 4 parks dry waves' lanes only and keeps one.)
-  const uint32_t slow_default = (nch == 1 && ctx->V.n_extra == 0 && !dry_only) ? 4u : 1u;
-  const uint32_t slow_waves_all = (uint32_t)ctx->num_cu * (slow_per_cu >= 1 && slow_per_cu <= 4 ? (uint32_t)slow_per_cu : slow_default);
-  if (decoupled) { da.slow_indirect = 1; da.slow_cap = slow_cap_all / 2u > slow_waves_all ? slow_cap_all / 2u - slow_waves_all : 0u; }      // (its end markers stay below the upper half)
-  // B: a second solve launch behind the scan, in passes without a live queue.  (Measured, round 3: with the straggler
-  // kernel's wave on one of a CU's SIMDs the blocks of this launch are not placed before the first launch's blocks leave --
-  // zero iterations in every pass looked at: a pass with a live queue has none.)
-  unsigned b_blocks = 0;
-  if (!live) {
-    int b_per_cu = ctx->solve_max_blocks - ctx->stream_blocks;
-    if (b_per_cu < 1) b_per_cu = 1;
-    const uint64_t want = (nch * (ctx->est_sum_total / 64 + ctx->est_items_total) + 3) / 4;
-    uint64_t b = (uint64_t)ctx->num_cu * (uint64_t)b_per_cu;
-    if (want < b) b = want < 1 ? 1 : want;
-    b_blocks = (unsigned)b;
-  }
-  da.slow_live = live ? 1 : 0;
-  // A live queue takes every solve that reaches slow_at iterations -- outliers, by the measure of the previous pass.  With
-  // a lens where such solves are not outliers (the petzval table: 3 % of all solves, 62 000 a frame, each a whole wave
-  // of the straggler kernel: 12 ms a frame against 10 chunked) only waves running dry park, and only their last lanes.
-  // (It stays that way for the lens: a pass that parks dry waves' lanes only says nothing about what a live queue would get.)
-  da.slow_dry_only = dry_only ? 1 : 0;
-  // (the first round parks only once the scan has ended: 1 070 parked solves per headline pass instead of 2 486)
-  da.slow_after_producers = 1;
-  da.slow_waves = live ? slow_waves_all : 0u;
-  da.producers_done = &ctx->d_ctr->publishers_done;
-  da.producers_total = (uint32_t)ctx->publish_waves;
-  pa.end_tasks = (a_blocks + b_blocks) * 4u;       // every first-round solve wave may hold one ticket past the last task
-  // First batches from the lens and the frame (lentil_batch_model.h): every item is published with the traces it is expected
-  // to need, so that the first accept finds nothing to schedule and the pass can do without a second round (lean tail, below)
-  // (Not for items with very many draws each -- BASELINE config 5's 2 048: their first accept is long, 0.3-0.65 ms, and the
-  // second round that runs beside it is all but free, while its traces inside the first round are throughput; the bands of
-  // that frame, each alone on one GPU, took 5-19 % longer with the lean tail: profiles/r05_emulated_bands.txt.)
-  const bool few_draws_per_item = ctx->est_items_total == 0 || ctx->est_sum_total / ctx->est_items_total <= ctx->predict_max_draws;
-  const bool predict = ctx->predict && decoupled && few_draws_per_item;
-  if (predict && ctx->bm_valid) pub.model = batch_model_dev(ctx);        // (calibrated ahead of the scan, above)
-  const bool predicted = predict && pub.model.land != nullptr;
-  // The lean tail (below): known before anything is launched -- the solve and straggler kernels count parked solves per item for
-  // accept_kernel<3> (DrawArgs::item_ready) in such a pass.
-  // (LENTIL_INJECT_STALL stalls the second round's resident solve waves: that pass keeps its second round in flight)
-  const bool lean_pass = decoupled && predicted && ctx->lean_ok && blind_rounds <= 2 && !da.inject_stall;
-  // Round 6: the first accept takes the items whose parked solves are through, whole, and leaves the others to the accept behind
-  // the stragglers (accept_kernel<3>).  For frames the wide walk serves: <= 64 retries, records of <= 64 floats.
-  uint32_t add_floats = 1;
-  for (uint32_t k = 0; k < ctx->F.n_aovs; ++k) if (!(ctx->F.closest_mask & (1u << k))) add_floats += 4;
-  const bool ready_accept = lean_pass && retries <= kAcceptWinRetries && add_floats <= 64u;
-  da.item_ready = ready_accept ? 1 : 0;
-  HIP_TRY(ctx, hipStreamWaitEvent(ctx->pub_stream, ctx->ev[0], 0));
-  hipLaunchKernelGGL(publish_kernel, dim3((unsigned)ctx->publish_waves), dim3(64), 0, ctx->pub_stream, pa);
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipEventRecord(ctx->pub_done, ctx->pub_stream));
-  if (live) {
-    // (behind the publishers on their stream: they end with the scan, whose registers this kernel's waves need)
-    hipLaunchKernelGGL(solve_slow_kernel, dim3(da.slow_waves), dim3(64), coop_lds_bytes(ctx->hlens.n_terms), ctx->pub_stream, da);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_slow, ctx->pub_stream));
-  }
-  HIP_TRY(ctx, hipStreamWaitEvent(ch.stream, ctx->ev[0], 0));
-  da.instance = 0;
-  launch_solve_po<true>(ctx, da, ch.stream, a_blocks);
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipEventRecord(ch.done, ch.stream));
-
-  const uint64_t acc_max = (uint64_t)ctx->num_cu * (uint64_t)(ctx->accept_stream_blocks < 1 ? 1 : ctx->accept_stream_blocks);
-  const uint64_t acc_want = ctx->est_items_total + ctx->est_items_total / 4 + 1;
-  const unsigned accept_blocks = (unsigned)(acc_want > acc_max ? acc_max : acc_want);
-  hipStream_t tail = ctx->stream;       // the stream the pass's last kernels and its counter read-back are on
-  bool lean = false;                    // lean tail (below): no second round in flight
-  if (decoupled) {
-    // ---- the decoupled pass with its chain of kernels laid along streams: a dependency that crosses streams costs
-    // 40-90 us (event, barrier packet, a queue waking up) where a kernel behind its predecessor on ONE stream costs ~2:
-    //   chunk stream : A -> first accept                      (the accept starts as the last first-round solve ends)
-    //   main stream  : scan -> second round's solves          (released by what the first accept waited for)
-    //   straggler st.: publishers -> stragglers of round one -> of round two -> second accept -> later rounds' accepts
-    //                  -> the resolve's second half -> counter read-back       (each behind the kernel it ends last)
-    // The only cross-stream waits left on the critical path release kernels that then sit waiting for tasks anyway.
-    // (Round 4: everything from the second round's stragglers on sits on THEIR stream -- the second accept follows the kernel
-    // that ends last, solve_slow_kernel of round two, in-stream; what else it needs -- the second round's solves, the first
-    // accept, the first round's stragglers -- has ended before that kernel does, so those waits find their events fired.
-    // On the publishers' stream the accept came ~60 us after the stragglers' end: three cross-stream waits in a row.)
-    hipStream_t ps = ctx->slow1_stream;
-    HIP_TRY(ctx, hipStreamWaitEvent(ch.stream, ctx->pub_done, 0));       // (both long past when A ends)
-    HIP_TRY(ctx, hipStreamWaitEvent(ch.stream, ctx->scans_done, 0));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_round, ch.stream));
-    // (lean tail: no next round's solve waves share the CUs with the first accept -- a block per item, as many as fit)
-    unsigned accept1_blocks = accept_blocks;
-    if (ready_accept) {
-      // accept_kernel<3> waits for nothing and is what stands between the solve kernel's end and the touched groups' resolve:
-      // a block per item where that many fit (4 per CU: 4 x 20.7 KB of LDS beside a straggler wave's 10, 16 waves of <= 96 registers)
-      const uint64_t m = (uint64_t)ctx->num_cu * (uint64_t)ctx->ready_blocks;
-      accept1_blocks = (unsigned)(acc_want > m ? m : acc_want);
-    }
-    const bool resolves_early = ctx->F.dir && ctx->F.touched && ctx->n_chunks >= 2 && !ctx->comm && !ctx->closest_deferred;
-    // With accept_kernel<3> the frame's resolve does not wait for the first accept.  The whole frame is resolved behind the scan
-    // -- the pixels' own sums are complete then, the HBM is idle and the solve waves do not need it --, the groups of pixels
-    // the first accept's draws land in are resolved again behind it (about half of a headline frame's groups: 86 us where
-    // the whole frame takes 130), the few groups of the last accept once more at the end.  (The accept behind the stragglers
-    // has a few items, so the whole-frame resolve behind the first accept would be what the pass ends on.)
-    const bool resolve_after_scan = resolves_early && ready_accept;
-    if (resolve_after_scan) {
-      hipStream_t rs = ctx->chunks[1].stream;
-      if (ctx->clear_pending) HIP_TRY(ctx, hipStreamWaitEvent(rs, ctx->ev_clear, 0));      // (it reads the accumulators clear_frame is wiping on the chunk stream)
-      HIP_TRY(ctx, hipStreamWaitEvent(rs, ctx->scans_done, 0));
-      if ((rc = launch_resolve_half(ctx, rs, 0u))) return rc;
-    }
-    {
-      DrawArgs d0 = da;
-      d0.emit_live = lean_pass ? 0 : 1;       // (lean tail: nobody is waiting for tasks)
-      d0.lean_defer = lean_pass ? 1 : 0;
-      d0.end_tasks = (uint32_t)ctx->num_cu * 4u;
-      if (ready_accept) hipLaunchKernelGGL(accept_kernel<3>, dim3(accept1_blocks), dim3(256), 0, ch.stream, d0);
-      else hipLaunchKernelGGL(accept_kernel<1>, dim3(accept1_blocks), dim3(256), 0, ch.stream, d0);
-      HIP_TRY(ctx, hipGetLastError());
-      HIP_TRY(ctx, hipEventRecord(ctx->ev_acc1, ch.stream));
-    }
-    if (resolves_early) {
-      hipStream_t rs = ctx->chunks[1].stream;
-      HIP_TRY(ctx, hipStreamWaitEvent(rs, ctx->ev_acc1, 0));
-      if ((rc = launch_resolve_half(ctx, rs, resolve_after_scan ? 1u : 0u))) return rc;
-      HIP_TRY(ctx, hipEventRecord(ctx->ev_res, rs));
-      ctx->early_resolve_pending = true;
-    }
-    // Lean tail (first batches from the model): the first accept is expected to schedule nothing -- no second round's solve and
-    // straggler kernels, no waiting for them: the accept of the items that met parked solves follows the first accept on its
-    // stream, behind the first round's stragglers.  Should the first accept have scheduled tasks after all, that accept does
-    // nothing (DrawArgs::lean_gate) and the round is run by streamed_finish.
-    lean = lean_pass;
-    if (lean) {
-      hipStream_t ls = ch.stream;
-      da.parity = 1; da.round = 1;
-      HIP_TRY(ctx, hipStreamWaitEvent(ls, ctx->ev_slow, 0));      // the first round's stragglers
-      hipLaunchKernelGGL(reset_round_kernel, dim3(1), dim3(1), 0, ls, ctx->d_ctr, 0u, 1u);
-      {
-        DrawArgs d2 = da;
-        d2.lean_gate = 1;
-        d2.slow_indirect = 0; d2.slow_cap = slow_cap_all; d2.slow_live = 0;
-        hipLaunchKernelGGL(accept_kernel<2>, dim3(accept_blocks), dim3(256), 0, ls, d2);
-      }
-      HIP_TRY(ctx, hipGetLastError());
-      da.slow_indirect = 0; da.slow_cap = slow_cap_all; da.slow_live = 0;
-      if (ctx->early_resolve_pending) {
-        HIP_TRY(ctx, hipStreamWaitEvent(ls, ctx->ev_res, 0));
-        if ((rc = launch_resolve_half(ctx, ls, 2u))) return rc;
-        ctx->late_resolve_done = true;
-      }
-      tail = ls;
-    } else {
-    const char *overlap_env = getenv("LENTIL_OVERLAP_ACCEPT");      // (read per pass: the tests switch it)
-    const bool overlap_accept = !(overlap_env && overlap_env[0] == '0');
-    for (int round = 1; round < blind_rounds; ++round) {
-      da.parity = round & 1; da.round = round;
-      DrawArgs d1 = da;
-      d1.slow_after_producers = 0;      // (its straggler kernel runs beside it from the start)
-      d1.slow_indirect = 0;
-      if (round == 1) {
-        d1.no_reset = 1;
-        d1.producers_done = &ctx->d_ctr->accept_final[0];      // (set behind the queue's end markers)
-        d1.producers_total = 1u;
-        d1.slow = slow_base + slow_cap_all / 2u;
-        d1.slow_cap = slow_cap_all - slow_cap_all / 2u - d1.slow_waves;
-        // Round 5: the second round's resident solve and straggler kernels start BEHIND the first accept, not beside it.  Beside
-        // it they were waiting -- holding registers and LDS -- for end markers that the accept's LAST block writes, and about one
-        // such pass in 25 found only an eighth (or seven eighths) of the accept's blocks ever begun: whole XCDs' shares of the
-        // grid stayed undispatched until the waiting waves gave up (250 ms, then the redo; lentil_hip_last_redo_note: "accept
-        // blocks done 64 begun 64" of 512).  The blocks that did run had served every item, so nothing was wrong but the wait.
-        // A kernel of a pass may spin only on kernels that hold all the resources they will ever need.  What this costs is the
-        // head start of the second round's solves (~0.1 ms of a pass that has a second round at all; the lean tail has none).
-        // Round 6: beside it again, by default.  Since the end markers of an emitting accept are written by the block that finishes
-        // the pass's LAST ITEM (DevCounters::accept_items_done), not by the grid's last block, a share of the grid that is never
-        // dispatched keeps nobody waiting; soaked with the dispatch probe's build armed (tools/sessions_r06/r06_session26.sh: 1 600
-        // passes with a second round in flight -- config 5's bands, the headline without the first-batch model --, no stall, no
-        // probe event; profiles/r06_overlap_accept_soak.txt) and worth 13 % of a config-5 band's pass.  LENTIL_OVERLAP_ACCEPT=0:
-        // behind it.
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, overlap_accept ? ctx->ev_round : ctx->ev_acc1, 0));
-        launch_solve_po<true>(ctx, d1, ctx->stream, (unsigned)ctx->num_cu);
-      } else {
-        d1.producers_done = nullptr; d1.producers_total = 0;
-        d1.slow_cap = slow_cap_all;
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_round, ps));                   // behind the accept that filled this round's queues
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_round, 0));
-        launch_solve_po<false>(ctx, d1, ctx->stream, (unsigned)ctx->num_cu);
-      }
-      HIP_TRY(ctx, hipGetLastError());
-      HIP_TRY(ctx, hipEventRecord(ctx->ev_solve, ctx->stream));
-      if (round == 1) {
-        // (on a stream of its own: the first round's straggler kernel, ahead of everything on `ps`, is at work for another
-        // ~0.25 ms -- its last records come when A ends -- and this round's parked solves need not wait for it)
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->slow1_stream, overlap_accept ? ctx->ev_round : ctx->ev_acc1, 0));
-        hipLaunchKernelGGL(solve_slow_kernel, dim3(d1.slow_waves), dim3(64), coop_lds_bytes(ctx->hlens.n_terms), ctx->slow1_stream, d1);
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_slow1, ctx->slow1_stream));
-        HIP_TRY(ctx, hipStreamWaitEvent(ps, ctx->ev_slow, 0));      // the first round's stragglers (publishers' stream)
-      } else {
-        hipLaunchKernelGGL(solve_slow_kernel, dim3(d1.slow_waves), dim3(64), coop_lds_bytes(ctx->hlens.n_terms), ps, d1);      // beside the round's solves
-      }
-      HIP_TRY(ctx, hipStreamWaitEvent(ps, ctx->ev_solve, 0));
-      if (round == 1) {
-        HIP_TRY(ctx, hipStreamWaitEvent(ps, ctx->ev_acc1, 0));
-        // (the first round's queues can go back to empty for what the accept below schedules; its result pool is still read)
-        hipLaunchKernelGGL(reset_round_kernel, dim3(1), dim3(1), 0, ps, ctx->d_ctr, 0u, 1u);
-        hipLaunchKernelGGL(accept_kernel<2>, dim3(accept_blocks), dim3(256), 0, ps, da);
-        da.slow_cap = slow_cap_all;
-      } else {
-        hipLaunchKernelGGL(accept_kernel<0>, dim3(accept_blocks), dim3(256), 0, ps, da);
-      }
-      HIP_TRY(ctx, hipGetLastError());
-    }
-    da.slow_indirect = 0; da.slow_cap = slow_cap_all;
-    da.slow_live = 0;
-    if (ctx->early_resolve_pending) {
-      HIP_TRY(ctx, hipStreamWaitEvent(ps, ctx->ev_res, 0));
-      if ((rc = launch_resolve_half(ctx, ps, 2u))) return rc;
-      ctx->late_resolve_done = true;
-    }
-    tail = ps;
-    }
-  } else {
-  if ((rc = join_clear(ctx))) return rc;       // (this form's accepts are on the main stream)
-  // B: the rest of the CUs' room, once the scan's waves have left
-  da.instance = 1;
-  if (b_blocks) launch_solve_po<true>(ctx, da, ctx->stream, b_blocks);
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ch.done, 0));
-  HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->pub_done, 0));
-  if (live) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_slow, 0));
-  else launch_slow(ctx, da, ctx->stream);
-  {
-    DrawArgs d0 = da;
-    d0.emit_live = overlap ? 1 : 0;
-    d0.end_tasks = (uint32_t)ctx->num_cu * 4u;
-    if (overlap) HIP_TRY(ctx, hipEventRecord(ctx->ev_round, ctx->stream));      // everything the first accept waits for
-    hipLaunchKernelGGL(accept_kernel<0>, dim3(accept_blocks), dim3(256), 0, ctx->stream, d0);
-    HIP_TRY(ctx, hipGetLastError());
-  }
-  // The frame's resolve, first half: behind the first accept, beside the second round's solves (one block per CU, no
-  // HBM traffic to speak of) on the otherwise idle second chunk stream.  What later accepts add lands in groups of
-  // pixels whose `touched` flag is set by then: lentil_hip_redistribute resolves those once more at its end.
-  if (ctx->F.dir && ctx->F.touched && ctx->n_chunks >= 2 && !ctx->comm && !ctx->closest_deferred) {
-    hipStream_t rs = ctx->chunks[1].stream;
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_acc1, ctx->stream));
-    HIP_TRY(ctx, hipStreamWaitEvent(rs, ctx->ev_acc1, 0));
-    if ((rc = launch_resolve_half(ctx, rs, 0u))) return rc;
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_res, rs));
-    ctx->early_resolve_pending = true;
-  }
-  for (int round = 1; round < blind_rounds; ++round) {
-    da.parity = round & 1; da.round = round;
-    if (live) {
-      // the round's stragglers beside its solves: the straggler kernel on the other stream, released by the accept
-      // before it (round 1 with `overlap`: by what that accept itself waited for); this round's accept waits for both
-      const bool beside = overlap && round == 1;
-      if (beside) {
-        DrawArgs d1 = da;
-        d1.slow_after_producers = 0;
-        d1.no_reset = 1;
-        d1.producers_done = &ctx->d_ctr->accept_final[0];      // (set behind the queue's end markers)
-        d1.producers_total = 1u;
-        HIP_TRY(ctx, hipStreamWaitEvent(ch.stream, ctx->ev_round, 0));
-        launch_solve_po<true>(ctx, d1, ch.stream, (unsigned)ctx->num_cu);
-        HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipEventRecord(ch.done, ch.stream));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->pub_stream, ctx->ev_round, 0));
-        hipLaunchKernelGGL(solve_slow_kernel, dim3(d1.slow_waves), dim3(64), coop_lds_bytes(ctx->hlens.n_terms), ctx->pub_stream, d1);
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_slow, ctx->pub_stream));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ch.done, 0));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_slow, 0));
-        // (the first accept and this round's solves are done: the first round's queues can go back to empty for what
-        // the accept below schedules)
-        hipLaunchKernelGGL(reset_round_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->d_ctr, 0u, 0u);
-      } else {
-        da.producers_done = nullptr; da.producers_total = 0;
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_round, ctx->stream));
-        launch_solve_po<false>(ctx, da, ctx->stream, (unsigned)ctx->num_cu);
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->pub_stream, ctx->ev_round, 0));
-        hipLaunchKernelGGL(solve_slow_kernel, dim3(da.slow_waves), dim3(64), coop_lds_bytes(ctx->hlens.n_terms), ctx->pub_stream, da);
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_slow, ctx->pub_stream));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_slow, 0));
-      }
-    } else if (overlap && round == 1) {
-      // nothing parks in this pass: the second round's resident solves beside the first accept, released by what that
-      // accept itself waited for, fed by its tagged task slots and closed by its last block's end markers
-      DrawArgs d1 = da;
-      d1.slow_after_producers = 0;
-      d1.no_reset = 1;
-      d1.producers_done = &ctx->d_ctr->accept_final[0];      // (set behind the queue's end markers)
-      d1.producers_total = 1u;
-      HIP_TRY(ctx, hipStreamWaitEvent(ch.stream, ctx->ev_round, 0));
-      launch_solve_po<true>(ctx, d1, ch.stream, (unsigned)ctx->num_cu);
-      HIP_TRY(ctx, hipGetLastError());
-      HIP_TRY(ctx, hipEventRecord(ch.done, ch.stream));
-      HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ch.done, 0));
-      hipLaunchKernelGGL(reset_round_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->d_ctr, 0u, 0u);
-    } else {
-      launch_solve(ctx, da, ctx->stream, (unsigned)ctx->num_cu);
-    }
-    hipLaunchKernelGGL(accept_kernel<0>, dim3(accept_blocks), dim3(256), 0, ctx->stream, da);
-    HIP_TRY(ctx, hipGetLastError());
-  }
-  da.slow_live = 0;       // (rounds the host adds one by one, below, park and finish their stragglers the plain way)
-  if (ctx->early_resolve_pending) {
-    // the resolve's second half behind the last accept enqueued blind (should the host have to add rounds, or redo
-    // the draws, lentil_hip_redistribute runs it once more)
-    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_res, 0));
-    if ((rc = launch_resolve_half(ctx, ctx->stream, 2u))) return rc;
-    ctx->late_resolve_done = true;
-  }
-  }
-  const int C = ctx->n_chunks;
-  ht_mark(ctx, "all_launched");
-  ctx->clear_pending = false;       // (every stream of the pass is behind the wipe by now, and the main stream will be behind the pass)
-  StreamTail t;
-  t.tail = tail; t.pass_t0 = pass_t0; t.calibrates_now = calibrates_now; t.predicted = predicted; t.lean = lean;
-  t.live = live; t.inject = da.inject_stall != 0; t.blind_rounds = blind_rounds; t.da = da; t.slow_base = slow_base;
-  t.slow_cap_all = slow_cap_all; t.accept_blocks = accept_blocks; t.item_cap = pub.item_cap; t.task_cap = pub.task_cap;
-  t.range_cap = plan.sa.range_cap; t.pool_cap = pub.pool_cap; t.stuck_ticks = stuck_ticks;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->h_ctr_pinned, ctx->d_ctr, sizeof(DevCounters) * C, hipMemcpyDeviceToHost, tail));
-  // The asynchronous end (lentil_hip_ctx::async_end): the lean tail is the pass that expects to have nothing left to do, and the
-  // frame takes nothing but gaussian splats (closest-filtered AOVs, lentil_debug and cryptomatte have host steps behind the pass).
-  // Everything of the pass is behind `tail` by now (the lean tail's accepts wait for the scan, the publishers, the stragglers
-  // and the early resolve); the context's own stream waits for it in turn, so whatever the caller enqueues next follows the pass.
-  const bool defer = ctx->async_end && lean && !ctx->crypto && !ctx->F.zkey && !ctx->F.zkey_dbg &&
-                     !ctx->comm && !ctx->closest_deferred && !da.inject_stall && !host_trace_passes() && ctx->inflight.size() < 2;
-  if (defer) {
-    lentil_hip_ctx::Slot &sl = ctx->slots[ctx->slot];
-    HIP_TRY(ctx, hipEventRecord(sl.ev_tail, tail));
-    if (tail != ctx->stream) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, sl.ev_tail, 0));
-    t.deferred = true;
-    lentil_hip_ctx::Inflight in;
-    in.slot = ctx->slot; in.t = t; in.V = ctx->V; in.have_visits = ctx->have_visits;
-    ctx->inflight.push_back(in);
-    turn.keep();                  // (the device's turn stays this context's until the pass has been looked at)
-    ctx->last_streamed = 1;
-    ++ctx->last_blind;
-    *deferred = true;
-    *streamed = true;
-    return LENTIL_OK;
-  }
-  HIP_TRY(ctx, hipStreamSynchronize(tail));
-  ht_mark(ctx, "tail_synced");
-  if (tail != ctx->stream) {
-    // everything the pass enqueued anywhere is behind the read-back that has just arrived; what the caller enqueues on
-    // the context's stream next (resolve, downloads, the next pass) follows the main stream's own last kernel
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  ht_mark(ctx, "main_synced");
-  {
-    // (host time from the pass's first launch to its counters: an upper bound of every wait inside it)
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - pass_t0).count();
-    if (!calibrates_now && ms > ctx->longest_pass_ms && ms < 200.0) {
-      ctx->longest_pass_ms = ms; ctx->longest_pass_visits = ctx->V.n; ctx->longest_pass_sum = ctx->est_sum_total;
-    }
-  }
-  ++ctx->last_blind;
-  return streamed_finish(ctx, t, ctx->h_ctr_pinned, true, streamed);
-}
+#include "lentil_stream_pass.h"
 
 // Frame-wide visit id on the host: visit_gid (lentil_kernels.h) for the work list's order across ranks.
 static uint32_t host_visit_gid(const VisitsDev &V, uint32_t v) {
@@ -3520,7 +2433,7 @@ static int redistribute_tl_chroma(lentil_hip_ctx *ctx) {
     lentil_hip_ctx::Chunk &ch = ctx->chunks[0];
     ch.tile_begin = 0; ch.tile_end = plan.n_tiles;
     ch.v_begin = 0; ch.v_end = ctx->V.n;
-    if ((rc = launch_scan(ctx, plan, ch, ctx->d_ctr, nullptr))) return rc;
+    if ((rc = launch_scan(ctx, plan, ch, ctx->d_ctr))) return rc;
     ++ctx->last_scan_launches;
     HIP_TRY(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->scans_done, ctx->stream));
@@ -4081,7 +2994,7 @@ static int redistribute_pass(lentil_hip_ctx *ctx) {
         if (ch.v_end > ctx->V.n) ch.v_end = ctx->V.n;
       }
       if (ch.v_end > ch.v_begin) {
-        const int rc = launch_scan(ctx, plan, ch, ctx->d_ctr + ci, nullptr);
+        const int rc = launch_scan(ctx, plan, ch, ctx->d_ctr + ci);
         if (rc) return rc;
         ++ctx->last_scan_launches;
       }
@@ -4098,8 +3011,7 @@ static int redistribute_pass(lentil_hip_ctx *ctx) {
     init_draw_args(ctx, da);
     // solve/accept rounds enqueued without looking (an unused one costs ~30 us, a missing one a host round trip):
     // per chunk what it needed in the previous pass, at least 2 (3 when nothing is known); LENTIL_BLIND_ROUNDS fixes it
-    int forced_rounds = 0;
-    if (const char *e = getenv("LENTIL_BLIND_ROUNDS")) { forced_rounds = atoi(e); if (forced_rounds < 1) forced_rounds = 1; if (forced_rounds > 8) forced_rounds = 8; }
+    const int forced_rounds = forced_blind_rounds();
     const int blind_rounds = forced_rounds ? forced_rounds : 3;
     std::vector<int> rounds_of(C, blind_rounds);
     std::vector<DrawArgs> das(C, da);

@@ -1056,7 +1056,7 @@ __global__ __launch_bounds__(256) void scan_dma2_kernel(ScanArgs a) {
   extern __shared__ float4 smem[];
   // (the wave's number as a scalar: tile numbers, LDS bases and every branch on them stay in scalar registers)
   // ScanArgs::skip_blocks: the first blocks of the grid leave at once -- their CUs' registers and LDS go to a third resident
-  // solve block (lentil_hip.hip, scan_cus_pct).  They are part of the grid, not left out of it, so that whichever of the two
+  // solve block (lentil_scan.h, scan_grid: scan_cus_pct).  They are part of the grid, not left out of it, so that whichever of the two
   // kernels the dispatcher places first, every block that does scan finds a CU with room: a CU holds either this kernel's
   // block and two solve blocks or three solve blocks, and the blocks that leave free exactly the CUs the others need.
   if (blockIdx.x < a.skip_blocks) { scan_block_done(a); return; }
@@ -4850,7 +4850,7 @@ __global__ __launch_bounds__(256) void resolve_kernel(FrameDev F, float *resolve
 // adding draws (see lentil_hip_redistribute): just the 64-pixel groups a later round's draw was splatted into (flag 2;
 // the headline frame's first round touches about half of the groups, its second a few hundred).  A wave looks at 64 groups'
 // flags with one load and walks the set bits.  (min_flag 1: every group that received a draw -- the pass whose whole-frame
-// resolve ran behind the scan, before any accept, see redistribute_streamed.)
+// resolve ran behind the scan, before any accept, see make_stream_form in lentil_stream_pass.h.)
 // (Round 6: within a flagged group only the pixels a draw reached are written again -- resolve_touched_group.)
 // One flagged 64-pixel group of a frame whose untouched state is resolved already (the whole-frame resolve ran earlier in the
 // pass, from the pixels' own sums alone or with an earlier round's draws): the group's 64 per-pixel flags are read (one coalesced

@@ -59,7 +59,7 @@ def vid(M, tile, group, lane):
 
 
 def blocks_of(n_tiles, num_cu):
-    """scan_dma2_kernel's grid for a launch over n_tiles tiles (launch_scan, csrc/lentil_hip.hip)"""
+    """scan_dma2_kernel's grid for a launch over n_tiles tiles (scan_grid, csrc/lentil_scan.h)"""
     return max(1, min((n_tiles + 15) // 16, num_cu))
 
 

@@ -1,7 +1,7 @@
 """The shapes the scan kernels are tested at (tests/test_scan_shape_cases.py: the table against the oracle, no GPU;
 tests/test_gpu_scan_shapes.py: the kernels against the oracle).  A plain module: no fixtures, fixed seeds, nothing random.
 
-A pass starts in one of seven scan kernels (include/lentil_hip.h, LENTIL_SCAN_*; plan_scan in csrc/lentil_hip.hip).  Which
+A pass starts in one of seven scan kernels (include/lentil_hip.h, LENTIL_SCAN_*; plan_scan in csrc/lentil_scan.h).  Which
 one follows from the stream's shape, and each case below names the kernel its shape selects -- `expect` -- and, for the
 uniform streams, the pixels per tile or group -- `ppt` (lentil_hip_debug_last_scan reports both).  Where the figures come from
 (LDS sizes as plan_scan computes them, wave queues of 4608 B included; a context streams by default, so the two resident solve

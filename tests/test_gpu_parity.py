@@ -1043,6 +1043,33 @@ def test_blind_passes_and_fallback(orc, monkeypatch, stream):
         ctx.close()
 
 
+def test_streamed_pass_that_parks_nothing(orc, monkeypatch):
+    """The streamed pass of frames with many draws, at the small frame of test_blind_passes_and_fallback: no straggler queue
+    (LENTIL_SLOW_BELOW=0: no draw sum is below it, DrawArgs::slow stays null), so the pass has its second solve launch behind
+    the scan, its accepts on the main stream, and the second round's resident solves beside the first accept.  The first pass
+    of a context is chunked; the second and third stream, fit, and give what the oracle gives."""
+    W, H, M = 96, 64, 9
+    p, model, table, keep = common.po_setup(W, H, samples_override=48)
+    light, keep_l = common.make_stream(p, W, H, M, f_hi=0.002)      # the column arrays must outlive the passes
+    ref = common.run_oracle(orc, p, table, light)
+    monkeypatch.setenv("LENTIL_CHUNKS", "3")
+    monkeypatch.setenv("LENTIL_STREAM", "1")
+    monkeypatch.setenv("LENTIL_SLOW_BELOW", "0")
+    ctx = capi.Context(0)
+    try:
+        for streamed in (0, 1, 1):
+            c = gpu_run(ctx, p, table, light)
+            rc = ref.counters()
+            assert (c.redistributed_visits, c.attempted_draws, c.accepted_draws) == (
+                rc.redistributed_visits, rc.attempted_draws, rc.accepted_draws)
+            assert c.streamed == streamed
+            assert c.fallback_chunks == 0
+            check_logs(ctx, ref)
+            check_frame(ctx, ref)
+    finally:
+        ctx.close()
+
+
 @pytest.mark.parametrize("size", ["small", "large"])
 def test_streamed_pass_that_stalls_after_its_first_accept_is_run_again(orc, monkeypatch, size):
     """A streamed pass whose resident waves give up waiting (kStuckTicks) AFTER the first accept has added draws to the frame
