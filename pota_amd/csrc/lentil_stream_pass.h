@@ -409,7 +409,24 @@ static StreamForm make_stream_form(lentil_hip_ctx *ctx, const DrawArgs &seed, co
   // 60 steps each, gpurun_out/r06s05.  Config 4 parks dry waves' lanes only and keeps one.)
   const int slow_per_cu = ctx->slow_waves_per_cu;
   const uint32_t slow_default = (f.nch == 1 && ctx->V.n_extra == 0 && !f.dry_only) ? 4u : 1u;
-  f.slow_waves_all = (uint32_t)ctx->num_cu * (slow_per_cu >= 1 && slow_per_cu <= 4 ? (uint32_t)slow_per_cu : slow_default);
+  uint32_t slow_cu = slow_per_cu >= 1 && slow_per_cu <= 4 ? (uint32_t)slow_per_cu : slow_default;
+  const size_t solve_lds = solve_block_lds(ctx);
+  if (f.live) {
+    // ... and no more per CU than leave room for what they wait for.  A live queue's waves spin on end markers that a resident
+    // solve wave writes -- a round later, a solve wave fed by an accept's blocks --, and those kernels are launched beside the
+    // straggler kernel, not ahead of it: whichever the dispatcher places first keeps its LDS.  A straggler wave's block is
+    // 9-21 KB with the shipped tables and 41 KB with a table of kMaxTerms terms (coop_lds_bytes).  Of the four asked for per CU
+    // three of those fit a CU's 160 KB, and with three resident no CU had the 52 KB of an interpreter's solve block left: no
+    // task was ever taken, no end marker written, every straggler wave waited out its 250 ms, and every streamed pass of such
+    // a table was redone (tests/lens_tables.py, "full").  So: as many as leave a CU one solve block and one accept block
+    // -- then not every CU can be full of them.  Four, as ever, with every shipped table on either solve kernel (the
+    // largest, petzval_58mm's 707 terms under the interpreter: 4 x 20.0 + 52.5 + 21 = 153.4 KB; two at kMaxTerms).
+    // (A queue that is not live has no wave that waits: its kernel runs behind the solves and is left as it was.)
+    constexpr size_t kAcceptBlockLds = 21u * 1024u;       // accept_kernel's block: 20.7 KB (tools/kernel_resources.py)
+    const size_t wave_lds = coop_lds_bytes(ctx->hlens.n_terms) + sizeof(CoopShared) + 512u;
+    while (slow_cu > 1u && !fits_cu_beside_solves((size_t)slow_cu * wave_lds + kAcceptBlockLds, 1u, solve_lds, 0u)) --slow_cu;
+  }
+  f.slow_waves_all = (uint32_t)ctx->num_cu * slow_cu;
   // A: as many resident solve blocks per CU as leave a scan block its LDS.  (Round 6: the table interpreter's blocks hold 52 KB each --
   // two of them and an 80 KB scan_dma_kernel block do not fit a CU's 160 KB, and where the dispatcher placed the solve blocks
   // first no scan block ever found room: the resident waves waited for a scan that could not start until a publisher gave up,
@@ -417,7 +434,6 @@ static StreamForm make_stream_form(lentil_hip_ctx *ctx, const DrawArgs &seed, co
   // its second pass with lentil_hip_set_lens_mode(ctx, 1) --, found when the library began to count its stalls.  plan_scan only
   // budgeted for scan_dma2_kernel.)
   unsigned a_per_cu = (unsigned)ctx->stream_blocks;
-  const size_t solve_lds = solve_block_lds(ctx);
   while (a_per_cu > 1u && !fits_cu_beside_solves(plan.lds, a_per_cu, solve_lds, 512u)) --a_per_cu;
   f.a_blocks = (unsigned)ctx->num_cu * a_per_cu;
   // CUs the scan leaves alone (scan_cus_pct) have registers for one more resident solve block
