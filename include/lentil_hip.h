@@ -813,7 +813,8 @@ int lentil_hip_trace_points_path(lentil_hip_ctx *ctx, int *path);
  * and the shutter.  A visit's source pixel and inverse density are derived as the pass derives them: from pixel_x0 / pixel_y0 /
  * pixel_row_stride / pixels_per_row and params.inverse_sample_density for a uniform stream, from the pixel and inv_density
  * columns for a ragged one.  Neither needs a frame, touches an accumulator, a cryptomatte table, the counter block
- * (lentil_hip_get_counters) or the xor128 state, or consults an occlusion probe.  Both observe the context (a pass in flight is
+ * (lentil_hip_get_counters) or the xor128 state; plan_visits consults no occlusion probe, list_draws only with
+ * LENTIL_DRAWS_PROBED (below).  Both observe the context (a pass in flight is
  * finished first) and take no part in the streamed passes' turns.  Visits are numbered as in the bound stream; a range is
  * [first_visit, first_visit + n_visits), and must lie inside the stream and below 2^32.
  *
@@ -852,6 +853,32 @@ int lentil_hip_trace_points_path(lentil_hip_ctx *ctx, int *path);
  *   LENTIL_ERR_UNSUPPORTED, with a message: polynomial optics with abb_chromatic != 0 (three traces per attempt under another
  *   counting rule), the thin lens with abb_chromatic > 0 (the channels follow the pass's xor128 order; trace_points does not
  *   offer it either).
+ *   flags LENTIL_DRAWS_PROBED: the list under the context's occlusion probe (lentil_hip_set_occlusion_probe or
+ *   lentil_hip_set_occlusion_probe_device, with its camera_to_world or the fp64 inverse, motion keys included) -- the draw
+ *   list of the reference's pass under that probe.  Without the flag a probe is ignored: the unprobed list, bit for bit.
+ *   With the flag and no probe the call fails with LENTIL_ERR_INVALID.
+ *     Polynomial optics: seed m = attempt + try of a visit is occluded or it is not, whichever attempt looks at it.  An
+ *     attempt's outcome is the first seed in attempt ... attempt + vignetting_retries that is neither vignetted nor
+ *     occluded; `tries` counts the failed tries before it, vignetted or occluded; xy and pixel are that try's.
+ *     Thin lens: an occluded attempt is lost, `tries` stays 0.  Samples the skydome supplied are exempt and never asked about.
+ *     The selection is the same: the first `samples` attempts below 5 * samples that land in the frame.  *attempts is the
+ *     reference's attempted_draws under the probe.  plan_visits' totals[2] still bounds the list.
+ *     What the callback is asked: one segment per (visit, seed) that the reference's walk reaches and that got through the
+ *     lens (a vignetted try is never asked about: its answer cannot matter), each at most once per call, each bit-identical
+ *     to the segment a pass lists for that try.  (With enable_dof == 0 every seed of a visit has the same aperture point, so
+ *     a visit's segments coincide; they are still one per seed.)
+ *     Which seeds a visit reaches depends on the answers, so the list is made in turns: the callback may be called several
+ *     times per list_draws call, always on the calling thread, with the segments no earlier turn asked about.  It must not
+ *     call into the context.  Answers are not kept between calls: a counting call (capacity == 0) followed by the real one
+ *     asks twice.  Host callback: segments and answers travel as in a pass.  Device callback: segments and answers stay on
+ *     the device, the host reads back each turn's list length (and waits for it); every list is made into buffers that hold
+ *     it, so `capacity` as handed to the callback is at least *d_n.  A device callback that returns non-zero fails the call
+ *     with LENTIL_ERR_INVALID and the code in the message, as it fails a pass; the context stays usable.
+ *     lentil_hip_probe_stats counts these segments, occluded answers and calls too, lentil_hip_probe_device_stats the lists
+ *     (and one wait per turn).  The list as a set, and the set of segments asked per visit, do not depend on the grid, on
+ *     the capacity or on how the stream is split into ranges.  The call keeps two bits per seed 0 ... 5 * samples +
+ *     vignetting_retries of every redistributed visit of the range; LENTIL_ERR_NOMEM, with a message, where that store
+ *     does not fit: split the range.  LENTIL_DRAWS_DEVICE_POINTERS combines freely with the flag.
  * LENTIL_ERR_INVALID (both calls): no parameters or no visits, polynomial optics without a lens, bokeh_enable_image without
  * tables (list_draws), a range outside the stream or beyond 2^32, out NULL with n_visits > 0 (plan) or capacity > 0 (list),
  * n_draws NULL.  n_visits == 0 launches nothing (zero totals, zero n_draws).
@@ -872,11 +899,12 @@ int lentil_hip_plan_visits(lentil_hip_ctx *ctx, uint64_t first_visit, uint64_t n
                            uint32_t flags, uint64_t totals[3] /* optional: visits, redistributed, sum of their samples */);
 
 #define LENTIL_DRAWS_DEVICE_POINTERS 1u
+#define LENTIL_DRAWS_PROBED 2u              /* the list under the context's occlusion probe (see above) */
 typedef struct lentil_draw {                /* 32 bytes */
   uint32_t visit;     /* index into the bound stream */
   uint32_t attempt;   /* the reference's total_samples_taken of the draw */
   uint32_t pixel;     /* linear pixel ix + iy * xres */
-  int32_t  tries;     /* vignetted tries before the one that got through (thin lens: 0) */
+  int32_t  tries;     /* vignetted (LENTIL_DRAWS_PROBED: or occluded) tries before the one that got through (thin lens: 0) */
   double   xy[2];     /* continuous pixel coordinates before floor (trace_points' out_xy) */
 } lentil_draw;
 typedef struct lentil_draw_list {

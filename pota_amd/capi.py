@@ -603,13 +603,14 @@ class Context:
         self._chk(self.lib.lentil_hip_plan_visits(self.h, first, n, ptr, flags, tot))
         return out, (tuple(int(t) for t in tot) if totals else None)
 
-    def list_draws(self, first=0, n=None, capacity=None, lam=0.0, device=False):
+    def list_draws(self, first=0, n=None, capacity=None, lam=0.0, device=False, probed=False):
         """The accepted draws of the bound visits first ... first + n - 1 (lentil_hip_list_draws) -> (records, n_draws,
         attempts): records a numpy array of _abi.Draw (visit, attempt, pixel, tries, xy), in no particular order, the first
         min(n_draws, capacity) of it filled and returned; n_draws the accepted draws found (above capacity: ask again with more
         room); attempts the attempts made.  capacity None: sized from plan_visits' totals[2], which always suffices.
         lam: micrometres, 0 = params.lambda_bw.  device=True: the records stay on the GPU, a uint8 [capacity, 32] torch tensor,
-        whole (the call returns when it is filled)."""
+        whole (the call returns when it is filled).  probed=True (_abi.DRAWS_PROBED): the list under the context's occlusion
+        probe -- tries then counts occluded tries too, and the probe's callback is called once per turn, on this thread."""
         first, n = self._visit_range(first, n)
         if capacity is None:
             capacity = self.plan_visits(first, n)[1][2] if n else 0
@@ -624,6 +625,8 @@ class Context:
         else:
             out = np.empty(capacity, _abi.Draw)
             b.out, b.flags = (out.ctypes.data if capacity else None), 0
+        if probed:
+            b.flags |= _abi.DRAWS_PROBED
         self._chk(self.lib.lentil_hip_list_draws(self.h, C.byref(b)))
         if not device:
             out = out[:min(nd.value, capacity)]

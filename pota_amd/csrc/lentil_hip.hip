@@ -112,7 +112,8 @@ struct lentil_hip_ctx {
   int rays_path = 0;                  // what the last lentil_hip_camera_rays call ran (lentil_hip_camera_rays_path)
   int points_path = 0;                // ... the last lentil_hip_trace_points call (lentil_hip_trace_points_path)
   int draws_path = 0;                 // ... the last lentil_hip_list_draws call (lentil_hip_list_draws_path)
-  // lentil_hip_plan_visits / lentil_hip_list_draws: [0..2] the plan's totals, [4] the list's ticket, [5] its draws, [6] its attempts
+  // lentil_hip_plan_visits / lentil_hip_list_draws: [0..2] the plan's totals, [4] the list's ticket, [5] its draws, [6] its attempts,
+  // [7] the visits a probed list's turn left unsettled, [8..11] ListProbeArgs::x
   unsigned long long *d_list_ctr = nullptr;
 
   DevBokeh bokeh{};
@@ -373,6 +374,7 @@ struct lentil_hip_ctx {
   float *d_c2w_keys = nullptr;
   bool c2w_keys_valid = false;                // d_c2w_keys holds the inverses of the keys as they stand
   ProbeBuf tlc_pb;                            // the lists of a thin-lens abb_chromatic > 0 pass (tl_chroma_probe; the chunks have their own)
+  ProbeBuf ld_pb;                             // the lists of a probed lentil_hip_list_draws call's turns
   uint64_t n_probes = 0, n_probes_occluded = 0, n_probe_calls = 0;     // since the context was created (lentil_hip_probe_stats)
   // ... answered on the device (lentil_hip_set_occlusion_probe_device): the renderer's callback; lists handed to it, host waits made
   // for such lists, lists that did not fit, the longest list (lentil_hip_probe_device_stats)
@@ -826,6 +828,7 @@ LENTIL_API int lentil_hip_destroy(lentil_hip_ctx *ctx) {
   (void)hipFree(ctx->d_ranges);
   (void)hipFree(ctx->d_c2w_keys);
   probe_buf_free(ctx->tlc_pb);
+  probe_buf_free(ctx->ld_pb);
   for (auto &ch : ctx->chunks) probe_buf_free(ch.pb);
   if (ctx->jit_module) (void)hipModuleUnload(ctx->jit_module);
   (void)hipFree(ctx->d_bm_land); (void)hipFree(ctx->d_bm_box); (void)hipFree(ctx->d_bm_npass);
@@ -4183,7 +4186,7 @@ static int list_range_check(lentil_hip_ctx *ctx, uint64_t first, uint64_t n) {
   if (first > ctx->V.n || n > ctx->V.n - first)
     return fail(ctx, LENTIL_ERR_INVALID, "visits " + std::to_string(first) + " + " + std::to_string(n) + " lie outside the stream of " + std::to_string(ctx->V.n));
   if (first + n > (1ull << 32)) return fail(ctx, LENTIL_ERR_INVALID, "the visit range must lie below 2^32");
-  if (!ctx->d_list_ctr) HIP_TRY(ctx, hipMalloc(&ctx->d_list_ctr, 8 * sizeof(unsigned long long)));
+  if (!ctx->d_list_ctr) HIP_TRY(ctx, hipMalloc(&ctx->d_list_ctr, 16 * sizeof(unsigned long long)));
   return LENTIL_OK;
 }
 
@@ -4219,6 +4222,139 @@ LENTIL_API int lentil_hip_plan_visits(lentil_hip_ctx *ctx, uint64_t first_visit,
   return LENTIL_OK;
 }
 
+// One turn's walk of a probed list, on the lens path the unprobed list takes.
+static int list_probed_launch(lentil_hip_ctx *ctx, dim3 grid, bool po, const ListDrawArgs &a, const ProbeArgs &pr, const ListProbeArgs &b) {
+  int path = 0;
+  if (po) {
+#define LENTIL_LAUNCH_GEN(NAME)                                                                              \
+    if (!path && ctx->use_generated && ctx->lens_hash == gen::Lens_##NAME::kTableHash) {                      \
+      hipLaunchKernelGGL((list_draws_probed_kernel<GenLens<gen::Lens_##NAME>, false, true>), grid, dim3(kLdBlock), 0, ctx->stream, a, pr, b); \
+      path = 2;                                                                                              \
+    }
+    LENTIL_GENERATED_LENSES(LENTIL_LAUNCH_GEN)
+#undef LENTIL_LAUNCH_GEN
+    if (!path) {
+      hipLaunchKernelGGL((list_draws_probed_kernel<LdsLens, true, true>), grid, dim3(kLdBlock), 0, ctx->stream, a, pr, b);
+      path = 1;
+    }
+  } else {
+    hipLaunchKernelGGL((list_draws_probed_kernel<LdsLens, false, false>), grid, dim3(kLdBlock), 0, ctx->stream, a, pr, b);
+  }
+  ctx->draws_path = path;
+  HIP_TRY(ctx, hipGetLastError());
+  return LENTIL_OK;
+}
+
+// LENTIL_DRAWS_PROBED (lentil_list_draws.h): the answer store is sized and allocated, then the turns -- counter reset, the
+// walk, the clamp, the turn's length and the unsettled visits read back (64 bytes, one wait), the callback on this thread
+// (host: segments out, answers in, as probe_ask moves them; device: probe_call_device, nothing else crosses), the apply kernel
+// -- until a turn leaves no visit unsettled.  The turn's buffers are the context's (ld_pb), kept between calls; a turn that
+// wanted more than they hold asks the rest in a later turn, into larger ones.  h: ListDrawArgs::ctr [0..2] at the end.
+static int list_draws_probed(lentil_hip_ctx *ctx, ListDrawArgs &a, dim3 grid, bool po, TmpFree &tf, unsigned long long h[3]) {
+  hipStream_t st = ctx->stream;
+  const uint64_t n_visits = a.v_end - a.v_begin;
+  int rc;
+  ProbeArgs pr{};
+  if ((rc = probe_prepare(ctx, pr, st))) return rc;
+  ListProbeArgs b{};
+  b.x = ctx->d_list_ctr + 8;
+  if ((rc = dev_alloc(ctx, (size_t)n_visits, &b.st, tf.v))) return rc;
+  HIP_TRY(ctx, hipMemsetAsync(a.ctr, 0, 8 * sizeof(unsigned long long), st));       // (ListDrawArgs::ctr [0..3] and ListProbeArgs::x)
+  {
+    PlanArgs pa{};
+    pa.P = a.P; pa.V = a.V; pa.lens_length = a.lens_length; pa.v_begin = a.v_begin; pa.v_end = a.v_end;
+    const uint64_t want = (n_visits + kLdBlock - 1) / kLdBlock, most = (uint64_t)ctx->num_cu * 8u;
+    hipLaunchKernelGGL(ld_probe_alloc_kernel, dim3((unsigned)(want < most ? want : most)), dim3(kLdBlock), 0, st, pa, b);
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  unsigned long long sized[2] = {0, 0};
+  HIP_TRY(ctx, hipMemcpyAsync(sized, b.x, sizeof sized, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  const uint64_t words = sized[0], most_seeds = sized[1];
+  h[0] = h[1] = h[2] = 0;
+  if (!words) {       // no visit of the range is redistributed: nothing is drawn, nobody is asked
+    ctx->draws_path = !po ? 0 : 1;
+    if (po && ctx->use_generated) {
+#define LENTIL_PATH_GEN(NAME) if (ctx->lens_hash == gen::Lens_##NAME::kTableHash) ctx->draws_path = 2;
+      LENTIL_GENERATED_LENSES(LENTIL_PATH_GEN)
+#undef LENTIL_PATH_GEN
+    }
+    return LENTIL_OK;
+  }
+  // the store: two arrays of `words` 32-bit words; a seed's place in it is a 32-bit bit index
+  const std::string split = "list_draws: the answer store of a probed list over these visits (" + std::to_string(words * 8u) +
+                            " bytes) does not fit; split the visit range";
+  if (words > (1ull << 27)) return fail(ctx, LENTIL_ERR_NOMEM, split);
+  {
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
+    if (words * 8u > free_b / 2u) return fail(ctx, LENTIL_ERR_NOMEM, split);
+    uint32_t *store = nullptr;
+    if (hipMalloc((void **)&store, (size_t)words * 8u) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, LENTIL_ERR_NOMEM, split); }
+    tf.v.push_back(store);
+    b.A = store; b.B = store + words;
+    HIP_TRY(ctx, hipMemsetAsync(store, 0, (size_t)words * 8u, st));
+  }
+  ProbeBuf &pb = ctx->ld_pb;
+  const bool host = ctx->probe_fn != nullptr;
+  constexpr uint64_t kFirstMost = 1ull << 22, kMost = 1ull << 24;
+  uint64_t want_cap = words * 7u < 4096u ? 4096u : (words * 7u > kFirstMost ? kFirstMost : words * 7u);      // about the sum of the samples
+  if (want_cap < pb.cap) want_cap = pb.cap;
+  // every walk of an unsettled visit asks about a new seed of it; a turn that did not fit retires a buffer's worth of the store's seeds
+  const uint64_t max_turns = most_seeds + 64u + words * 32u / 4096u;
+  const dim3 pgrid((unsigned)ctx->num_cu * 4u), pblock(256);
+  unsigned long long t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (uint64_t turn = 0;; ++turn) {
+    if (turn >= max_turns) return fail(ctx, LENTIL_ERR_INVALID, "list_draws: the probed list's turns did not end (internal)");
+    if (pb.cap < want_cap || (host && pb.h_cap < want_cap) || !pb.count) {
+      HIP_TRY(ctx, hipStreamSynchronize(st));       // (the last turn's apply kernel reads the buffers that go)
+      if ((rc = probe_buf_reserve(ctx, pb, want_cap, host))) return rc;
+    }
+    if (pb.occ_dirty) { HIP_TRY(ctx, hipMemsetAsync(pb.occ, 0, pb.cap, st)); pb.occ_dirty = false; }
+    probe_bind(pb, pb.cap, pr);
+    HIP_TRY(ctx, hipMemsetAsync(pb.count, 0, sizeof(unsigned int), st));
+    HIP_TRY(ctx, hipMemsetAsync(a.ctr + 0, 0, sizeof(unsigned long long), st));
+    HIP_TRY(ctx, hipMemsetAsync(a.ctr + 3, 0, sizeof(unsigned long long), st));
+    if ((rc = list_probed_launch(ctx, grid, po, a, pr, b))) return rc;
+    hipLaunchKernelGGL(ld_probe_clamp_kernel, dim3(1), dim3(64), 0, st, pb.count, pr.cap, b.x);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(t, a.ctr, sizeof t, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (!host) ++ctx->n_dev_waits;
+    const uint64_t raw = t[7], unsettled = t[3];
+    const uint64_t n = raw < pb.cap ? raw : pb.cap;
+    if (n) {
+      if (host) {
+        HIP_TRY(ctx, hipMemcpyAsync(pb.h_seg, pb.seg, (size_t)n * sizeof(lentil_probe_segment), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        memset(pb.h_occ, 0, (size_t)n);
+        ctx->probe_fn(ctx->probe_user, n, pb.h_seg, pb.h_occ);
+        uint64_t occ = 0;
+        for (uint64_t i = 0; i < n; ++i) occ += pb.h_occ[i] ? 1u : 0u;
+        ctx->n_probes += n; ctx->n_probes_occluded += occ; ++ctx->n_probe_calls;
+        if (occ) HIP_TRY(ctx, hipMemcpyAsync(pb.occ, pb.h_occ, (size_t)n, hipMemcpyHostToDevice, st));
+      } else {
+        if ((rc = probe_call_device(ctx, pb, pb.cap, st))) { pb.occ_dirty = true; return rc; }
+        ctx->n_probes += n;
+        if (n > ctx->dev_longest) ctx->dev_longest = n;
+      }
+      hipLaunchKernelGGL(ld_probe_apply_kernel, pgrid, pblock, 0, st, b, (const uint32_t *)pb.idx, pb.occ, (const unsigned int *)pb.count, pr.cap);
+      HIP_TRY(ctx, hipGetLastError());
+    }
+    if (!unsettled) break;
+    if (!n) return fail(ctx, LENTIL_ERR_INVALID, "list_draws: a probed list's turn left visits unsettled and asked nothing (internal)");
+    if (raw > pb.cap) want_cap = raw * 2u > kMost ? (pb.cap > kMost ? pb.cap : kMost) : raw * 2u;
+  }
+  HIP_TRY(ctx, hipStreamSynchronize(st));       // (the last apply, and the host form's upload from the pinned answers)
+  if (!host) {
+    unsigned long long occ = 0;
+    HIP_TRY(ctx, hipMemcpy(&occ, b.x + 2, sizeof occ, hipMemcpyDeviceToHost));
+    ctx->n_probes_occluded += occ;
+  }
+  h[0] = t[0]; h[1] = t[1]; h[2] = t[2];
+  return LENTIL_OK;
+}
+
 LENTIL_API int lentil_hip_list_draws(lentil_hip_ctx *ctx, const lentil_draw_list *list) {
   CHECK_CTX(ctx);
   if (!list) return fail(ctx, LENTIL_ERR_INVALID, "list is null");
@@ -4233,6 +4369,9 @@ LENTIL_API int lentil_hip_list_draws(lentil_hip_ctx *ctx, const lentil_draw_list
   if (!po && ctx->P.abb_chromatic > 0.0f)
     return fail(ctx, LENTIL_ERR_UNSUPPORTED, "list_draws: the thin lens with abb_chromatic > 0 draws its channels in the pass's xor128 order");
   if (list->capacity && !list->out) return fail(ctx, LENTIL_ERR_INVALID, "out is null with capacity > 0");
+  const bool probed = (list->flags & LENTIL_DRAWS_PROBED) != 0u;
+  if (probed && !probing(ctx))
+    return fail(ctx, LENTIL_ERR_INVALID, "list_draws: LENTIL_DRAWS_PROBED needs an occlusion probe (set_occlusion_probe or set_occlusion_probe_device)");
   *list->n_draws = 0;
   if (list->attempts) *list->attempts = 0;
   if (!list->n_visits) return LENTIL_OK;
@@ -4254,6 +4393,15 @@ LENTIL_API int lentil_hip_list_draws(lentil_hip_ctx *ctx, const lentil_draw_list
   const uint64_t want = (tickets + kLdBlock / 64 - 1) / (kLdBlock / 64), cap = (uint64_t)ctx->num_cu * 8u;
   const dim3 grid((unsigned)(want < cap ? want : cap));
   int path = 0;
+  if (probed) {
+    unsigned long long h[3] = {0, 0, 0};
+    if ((rc = list_draws_probed(ctx, a, grid, po, tf, h))) return rc;
+    *list->n_draws = h[1];
+    if (list->attempts) *list->attempts = h[2];
+    const uint64_t written = h[1] < list->capacity ? h[1] : list->capacity;
+    if (!device && written) HIP_TRY(ctx, hipMemcpy(list->out, d_out, (size_t)written * sizeof(lentil_draw), hipMemcpyDeviceToHost));
+    return LENTIL_OK;
+  }
   if (po) {
 #define LENTIL_LAUNCH_GEN(NAME)                                                                              \
     if (!path && ctx->use_generated && ctx->lens_hash == gen::Lens_##NAME::kTableHash) {                      \

@@ -2,7 +2,7 @@
 // (lentil_hip_plan_visits, lentil_hip_list_draws): what the visit prologue decides per visit (src/lentil_filter.cpp:105-240),
 // and the accepted draws of a visit range -- the first `samples` attempts among 0 ... 5 * samples - 1 that get through the lens
 // and land in the frame (the loops of src/lentil_filter.cpp:249-300 and :311-447) -- with their continuous pixel coordinates.
-// No frame, no accumulators, no counter block, no xor128 state, no probes; no existing kernel changes.
+// No frame, no accumulators, no counter block, no xor128 state; occlusion probes only in the probed list at the end of this file.
 //
 // plan_visits_kernel.  One lane per visit, 64 consecutive visits per wave and step (the five 16-byte columns are read
 // coalesced), grid-stride over such groups; visit_prologue and visit_pixel are the pass's own (load_work_visit), the weight
@@ -245,5 +245,348 @@ __global__ __launch_bounds__(kLdBlock) void list_draws_kernel(ListDrawArgs a) {
       wave_attempts += made;
     }
     if (lane == 0u && wave_attempts) atomicAdd(&a.ctr[2], wave_attempts);
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// LENTIL_DRAWS_PROBED: the list under the context's occlusion probe.  Seed m = attempt + try of a visit is occluded or it is
+// not, whichever attempt looks at it; which seeds a visit reaches depends on the answers, so the list is made in turns.
+//
+// The answer store.  Two bits per seed 0 ... 5 * samples + max(vignetting_retries, 0) of every redistributed visit, in two
+// word arrays A and B: (A, B) = (0, 0) never asked about, (1, 0) asked in this turn, (1, 1) clear, (0, 1) occluded.
+// ld_probe_alloc_kernel hands every visit of the range its word offset (a wave scan and one atomic per 64 visits) and its
+// LdVisitState; ld_probe_apply_kernel, behind the callback, turns every listed seed's (1, 0) into clear or occluded.
+//
+// list_draws_probed_kernel, one per turn: list_draws_kernel's ticket / readlane / slab structure over the visits that are not
+// settled.  A try at a seed known to be occluded fails without a solve.  A try that gets through the lens at a seed whose
+// answer is not known leaves its lane `dirty`: what the attempt comes to is open.  The reference reaches attempt n only
+// while fewer than `samples` lower attempts were accepted, and an open attempt may yet be accepted (its seed clear) or not --
+// even one whose optimistic trace lands outside the frame, since an occluded seed hands the attempt to the next try, which may
+// land inside.  So a dirty lane asks only where accepted + (the successes and the dirty lanes below it) < samples: then the
+// reference reaches it whatever the open answers are, and no seed is asked about that the final walk does not reach.  The
+// lowest dirty lane of a walk always qualifies (below it everything is known), so every walk of an unsettled visit asks
+// about a new seed: at most 5 * samples + vignetting_retries + 1 turns.  Neighbouring attempts share seeds; an atomicOr on the
+// A bit elects the lister, the elected lanes take slots by probe_wave_slot, and one whose slot lies beyond the turn's
+// buffers takes its A bit back (the seed is asked about in a later turn; the host grows the buffers from the count).
+// A slab in which no lane asks is final -- its every consulted seed has its answer -- as long as every slab before it was:
+// its records are written as list_draws_kernel writes them and the visit's LdVisitState moves behind it, so a later turn
+// resumes there and no record is written twice.  Behind a slab that asked, the walk goes on optimistically with the upper
+// bound of the accepted count, only to ask.  A visit whose walk reaches its end with every slab final is settled.
+// Every loop is bounded as in list_draws_kernel; the turns are the host's (lentil_hip.hip: list_draws_probed).
+// ---------------------------------------------------------------------------------------
+constexpr uint32_t kLdSettled = 0xFFFFFFFFu;
+
+struct LdVisitState {               // 16 bytes per visit of the range
+  uint32_t off;                     // the visit's first word in A and in B
+  uint32_t k0;                      // the first attempt of the first slab that is not final; kLdSettled: nothing left to do
+  uint32_t accepted;                // accepted draws below k0
+  uint32_t pad;
+};
+
+struct ListProbeArgs {
+  LdVisitState *st;                 // [v_end - v_begin]
+  uint32_t *A, *B;                  // the answer store
+  unsigned long long *x;            // [0] words handed out, [1] the most seeds of a visit, [2] occluded answers, [3] a turn's count before the clamp
+};
+
+LD_DEV uint32_t ld_seed_count(const lentil_params &P, uint32_t samples) {
+  const uint32_t r = P.cameraType == LENTIL_POLYNOMIAL_OPTICS && P.vignetting_retries > 0 ? (uint32_t)P.vignetting_retries : 0u;
+  const unsigned long long n = (unsigned long long)(samples * 5u) + r + 1ull;      // (samples * 5u wraps as max_total does)
+  return n > 0xFFFFFFE0ull ? 0xFFFFFFE0u : (uint32_t)n;
+}
+
+__global__ __launch_bounds__(kLdBlock) void ld_probe_alloc_kernel(PlanArgs a, ListProbeArgs b) {
+  const VisitsDev &V = a.V;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t wave = (uint64_t)blockIdx.x * (kLdBlock / 64) + (threadIdx.x >> 6);
+  const uint64_t waves = (uint64_t)gridDim.x * (kLdBlock / 64);
+  const uint64_t n_groups = (a.v_end - a.v_begin + 63u) / 64u;
+  unsigned long long most = 0;
+  for (uint64_t g = wave; g < n_groups; g += waves) {
+    const uint64_t v = a.v_begin + g * 64u + lane;
+    const bool valid = v < a.v_end;
+    unsigned long long words = 0;
+    if (valid) {
+      const float invd = V.inv_density ? V.inv_density[v] : a.P.inverse_sample_density;
+      const VisitInfo I = visit_prologue(a.P, a.lens_length, V.rgba[v], V.pos_z[v], V.raydir_time[v], V.volume_ignore[v],
+                                         V.transmission[v], invd, V.cam);
+      if (I.redistribute) {
+        const uint32_t seeds = ld_seed_count(a.P, (uint32_t)I.samples);
+        words = ((unsigned long long)seeds + 31ull) / 32ull;
+        if (seeds > most) most = seeds;
+      }
+    }
+    unsigned long long incl = words;
+    for (int off = 1; off < 64; off <<= 1) {
+      const unsigned long long t = __shfl_up(incl, off);
+      if ((int)lane >= off) incl += t;
+    }
+    const unsigned long long total = ld_readlane(incl, 63);
+    unsigned long long base = 0;
+    if (lane == 0u && total) base = atomicAdd(&b.x[0], total);
+    base = ld_readlane(base, 0);
+    if (valid) {
+      LdVisitState s;
+      s.off = (uint32_t)(base + incl - words);       // (the host refuses a store of 2^27 words or more per array)
+      s.k0 = words ? 0u : kLdSettled;
+      s.accepted = 0u; s.pad = 0u;
+      b.st[v - a.v_begin] = s;
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) { const unsigned long long t = __shfl_down(most, off); most = t > most ? t : most; }
+  if (lane == 0u && most) atomicMax(&b.x[1], most);
+}
+
+// behind the list kernel of a turn: the count the callback reads never exceeds the buffers (what lay beyond took its A bit back)
+__global__ void ld_probe_clamp_kernel(unsigned int *count, uint32_t cap, unsigned long long *x) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    const unsigned int n = *count;
+    x[3] = n;
+    if (n > cap) *count = cap;
+  }
+}
+
+// behind the callback: every listed seed has its answer now.  The answer bytes are left zero, as the next list's callback is
+// promised them; the occluded ones are counted by wave ballot, one atomic per wave.
+__global__ __launch_bounds__(256) void ld_probe_apply_kernel(ListProbeArgs b, const uint32_t *idx, uint8_t *answers, const unsigned int *count, uint32_t cap) {
+  const uint32_t n_raw = *count;
+  const uint32_t n = n_raw < cap ? n_raw : cap;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  const uint64_t n_up = ((uint64_t)n + 63u) & ~63ull;       // (whole waves go round the loop together)
+  uint32_t wave_occ = 0;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_up; i += stride) {
+    bool occ = false;
+    if (i < n) {
+      const uint32_t bit_at = idx[i];
+      const uint32_t bit = 1u << (bit_at & 31u);
+      occ = answers[i] != 0;
+      atomicOr(&b.B[bit_at >> 5], bit);
+      if (occ) { atomicAnd(&b.A[bit_at >> 5], ~bit); answers[i] = 0; }
+    }
+    wave_occ += (uint32_t)__builtin_popcountll(__ballot(occ));
+  }
+  if ((threadIdx.x & 63u) == 0u && wave_occ) atomicAdd(&b.x[2], (unsigned long long)wave_occ);
+}
+
+// a.ctr: [0] the ticket (reset every turn), [1] accepted draws and [2] attempts made (both run over the turns),
+// [3] the visits this turn left unsettled (reset every turn).  pr: the turn's list (seg, idx, cap, count) and the camera-to-world.
+template <class LensT, bool kTables, bool PO>
+__global__ __launch_bounds__(kLdBlock) void list_draws_probed_kernel(ListDrawArgs a, ProbeArgs pr, ListProbeArgs b) {
+  __shared__ DevTerm s_terms[kTables ? kMaxTerms : 1];
+  __shared__ DevLens s_k;
+  if (PO) {
+    if (kTables) {
+      const uint32_t nt = a.lens->n_terms;
+      for (uint32_t i = threadIdx.x; i < nt; i += kLdBlock) s_terms[i] = a.terms[i];
+    }
+    if (threadIdx.x == 0) {
+      s_k = *a.lens;
+      s_k.lambda_pow[0] = 1.0; s_k.lambda_pow[1] = a.lambda;
+      for (uint32_t e = 2; e <= kMaxExp; ++e) s_k.lambda_pow[e] = ipow_u(a.lambda, e);     // lens_ipow, like the host
+    }
+    __syncthreads();
+  }
+  LensT L{};
+  if constexpr (kTables) L.terms = s_terms;
+  L.k = &s_k;
+  const lentil_params &P = a.P;
+  const VisitsDev &V = a.V;
+  const uint32_t lane = threadIdx.x & 63u;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  const unsigned long long n_groups = (a.v_end - a.v_begin + 63u) / 64u;
+  const double qnan = __builtin_nan("");
+  // The wave's sums go out once, behind the ticket loop.  Inside it, at its end, a second `if (lane == 0u)` in front of the
+  // ticket's own made the compiler send lanes 1 ... 63 straight back to the ticket's readlane, past lane 0 and its atomic
+  // (jump threading over the two equal conditions): they read ticket 0 again and never left.  The loop's body must not end
+  // in a branch on the lane.
+  unsigned long long wave_attempts = 0, wave_open = 0;
+  for (;;) {
+    unsigned long long g = 0;
+    if (lane == 0u) g = atomicAdd(&a.ctr[0], 1ull);
+    g = ld_readlane(g, 0);
+    if (g >= n_groups) break;
+    // ---- the visits of the group that are not settled, lane = visit
+    const uint64_t v = a.v_begin + g * 64u + lane;
+    LdVisitState S;
+    S.off = 0u; S.k0 = kLdSettled; S.accepted = 0u; S.pad = 0u;
+    if (v < a.v_end) S = b.st[v - a.v_begin];
+    const bool open = S.k0 != kLdSettled;
+    unsigned long long todo = __ballot(open);      // (a group with nothing open falls through the empty loop below)
+    VisitInfo I{};
+    int vpx = 0, vpy = 0;
+    float wpx = 0.f, wpy = 0.f, wpz = 0.f, wtime = 0.f;
+    uint32_t exempt_u = 0u;
+    if (open) {
+      const float invd = V.inv_density ? V.inv_density[v] : P.inverse_sample_density;
+      const float4 pos_z = V.pos_z[v];
+      const float4 raydir_time = V.raydir_time[v];
+      I = visit_prologue(P, a.lens_length, V.rgba[v], pos_z, raydir_time, V.volume_ignore[v], V.transmission[v], invd, V.cam);
+      visit_pixel(V, v, vpx, vpy);
+      wpx = pos_z.x; wpy = pos_z.y; wpz = pos_z.z; wtime = raydir_time.w;
+      exempt_u = probe_from_skydome(pos_z) ? 1u : 0u;
+    }
+    // ---- the set lanes one after another, lane = attempt
+    while (todo) {
+      const int src = __builtin_ctzll(todo);
+      todo &= todo - 1ull;
+      const float cs[3] = {ld_readlane(I.cs[0], src), ld_readlane(I.cs[1], src), ld_readlane(I.cs[2], src)};
+      const int px = (int)ld_readlane((uint32_t)vpx, src), py = (int)ld_readlane((uint32_t)vpy, src);
+      const uint32_t samples = ld_readlane((uint32_t)I.samples, src);
+      const uint32_t off = ld_readlane(S.off, src);
+      const uint32_t k_first = ld_readlane(S.k0, src);
+      const bool exempt = ld_readlane(exempt_u, src) != 0u;
+      const float org[3] = {ld_readlane(wpx, src), ld_readlane(wpy, src), ld_readlane(wpz, src)};
+      const float time = ld_readlane(wtime, src);
+      const uint32_t visit = (uint32_t)(a.v_begin + g * 64u) + (uint32_t)src;
+      const uint32_t max_total = samples * 5u;                           // unsigned, as the reference's max_total_samples
+      const uint32_t *A = b.A + off, *B = b.B + off;
+      uint32_t accepted = ld_readlane(S.accepted, src);                  // exact while `clean`
+      uint32_t bound = accepted;                                         // what the accepted count can be at most
+      uint32_t made = 0, k_resume = k_first;
+      bool clean = true;                                                 // every slab so far is final
+      for (uint32_t k0 = k_first; k0 < max_total && bound < samples; k0 = (max_total - k0 > kLdSlab) ? k0 + kLdSlab : max_total) {
+        const uint32_t attempt = k0 + lane;
+        const bool commit = max_total - k0 > lane;                      // attempt < max_total, without the sum's wrap
+
+        uint32_t code = LENTIL_POINT_VIGNETTED;
+        double xy0 = qnan, xy1 = qnan;
+        int tries = 0;
+        bool dirty = false;
+        uint32_t pend_m = 0;
+        float pend_lx = 0.f, pend_ly = 0.f;
+        if (PO) {
+          const DevLens &k = L.consts();
+          const double target[3] = {-(double)cs[0] * 10.0, -(double)cs[1] * 10.0, -(double)cs[2] * 10.0};   // src/lentil_filter.cpp:271
+          bool ok = false;
+          bool trying = commit && tries <= P.vignetting_retries;
+          double sensor[4] = {0.0, 0.0, 0.0, 0.0};
+          while (__any(trying)) {
+            const uint32_t m = attempt + (uint32_t)tries;
+            bool occluded = false, known = true;
+            if (trying && !exempt) {
+              const uint32_t bit = 1u << (m & 31u);
+              const bool sa = (__hip_atomic_load(&A[m >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit) != 0u;
+              const bool sb = (B[m >> 5] & bit) != 0u;
+              occluded = sb && !sa;
+              known = sb;
+            }
+            const bool solve = trying && !occluded;
+            double ax, ay;
+            po_aperture_sample(P, a.bokeh, a.bokeh.cdfRow, (uint32_t)(px * py + px), m, ax, ay);
+            NewtonState s;
+            newton_init(s);
+            while (solve && newton_continue(s)) newton_iter(L, target, ax, ay, s);
+            double out4;
+            const float transmittance = (float)newton_finish(L, s, out4);
+            bool pass = !(transmittance <= 0);
+            const double ipx = s.x + s.dx * k.back_focal_length;
+            const double ipy = s.y + s.dy * k.back_focal_length;
+            if (ipx * ipx + ipy * ipy > k.inner_pupil_radius * k.inner_pupil_radius) pass = false;
+            if (!solve) pass = false;
+            if (trying) {
+              if (pass) {
+                sensor[0] = s.x; sensor[1] = s.y; sensor[2] = s.dx; sensor[3] = s.dy;
+                ok = true; trying = false;
+                if (!known) { dirty = true; pend_m = m; pend_lx = (float)(-ax * 0.1); pend_ly = (float)(-ay * 0.1); }   // src/lentil.h:614
+              } else {
+                ++tries; trying = tries <= P.vignetting_retries;
+              }
+            }
+          }
+          if (ok) {
+            const double sen0 = sensor[0] + sensor[2] * -P.sensor_shift;
+            const double sen1 = sensor[1] + sensor[3] * -P.sensor_shift;
+            uint32_t pn = 0;
+            code = po_sensor_to_pixel_xy(P, sen0, sen1, pn, xy0, xy1) ? pn : LENTIL_POINT_OUTSIDE;
+          }
+        } else if (commit) {
+          TlRay ray;
+          if (thinlens_ray(P, a.bokeh, a.bokeh.cdfRow, cs, px, py, attempt, ray)) {
+            bool occluded = false, known = true;
+            if (!exempt) {
+              const uint32_t bit = 1u << (attempt & 31u);
+              const bool sa = (__hip_atomic_load(&A[attempt >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit) != 0u;
+              const bool sb = (B[attempt >> 5] & bit) != 0u;
+              occluded = sb && !sa;
+              known = sb;
+            }
+            if (!occluded) {                                              // (an occluded attempt is lost)
+              const float image_dist_focusdist =
+                  (float)(((double)-P.focal_length * -P.focus_distance) / ((double)-P.focal_length + -P.focus_distance));
+              uint32_t pn = 0;
+              float fx, fy;
+              code = thinlens_project_xy(P, ray, image_dist_focusdist, pn, fx, fy) ? pn : LENTIL_POINT_OUTSIDE;
+              xy0 = (double)fx; xy1 = (double)fy;
+              if (!known) { dirty = true; pend_m = attempt; pend_lx = ray.lx; pend_ly = ray.ly; }
+            }
+          }
+        }
+
+        // ---- who asks: the dirty lanes the reference reaches whatever the open answers are
+        const bool success = commit && !dirty && code < LENTIL_POINT_OUTSIDE;
+        const unsigned long long okm = __ballot(success);
+        const unsigned long long dm = __ballot(dirty);
+        const bool ask = dirty && bound + (uint32_t)__builtin_popcountll((okm | dm) & below) < samples;
+        const unsigned long long am = __ballot(ask);
+        if (am) {
+          clean = false;
+          bool win = false;
+          const uint32_t bit = 1u << (pend_m & 31u);
+          uint32_t *wa = b.A + off + (pend_m >> 5);
+          if (ask) win = (atomicOr(wa, bit) & bit) == 0u;
+          const unsigned long long wm = __ballot(win);
+          if (wm) {
+            const uint32_t slot = probe_wave_slot(pr.count, wm, lane);
+            if (win) {
+              if (slot < pr.cap) {
+                float c2w[4][4];
+                probe_cam_to_world(V.cam, pr, time, c2w);
+                float tgt[3];
+                probe_target(P, c2w, pend_lx, pend_ly, 0.0f, tgt);
+                lentil_probe_segment sg;
+                sg.origin[0] = org[0]; sg.origin[1] = org[1]; sg.origin[2] = org[2];
+                sg.target[0] = tgt[0]; sg.target[1] = tgt[1]; sg.target[2] = tgt[2];
+                pr.seg[slot] = sg;
+                pr.idx[slot] = off * 32u + pend_m;
+              } else {
+                atomicAnd(wa, ~bit);
+              }
+            }
+          }
+        }
+        if (clean) {
+          // ---- the reference's selection, as list_draws_kernel makes it
+          const bool take = success && accepted + (uint32_t)__builtin_popcountll(okm & below) < samples;
+          const unsigned long long tm = __ballot(take);
+          const uint32_t nt = (uint32_t)__builtin_popcountll(tm);
+          if (tm) {
+            const unsigned long long slot = list_wave_slot(&a.ctr[1], tm, lane);
+            if (take && slot < a.capacity) {
+              lentil_draw r;
+              r.visit = visit; r.attempt = attempt; r.pixel = code; r.tries = tries;
+              r.xy[0] = xy0; r.xy[1] = xy1;
+              a.out[slot] = r;
+            }
+          }
+          accepted += nt;
+          bound = accepted;
+          if (accepted >= samples) made = k0 + (uint32_t)(63 - __builtin_clzll(tm)) + 1u;
+          else made = (max_total - k0 > kLdSlab) ? k0 + kLdSlab : max_total;
+          k_resume = (max_total - k0 > kLdSlab) ? k0 + kLdSlab : max_total;
+        } else {
+          bound += (uint32_t)__builtin_popcountll(okm | dm);
+        }
+      }
+      if (clean) wave_attempts += made; else ++wave_open;
+      if ((int)lane == src) {
+        LdVisitState s;
+        s.off = off; s.k0 = clean ? kLdSettled : k_resume; s.accepted = accepted; s.pad = 0u;
+        b.st[v - a.v_begin] = s;
+      }
+    }
+  }
+  if (lane == 0u) {
+    if (wave_attempts) atomicAdd(&a.ctr[2], wave_attempts);
+    if (wave_open) atomicAdd(&a.ctr[3], wave_open);
   }
 }
