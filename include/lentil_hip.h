@@ -237,7 +237,8 @@ typedef struct lentil_pass_totals {
   double scan_ms, draw_ms, resolve_ms;
 } lentil_pass_totals;
 
-/* one accepted draw, for index-parity tests: (visit, attempt n, linear pixel) */
+/* one accepted draw, for index-parity tests: (visit, attempt n, linear pixel).  Polynomial optics with abb_chromatic != 0:
+ * attempt is n | channel << 30, channel 0, 1, 2 for the reference's -1, 0, 1 (an attempt can have three records). */
 typedef struct lentil_draw_record {
   uint32_t visit;
   uint32_t attempt;
@@ -829,11 +830,13 @@ int lentil_hip_trace_points_path(lentil_hip_ctx *ctx, int *path);
  *   pixel       px | py << 16: the region-relative source pixel (the px, py of the draws' seed)
  *   flags       LENTIL_PLAN_REDISTRIBUTE: the visit is redistributed
  *   totals      optional, host memory: [0] visits in the range, [1] redistributed ones, [2] the sum of their samples -- an
- *               upper bound on what list_draws finds for the same range: size its `out` with it.
+ *               upper bound on what list_draws finds for the same range: size its `out` with it (the chromatic list of
+ *               LENTIL_DRAWS_CHANNELS: 11 times it).
  *   flags LENTIL_PLAN_DEVICE_POINTERS: `out` is device memory of the context's GPU.  With it and totals == NULL the call
  *   only enqueues on lentil_hip_stream(ctx); in every other case it returns when out / totals are filled.
  *
- * lentil_hip_list_draws: polynomial optics with abb_chromatic == 0 and the thin lens with abb_chromatic <= 0.
+ * lentil_hip_list_draws: polynomial optics with abb_chromatic == 0 and the thin lens with abb_chromatic <= 0; polynomial
+ * optics with abb_chromatic != 0 under LENTIL_DRAWS_CHANNELS (further down).
  *   A redistributed visit contributes one record for each of the first `samples` attempts n < 5 * samples whose trace is a
  *   pixel -- the attempts the reference's loop accepts before it stops.  The trace of attempt n is
  *   lentil_hip_trace_points' for (plan.cs, plan.pixel, n), the arithmetic is trace_points_kernel's operation for operation:
@@ -850,9 +853,29 @@ int lentil_hip_trace_points_path(lentil_hip_ctx *ctx, int *path);
  *                    the call returns when the list is complete -- with LENTIL_DRAWS_DEVICE_POINTERS (`out` is device memory
  *                    of the context's GPU) too.
  *   attempts         optional, host memory: the attempts made -- the reference's attempted_draws for these visits
- *   LENTIL_ERR_UNSUPPORTED, with a message: polynomial optics with abb_chromatic != 0 (three traces per attempt under another
- *   counting rule), the thin lens with abb_chromatic > 0 (the channels follow the pass's xor128 order; trace_points does not
- *   offer it either).
+ *   LENTIL_ERR_UNSUPPORTED, with a message: polynomial optics with abb_chromatic != 0 without LENTIL_DRAWS_CHANNELS (three
+ *   traces per attempt under another counting rule: below), the thin lens with abb_chromatic > 0 (the channels follow the
+ *   pass's xor128 order; trace_points does not offer it either), with or without that flag.
+ *   flags LENTIL_DRAWS_CHANNELS: the caller reads lentil_draw::attempt as n | channel << 30, channel 0, 1, 2 for the
+ *   reference's -1, 0, 1 -- as lentil_draw_record::attempt of a pass's draw log carries it.  A caller that does not know of
+ *   the channel bits would misread `attempt`, so the chromatic list is given only to one who sets the flag.  For every mode
+ *   the plain list serves, the flag changes nothing: the plain list, bit for bit (channel bits 0).
+ *     Polynomial optics with abb_chromatic != 0 (src/lentil_filter.cpp:248-299): attempt n traces the three channels of
+ *     lentil_hip_draw_channels, each with the seeds n + try, its own vignetting_retries + 1 tries and its own wavelength.
+ *     Every channel that gets through the lens and lands in the frame is a record: its `tries`, `xy` and `pixel` are that
+ *     channel's own -- lentil_hip_trace_points' for (plan.cs, plan.pixel, n) at the channel's wavelength.  Every channel that
+ *     does not takes one off the reference's `count`, the attempt itself adds one: count += successes - 2, a signed count
+ *     that may go down.  Attempts are made while count < samples and n < 5 * samples.  So a visit yields up to 11 * samples
+ *     records (count + 2 * attempts), and plan_visits' totals[2] no longer bounds the list: 11 * totals[2] does; or ask with
+ *     capacity 0 first and size `out` by *n_draws.  *n_draws counts records, *attempts attempts (the reference's
+ *     attempted_draws: one per attempt, not one per channel).  abb_chromatic > 0: `lambda` must be 0 (LENTIL_ERR_INVALID
+ *     otherwise; the wavelengths are the mode's own), and channel c belongs to colour component c alone (rgb_weight of
+ *     lentil_hip_draw_channels).  abb_chromatic < 0: three white channels at `lambda` (0: params.lambda_bw) -- every attempt
+ *     that lands gives three records with one pixel.  The channel bits need 5 * samples + vignetting_retries < 2^30, where
+ *     `samples` is samples_override, or 2000, the draw count formula's clamp, without one: with set_params' limit on
+ *     samples_override (2^24) only a vignetting_retries near 2^30 breaks it; refused with LENTIL_ERR_UNSUPPORTED.
+ *     With LENTIL_DRAWS_PROBED as well: LENTIL_ERR_UNSUPPORTED (not built; a pass under a probe refuses this mode too).
+ *     Capacity, LENTIL_DRAWS_DEVICE_POINTERS and lentil_hip_list_draws_path are as without the flag.
  *   flags LENTIL_DRAWS_PROBED: the list under the context's occlusion probe (lentil_hip_set_occlusion_probe or
  *   lentil_hip_set_occlusion_probe_device, with its camera_to_world or the fp64 inverse, motion keys included) -- the draw
  *   list of the reference's pass under that probe.  Without the flag a probe is ignored: the unprobed list, bit for bit.
@@ -900,9 +923,10 @@ int lentil_hip_plan_visits(lentil_hip_ctx *ctx, uint64_t first_visit, uint64_t n
 
 #define LENTIL_DRAWS_DEVICE_POINTERS 1u
 #define LENTIL_DRAWS_PROBED 2u              /* the list under the context's occlusion probe (see above) */
+#define LENTIL_DRAWS_CHANNELS 4u            /* the caller reads lentil_draw::attempt as n | channel << 30 (see above) */
 typedef struct lentil_draw {                /* 32 bytes */
   uint32_t visit;     /* index into the bound stream */
-  uint32_t attempt;   /* the reference's total_samples_taken of the draw */
+  uint32_t attempt;   /* the reference's total_samples_taken of the draw; the chromatic list: | channel << 30 */
   uint32_t pixel;     /* linear pixel ix + iy * xres */
   int32_t  tries;     /* vignetted (LENTIL_DRAWS_PROBED: or occluded) tries before the one that got through (thin lens: 0) */
   double   xy[2];     /* continuous pixel coordinates before floor (trace_points' out_xy) */
@@ -918,6 +942,14 @@ typedef struct lentil_draw_list {
 } lentil_draw_list;
 int lentil_hip_list_draws(lentil_hip_ctx *ctx, const lentil_draw_list *list);
 int lentil_hip_list_draws_path(lentil_hip_ctx *ctx, int *path);   /* 0 thin lens / none yet, 1 interpreter, 2 compiled-in lens */
+/* The colour channels the draw loop of these parameters traces per attempt (src/lentil_filter.cpp:254-268); needs no context
+ * and no GPU.  *n_channels: 3 for polynomial optics with abb_chromatic != 0, else 1 (the thin lens with abb_chromatic > 0
+ * picks a channel per attempt from xor128: not described here).  lambda[c]: the channel's wavelength in micrometres, the
+ * fp32 arithmetic of the reference widened to double -- abb_chromatic > 0: lerp(1 - c, 0.35, 0.55), 0.55, lerp(c, 0.55, 0.85);
+ * otherwise params.lambda_bw throughout (all three entries are always filled).  rgb_weight[c][k] (optional): what a draw of
+ * channel c adds to colour component k, as a factor -- {3,0,0}, {0,3,0}, {0,0,3} for abb_chromatic > 0, else 1 everywhere;
+ * alpha and the weight always take 1.  The pass and the chromatic list take their channels from this very function. */
+int lentil_hip_draw_channels(const lentil_params *p, uint32_t *n_channels, double lambda[3], float rgb_weight[3][3]);
 
 /* --- single-function device tests (parity of the optics primitives) -----------------
  * Runs n independent evaluations on the GPU; host pointers in/out.

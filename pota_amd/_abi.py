@@ -17,6 +17,7 @@ POINTS_PATH_THIN_LENS, POINTS_PATH_INTERPRETER, POINTS_PATH_COMPILED_IN = 0, 1, 
 PLAN_DEVICE_POINTERS, PLAN_REDISTRIBUTE = 1, 1                                                         # lentil_hip_plan_visits flags, lentil_visit_plan.flags
 DRAWS_DEVICE_POINTERS = 1
 DRAWS_PROBED = 2                                                                                        # lentil_draw_list::flags
+DRAWS_CHANNELS = 4                                                                                      # ... attempt is n | channel << 30
 DRAWS_PATH_THIN_LENS, DRAWS_PATH_INTERPRETER, DRAWS_PATH_COMPILED_IN = 0, 1, 2                        # lentil_hip_list_draws_path
 
 

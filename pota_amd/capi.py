@@ -31,7 +31,7 @@ EXPORTS = [
     "lentil_hip_lens_is_compiled", "lentil_hip_set_lens_mode",
     "lentil_hip_focus_search", "lentil_hip_test_y0_intersection", "lentil_hip_camera_rays", "lentil_hip_camera_rays_path",
     "lentil_hip_trace_points", "lentil_hip_trace_points_path",
-    "lentil_hip_plan_visits", "lentil_hip_list_draws", "lentil_hip_list_draws_path",
+    "lentil_hip_plan_visits", "lentil_hip_list_draws", "lentil_hip_list_draws_path", "lentil_hip_draw_channels",
     "lentil_hip_set_xor128_state", "lentil_hip_get_xor128_state", "lentil_hip_tl_chroma_stats", "lentil_hip_test_xor128_jump",
     "lentil_hip_host_alloc", "lentil_hip_host_free", "lentil_hip_visits_begin", "lentil_hip_visits_append",
     "lentil_hip_visits_wait", "lentil_hip_visits_end",
@@ -193,6 +193,7 @@ def load_library():
         "lentil_hip_plan_visits": (i, [vp, u64, u64, vp, C.c_uint32, C.POINTER(u64)]),
         "lentil_hip_list_draws": (i, [vp, C.POINTER(_abi.DrawList)]),
         "lentil_hip_list_draws_path": (i, [vp, C.POINTER(C.c_int)]),
+        "lentil_hip_draw_channels": (i, [C.POINTER(_abi.Params), C.POINTER(u32), C.POINTER(C.c_double), C.POINTER(C.c_float)]),
         "lentil_hip_set_xor128_state": (i, [vp, C.POINTER(C.c_uint32)]),
         "lentil_hip_get_xor128_state": (i, [vp, C.POINTER(C.c_uint32)]),
         "lentil_hip_tl_chroma_stats": (i, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
@@ -222,6 +223,19 @@ def load_library():
         raise RuntimeError("liblentil_hip.so ABI version mismatch")
     _lib = lib
     return lib
+
+
+def draw_channels(p):
+    """The colour channels the draw loop of these parameters traces per attempt (lentil_hip_draw_channels; no context, no GPU)
+    -> (n_channels, lambda: float64 [3], micrometres, rgb_weight: float32 [3, 3], channel x colour component)."""
+    import numpy as np
+    n = C.c_uint32()
+    lam = (C.c_double * 3)()
+    w = (C.c_float * 9)()
+    rc = load_library().lentil_hip_draw_channels(C.byref(p), C.byref(n), lam, w)
+    if rc != _abi.OK:
+        raise LentilError(rc, "lentil_hip_draw_channels")
+    return int(n.value), np.array(lam[:], np.float64), np.array(w[:], np.float32).reshape(3, 3)
 
 
 def sphere_occluder_device():
@@ -603,16 +617,27 @@ class Context:
         self._chk(self.lib.lentil_hip_plan_visits(self.h, first, n, ptr, flags, tot))
         return out, (tuple(int(t) for t in tot) if totals else None)
 
-    def list_draws(self, first=0, n=None, capacity=None, lam=0.0, device=False, probed=False):
+    def list_draws(self, first=0, n=None, capacity=None, lam=0.0, device=False, probed=False, channels=False):
         """The accepted draws of the bound visits first ... first + n - 1 (lentil_hip_list_draws) -> (records, n_draws,
         attempts): records a numpy array of _abi.Draw (visit, attempt, pixel, tries, xy), in no particular order, the first
         min(n_draws, capacity) of it filled and returned; n_draws the accepted draws found (above capacity: ask again with more
         room); attempts the attempts made.  capacity None: sized from plan_visits' totals[2], which always suffices.
         lam: micrometres, 0 = params.lambda_bw.  device=True: the records stay on the GPU, a uint8 [capacity, 32] torch tensor,
         whole (the call returns when it is filled).  probed=True (_abi.DRAWS_PROBED): the list under the context's occlusion
-        probe -- tries then counts occluded tries too, and the probe's callback is called once per turn, on this thread."""
+        probe -- tries then counts occluded tries too, and the probe's callback is called once per turn, on this thread.
+        channels=True (_abi.DRAWS_CHANNELS): the caller reads attempt as n | channel << 30 -- what polynomial optics with
+        abb_chromatic != 0 need (up to three records per attempt, a channel's tries / xy / pixel its own); any other mode gives
+        the plain list.  totals[2] does not bound that list, so capacity None then sizes it by a counting call (capacity 0)."""
         first, n = self._visit_range(first, n)
-        if capacity is None:
+        flags = (_abi.DRAWS_PROBED if probed else 0) | (_abi.DRAWS_CHANNELS if channels else 0)
+        if capacity is None and channels and n:
+            cnt = C.c_uint64()
+            b = _abi.DrawList()
+            b.first_visit, b.n_visits, b.capacity, b.lam, b.flags = first, n, 0, float(lam), flags
+            b.n_draws = C.pointer(cnt)
+            self._chk(self.lib.lentil_hip_list_draws(self.h, C.byref(b)))
+            capacity = cnt.value
+        elif capacity is None:
             capacity = self.plan_visits(first, n)[1][2] if n else 0
         capacity = int(capacity)
         nd, att = C.c_uint64(), C.c_uint64()
@@ -625,8 +650,7 @@ class Context:
         else:
             out = np.empty(capacity, _abi.Draw)
             b.out, b.flags = (out.ctypes.data if capacity else None), 0
-        if probed:
-            b.flags |= _abi.DRAWS_PROBED
+        b.flags |= flags
         self._chk(self.lib.lentil_hip_list_draws(self.h, C.byref(b)))
         if not device:
             out = out[:min(nd.value, capacity)]

@@ -2101,22 +2101,40 @@ static int enqueue_chunk_draws(lentil_hip_ctx *ctx, int ci, DrawArgs &da, int bl
   return LENTIL_OK;
 }
 
+// The wavelength channels of the draw loop, src/lentil_filter.cpp:254-268 (float arithmetic of linear_interpolate,
+// src/global.h:3-5): polynomial optics with abb_chromatic != 0 trace three per attempt -- abb_chromatic > 0 at three
+// wavelengths, each feeding its own colour component three-fold; abb_chromatic < 0 three white channels at lambda_bw, like
+// upstream.  Everything else draws one white channel at lambda_bw.  The pass (init_draw_args) and the chromatic list
+// (lentil_hip_list_draws) both take their channels from here.  -> the number of channels
+static uint32_t draw_channels_of(const lentil_params &P, double lambda[3], float rgb_weight[3][3]) {
+  const uint32_t n = (P.cameraType == LENTIL_POLYNOMIAL_OPTICS && P.abb_chromatic != 0.0f) ? 3u : 1u;
+  const bool coloured = n == 3u && P.abb_chromatic > 0.0f;
+  lambda[0] = lambda[1] = lambda[2] = (double)P.lambda_bw;
+  if (coloured) {
+    const float c = P.abb_chromatic;
+    const float p0 = (float)(1.0 - (double)c);
+    lambda[0] = (double)(0.35f + p0 * (0.55f - 0.35f));
+    lambda[1] = (double)0.55f;
+    lambda[2] = (double)(0.55f + c * (0.85f - 0.55f));
+  }
+  if (rgb_weight)
+    for (int ch = 0; ch < 3; ++ch)
+      for (int k = 0; k < 3; ++k) rgb_weight[ch][k] = coloured ? (ch == k ? 3.0f : 0.0f) : 1.0f;
+  return n;
+}
+
+LENTIL_API int lentil_hip_draw_channels(const lentil_params *p, uint32_t *n_channels, double lambda[3], float rgb_weight[3][3]) {
+  if (!p || !n_channels || !lambda) return LENTIL_ERR_INVALID;
+  *n_channels = draw_channels_of(*p, lambda, rgb_weight);
+  return LENTIL_OK;
+}
+
 static void init_draw_args(lentil_hip_ctx *ctx, DrawArgs &da) {
   const lentil_params &P = ctx->P;
   const int C = ctx->n_chunks;
   da.P = P;
-  // wavelength channels of the polynomial-optics draw loop, src/lentil_filter.cpp:254-268 (float arithmetic of
-  // linear_interpolate, src/global.h:3-5); abb_chromatic < 0 runs three white channels at 0.55, like upstream
-  da.n_channels = (P.cameraType == LENTIL_POLYNOMIAL_OPTICS && P.abb_chromatic != 0.0f) ? 3 : 1;
+  da.n_channels = (int)draw_channels_of(P, da.lambda, nullptr);
   da.chroma_weights = P.abb_chromatic > 0.0f ? 1 : 0;
-  da.lambda[0] = da.lambda[1] = da.lambda[2] = (double)P.lambda_bw;
-  if (da.n_channels == 3 && da.chroma_weights) {
-    const float c = P.abb_chromatic;
-    const float p0 = (float)(1.0 - (double)c);
-    da.lambda[0] = (double)(0.35f + p0 * (0.55f - 0.35f));
-    da.lambda[1] = (double)0.55f;
-    da.lambda[2] = (double)(0.55f + c * (0.85f - 0.55f));
-  }
   da.lens = P.cameraType == LENTIL_POLYNOMIAL_OPTICS ? ctx->d_lens : nullptr;
   da.terms = ctx->d_terms;
   da.bokeh = ctx->bokeh;
@@ -4364,12 +4382,26 @@ LENTIL_API int lentil_hip_list_draws(lentil_hip_ctx *ctx, const lentil_draw_list
   if ((rc = list_range_check(ctx, list->first_visit, list->n_visits))) return rc;
   const bool po = ctx->P.cameraType == LENTIL_POLYNOMIAL_OPTICS;
   if (ctx->P.bokeh_enable_image && !ctx->have_bokeh) return fail(ctx, LENTIL_ERR_INVALID, "bokeh_enable_image needs set_bokeh first");
-  if (po && ctx->P.abb_chromatic != 0.0f)
+  const bool probed = (list->flags & LENTIL_DRAWS_PROBED) != 0u;
+  // polynomial optics with abb_chromatic != 0: the chromatic list, for a caller who reads the channel bits of `attempt`
+  const bool chroma = po && ctx->P.abb_chromatic != 0.0f && (list->flags & LENTIL_DRAWS_CHANNELS) != 0u;
+  if (po && ctx->P.abb_chromatic != 0.0f && !chroma)
     return fail(ctx, LENTIL_ERR_UNSUPPORTED, "list_draws: polynomial optics with abb_chromatic != 0 trace three channels per attempt under another counting rule");
   if (!po && ctx->P.abb_chromatic > 0.0f)
     return fail(ctx, LENTIL_ERR_UNSUPPORTED, "list_draws: the thin lens with abb_chromatic > 0 draws its channels in the pass's xor128 order");
+  if (chroma && probed)
+    return fail(ctx, LENTIL_ERR_UNSUPPORTED, "list_draws: LENTIL_DRAWS_PROBED with polynomial optics and abb_chromatic != 0 (every channel's tries "
+                                             "under the probe) is not built; the pass refuses the pair too");
+  if (chroma && ctx->P.abb_chromatic > 0.0f && list->lambda != 0.0)
+    return fail(ctx, LENTIL_ERR_INVALID, "list_draws: with abb_chromatic > 0 the channels' wavelengths are the mode's own (lentil_hip_draw_channels): lambda must be 0");
+  if (chroma) {
+    // the channel rides in bits 30-31 of `attempt`: every seed attempt + try must stay below 2^30
+    const uint64_t most = ctx->P.samples_override > 0 ? (uint64_t)ctx->P.samples_override : 2000ull;      // (get_draw_count's clamp)
+    const uint64_t retries = ctx->P.vignetting_retries > 0 ? (uint64_t)ctx->P.vignetting_retries : 0ull;
+    if (5ull * most + retries >= (1ull << 30))
+      return fail(ctx, LENTIL_ERR_UNSUPPORTED, "list_draws: LENTIL_DRAWS_CHANNELS needs 5 * samples + vignetting_retries < 2^30 (the channel takes bits 30-31 of attempt)");
+  }
   if (list->capacity && !list->out) return fail(ctx, LENTIL_ERR_INVALID, "out is null with capacity > 0");
-  const bool probed = (list->flags & LENTIL_DRAWS_PROBED) != 0u;
   if (probed && !probing(ctx))
     return fail(ctx, LENTIL_ERR_INVALID, "list_draws: LENTIL_DRAWS_PROBED needs an occlusion probe (set_occlusion_probe or set_occlusion_probe_device)");
   *list->n_draws = 0;
@@ -4402,7 +4434,24 @@ LENTIL_API int lentil_hip_list_draws(lentil_hip_ctx *ctx, const lentil_draw_list
     if (!device && written) HIP_TRY(ctx, hipMemcpy(list->out, d_out, (size_t)written * sizeof(lentil_draw), hipMemcpyDeviceToHost));
     return LENTIL_OK;
   }
-  if (po) {
+  if (chroma) {
+    // the wavelengths are the pass's own (draw_channels_of); abb_chromatic < 0: the caller's lambda for all three, one trace
+    ListChromaArgs ch{};
+    draw_channels_of(ctx->P, ch.lambda, nullptr);
+    ch.n_traces = ctx->P.abb_chromatic > 0.0f ? 3u : 1u;
+    if (ch.n_traces == 1u) ch.lambda[0] = ch.lambda[1] = ch.lambda[2] = a.lambda;
+#define LENTIL_LAUNCH_GEN(NAME)                                                                              \
+    if (!path && ctx->use_generated && ctx->lens_hash == gen::Lens_##NAME::kTableHash) {                      \
+      hipLaunchKernelGGL((list_draws_chroma_kernel<GenLens<gen::Lens_##NAME>, false>), grid, dim3(kLdBlock), 0, ctx->stream, a, ch); \
+      path = 2;                                                                                              \
+    }
+    LENTIL_GENERATED_LENSES(LENTIL_LAUNCH_GEN)
+#undef LENTIL_LAUNCH_GEN
+    if (!path) {
+      hipLaunchKernelGGL((list_draws_chroma_kernel<LdsLens, true>), grid, dim3(kLdBlock), 0, ctx->stream, a, ch);
+      path = 1;
+    }
+  } else if (po) {
 #define LENTIL_LAUNCH_GEN(NAME)                                                                              \
     if (!path && ctx->use_generated && ctx->lens_hash == gen::Lens_##NAME::kTableHash) {                      \
       hipLaunchKernelGGL((list_draws_kernel<GenLens<gen::Lens_##NAME>, false, true>), grid, dim3(kLdBlock), 0, ctx->stream, a); \

@@ -2,7 +2,9 @@
 // (lentil_hip_plan_visits, lentil_hip_list_draws): what the visit prologue decides per visit (src/lentil_filter.cpp:105-240),
 // and the accepted draws of a visit range -- the first `samples` attempts among 0 ... 5 * samples - 1 that get through the lens
 // and land in the frame (the loops of src/lentil_filter.cpp:249-300 and :311-447) -- with their continuous pixel coordinates.
-// No frame, no accumulators, no counter block, no xor128 state; occlusion probes only in the probed list at the end of this file.
+// No frame, no accumulators, no counter block, no xor128 state; occlusion probes only in the probed list further down.  Polynomial
+// optics with abb_chromatic != 0 -- three colour channels per attempt, counted by another rule -- have a kernel of their own at
+// the end of this file (list_draws_chroma_kernel, LENTIL_DRAWS_CHANNELS).
 //
 // plan_visits_kernel.  One lane per visit, 64 consecutive visits per wave and step (the five 16-byte columns are read
 // coalesced), grid-stride over such groups; visit_prologue and visit_pixel are the pass's own (load_work_visit), the weight
@@ -589,4 +591,193 @@ __global__ __launch_bounds__(kLdBlock) void list_draws_probed_kernel(ListDrawArg
     if (wave_attempts) atomicAdd(&a.ctr[2], wave_attempts);
     if (wave_open) atomicAdd(&a.ctr[3], wave_open);
   }
+}
+
+// ---------------------------------------------------------------------------------------
+// LENTIL_DRAWS_CHANNELS: polynomial optics with abb_chromatic != 0 (src/lentil_filter.cpp:248-299).  Attempt n traces three
+// colour channels with the same seeds n + try, each with its own vignetting_retries + 1 tries and its own wavelength.  Every
+// channel that gets through the lens and lands in the frame is a draw; every one that does not takes one off `count`, and the
+// attempt itself adds one: count += successes - 2, a signed count that may go down and below zero.  The loop runs while
+// count < samples and n < 5 * samples; steps are at most +1, so `samples` is hit exactly, and an attempt is made iff every
+// running count before it was below `samples` (accept_item_chroma, lentil_kernels.h, selects the same way over the pass's
+// result pool).  A visit yields up to 11 * samples records: count_final + 2 * attempts.
+//
+// list_draws_chroma_kernel: list_draws_kernel's ticket / prologue / readlane / slab structure.  Per slab every lane traces its
+// attempt once per channel with trace_points_kernel's loops, operation for operation, through one of three DevLens copies in
+// LDS whose lambda_pow are filled as list_draws_kernel fills its one.  With abb_chromatic < 0 the three channels share one
+// wavelength and the three traces are the same trace: it runs once (a wave-uniform decision) and stands for all three.
+// Selection: delta = successes - 2 on the lanes that commit, a signed inclusive prefix over the wave, running = count + prefix;
+// istar is the first lane whose running count reaches `samples`; the lanes up to istar were executed (all committed lanes if
+// none reaches it).  Their channels' records take consecutive slots through one atomic per slab (list_wave_slot3) and carry
+// the channel in bits 30-31 of `attempt`, as the pass's draw log does.  `count` is carried across slabs as int32.
+// The wave's attempts go out once, behind the ticket loop (the trap recorded at list_draws_probed_kernel: the loop's body must
+// not end in a branch on the lane).  Every loop is bounded as in list_draws_kernel, the channel loop by 3.
+// ---------------------------------------------------------------------------------------
+struct ListChromaArgs {
+  double lambda[3];                 // lentil_hip_draw_channels' wavelengths
+  uint32_t n_traces;                // 3: a trace per channel; 1: the channels share their wavelength, one trace stands for all
+};
+
+// One wave's wanted records -- up to three per lane, a mask per channel -- take consecutive slots of the list through one
+// atomic; a lane's own records lie side by side, channel 0 first.  Called by the whole wave, some mask != 0.  -> the lane's
+// first slot.
+LD_DEV unsigned long long list_wave_slot3(unsigned long long *count, unsigned long long m0, unsigned long long m1,
+                                          unsigned long long m2, uint32_t lane) {
+  const unsigned long long below = (1ull << lane) - 1ull;
+  const int first = __builtin_ctzll(m0 | m1 | m2);
+  unsigned long long base = 0;
+  if ((int)lane == first)
+    base = atomicAdd(count, (unsigned long long)(__builtin_popcountll(m0) + __builtin_popcountll(m1) + __builtin_popcountll(m2)));
+  base = ld_readlane(base, first);
+  return base + (unsigned long long)(__builtin_popcountll(m0 & below) + __builtin_popcountll(m1 & below) + __builtin_popcountll(m2 & below));
+}
+
+// LensT / kTables: LdsLens with the term table staged into LDS (the interpreter) or GenLens<Gen> of a compiled-in lens.
+template <class LensT, bool kTables>
+__global__ __launch_bounds__(kLdBlock) void list_draws_chroma_kernel(ListDrawArgs a, ListChromaArgs ch) {
+  __shared__ DevTerm s_terms[kTables ? kMaxTerms : 1];
+  __shared__ DevLens s_k[3];
+  if (kTables) {
+    const uint32_t nt = a.lens->n_terms;
+    for (uint32_t i = threadIdx.x; i < nt; i += kLdBlock) s_terms[i] = a.terms[i];
+  }
+  if (threadIdx.x < 3u) {
+    DevLens &k = s_k[threadIdx.x];
+    const double lam = ch.lambda[threadIdx.x];
+    k = *a.lens;
+    k.lambda_pow[0] = 1.0; k.lambda_pow[1] = lam;
+    for (uint32_t e = 2; e <= kMaxExp; ++e) k.lambda_pow[e] = ipow_u(lam, e);               // lens_ipow, like the host
+  }
+  __syncthreads();
+  LensT L{};
+  if constexpr (kTables) L.terms = s_terms;
+  const lentil_params &P = a.P;
+  const VisitsDev &V = a.V;
+  const uint32_t lane = threadIdx.x & 63u;
+  const unsigned long long n_groups = (a.v_end - a.v_begin + 63u) / 64u;
+  const uint32_t n_traces = ch.n_traces == 3u ? 3u : 1u;
+  const double qnan = __builtin_nan("");
+  unsigned long long wave_attempts = 0;
+  for (;;) {
+    unsigned long long g = 0;
+    if (lane == 0u) g = atomicAdd(&a.ctr[0], 1ull);
+    g = ld_readlane(g, 0);
+    if (g >= n_groups) break;
+    // ---- the prologue, lane = visit
+    const uint64_t v = a.v_begin + g * 64u + lane;
+    VisitInfo I{};
+    int vpx = 0, vpy = 0;
+    if (v < a.v_end) {
+      const float invd = V.inv_density ? V.inv_density[v] : P.inverse_sample_density;
+      I = visit_prologue(P, a.lens_length, V.rgba[v], V.pos_z[v], V.raydir_time[v], V.volume_ignore[v], V.transmission[v], invd, V.cam);
+      visit_pixel(V, v, vpx, vpy);
+    } else {
+      I.redistribute = false;
+    }
+    unsigned long long todo = __ballot(I.redistribute);
+    // ---- the set lanes one after another, lane = attempt
+    while (todo) {
+      const int src = __builtin_ctzll(todo);
+      todo &= todo - 1ull;
+      const float cs[3] = {ld_readlane(I.cs[0], src), ld_readlane(I.cs[1], src), ld_readlane(I.cs[2], src)};
+      const int px = (int)ld_readlane((uint32_t)vpx, src), py = (int)ld_readlane((uint32_t)vpy, src);
+      const uint32_t samples = ld_readlane((uint32_t)I.samples, src);
+      const uint32_t visit = (uint32_t)(a.v_begin + g * 64u) + (uint32_t)src;
+      const uint32_t max_total = samples * 5u;                           // (the host keeps 5 * samples + retries below 2^30)
+      int32_t count = 0;                                                 // the reference's `count`: signed, may go down
+      uint32_t made = 0;
+      for (uint32_t k0 = 0; k0 < max_total && count < (int32_t)samples; k0 = (max_total - k0 > kLdSlab) ? k0 + kLdSlab : max_total) {
+        const uint32_t attempt = k0 + lane;
+        const bool commit = max_total - k0 > lane;                      // attempt < max_total
+
+        uint32_t code0 = LENTIL_POINT_VIGNETTED, code1 = LENTIL_POINT_VIGNETTED, code2 = LENTIL_POINT_VIGNETTED;
+        double xa0 = qnan, xb0 = qnan, xa1 = qnan, xb1 = qnan, xa2 = qnan, xb2 = qnan;
+        int tries0 = 0, tries1 = 0, tries2 = 0;
+#pragma unroll 1
+        for (uint32_t c = 0; c < n_traces; ++c) {
+          L.k = &s_k[c];
+          uint32_t code = LENTIL_POINT_VIGNETTED;
+          double xy0 = qnan, xy1 = qnan;
+          int tries = 0;
+          const DevLens &k = L.consts();
+          const double target[3] = {-(double)cs[0] * 10.0, -(double)cs[1] * 10.0, -(double)cs[2] * 10.0};   // src/lentil_filter.cpp:271
+          bool ok = false;
+          bool trying = commit && tries <= P.vignetting_retries;
+          double sensor[4] = {0.0, 0.0, 0.0, 0.0};
+          while (__any(trying)) {
+            double ax, ay;
+            po_aperture_sample(P, a.bokeh, a.bokeh.cdfRow, (uint32_t)(px * py + px), attempt + (uint32_t)tries, ax, ay);
+            NewtonState s;
+            newton_init(s);
+            while (trying && newton_continue(s)) newton_iter(L, target, ax, ay, s);
+            double out4;
+            const float transmittance = (float)newton_finish(L, s, out4);
+            bool pass = !(transmittance <= 0);
+            const double ipx = s.x + s.dx * k.back_focal_length;
+            const double ipy = s.y + s.dy * k.back_focal_length;
+            if (ipx * ipx + ipy * ipy > k.inner_pupil_radius * k.inner_pupil_radius) pass = false;
+            if (trying) {
+              if (pass) {
+                sensor[0] = s.x; sensor[1] = s.y; sensor[2] = s.dx; sensor[3] = s.dy;
+                ok = true; trying = false;
+              } else {
+                ++tries; trying = tries <= P.vignetting_retries;
+              }
+            }
+          }
+          if (ok) {
+            const double sen0 = sensor[0] + sensor[2] * -P.sensor_shift;
+            const double sen1 = sensor[1] + sensor[3] * -P.sensor_shift;
+            uint32_t pn = 0;
+            code = po_sensor_to_pixel_xy(P, sen0, sen1, pn, xy0, xy1) ? pn : LENTIL_POINT_OUTSIDE;
+          }
+          // (selects, not an indexed array: the results stay in registers)
+          if (c == 0u) { code0 = code; xa0 = xy0; xb0 = xy1; tries0 = tries; }
+          if (c == 1u) { code1 = code; xa1 = xy0; xb1 = xy1; tries1 = tries; }
+          if (c == 2u) { code2 = code; xa2 = xy0; xb2 = xy1; tries2 = tries; }
+        }
+        if (n_traces == 1u) {
+          code1 = code2 = code0; xa1 = xa2 = xa0; xb1 = xb2 = xb0; tries1 = tries2 = tries0;
+        }
+
+        // ---- the reference's selection: count += successes - 2 per attempt, until it reaches `samples`
+        const bool ok0 = commit && code0 < LENTIL_POINT_OUTSIDE;
+        const bool ok1 = commit && code1 < LENTIL_POINT_OUTSIDE;
+        const bool ok2 = commit && code2 < LENTIL_POINT_OUTSIDE;
+        const int delta = commit ? (ok0 ? 1 : 0) + (ok1 ? 1 : 0) + (ok2 ? 1 : 0) - 2 : 0;
+        int incl = delta;
+        for (int off = 1; off < 64; off <<= 1) {
+          const int up = __shfl_up(incl, off);
+          if ((int)lane >= off) incl += up;
+        }
+        const int running = count + incl;                               // the count behind this lane's attempt
+        const unsigned long long rmask = __ballot(commit && running >= (int32_t)samples);
+        const int istar = rmask ? __builtin_ctzll(rmask) : 63;          // (lanes that do not commit have delta 0: lane 63 holds the slab's sum)
+        const bool executed = commit && (int)lane <= istar;
+        const unsigned long long m0 = __ballot(executed && ok0), m1 = __ballot(executed && ok1), m2 = __ballot(executed && ok2);
+        if (m0 | m1 | m2) {
+          unsigned long long slot = list_wave_slot3(&a.ctr[1], m0, m1, m2, lane);
+          lentil_draw r;
+          r.visit = visit;
+          if (executed && ok0) {
+            if (slot < a.capacity) { r.attempt = attempt; r.pixel = code0; r.tries = tries0; r.xy[0] = xa0; r.xy[1] = xb0; a.out[slot] = r; }
+            ++slot;
+          }
+          if (executed && ok1) {
+            if (slot < a.capacity) { r.attempt = attempt | (1u << 30); r.pixel = code1; r.tries = tries1; r.xy[0] = xa1; r.xy[1] = xb1; a.out[slot] = r; }
+            ++slot;
+          }
+          if (executed && ok2) {
+            if (slot < a.capacity) { r.attempt = attempt | (2u << 30); r.pixel = code2; r.tries = tries2; r.xy[0] = xa2; r.xy[1] = xb2; a.out[slot] = r; }
+          }
+        }
+        count = __builtin_amdgcn_readlane(running, istar);
+        // (the loop ends behind the attempt that brought the count to `samples`; a slab without it was attempted to its end)
+        if (rmask) made = k0 + (uint32_t)istar + 1u;
+        else made = (max_total - k0 > kLdSlab) ? k0 + kLdSlab : max_total;
+      }
+      wave_attempts += made;
+    }
+  }
+  if (lane == 0u && wave_attempts) atomicAdd(&a.ctr[2], wave_attempts);
 }

@@ -13,6 +13,8 @@ double-gauss, 9 visits per pixel, 2 % highlights, samples_override = 256.
 (c) The caller's side of the same question without list_draws: trace_points asked for all 5 * samples attempts of every
     redistributed visit (out_pixel + out_xy), before any selection.
 (d) plan_visits with device pointers and totals, in GB/s of column traffic: five 16-byte columns read, 32 bytes written.
+(e) The same frame with abb_chromatic = 0.5: list_draws with LENTIL_DRAWS_CHANNELS (three traces per attempt, the list
+    sized by a counting call) beside the chunked pass's draw of that mode and beside (a).
 Every figure: one warm-up call, then the median of --repeats calls.
 
     python3 tools/list_draws_timing.py [--repeats 6] [--out profiles/list_draws.txt]
@@ -179,6 +181,30 @@ def main():
     say("(c) trace_points, all %d attempts of the %d redistributed visits, out_pixel + out_xy, before any selection: %.2f ms (median; min %.2f "
         "max %.2f, %d calls), %d tries -> %.3f ns per try made, %.3f ns per try the list needs; over list_draws: x %.2f in time"
         % ((5 * S, flagged.size) + tp_ms + (a.repeats, all_tries, tp_ms[0] * 1e6 / all_tries, tp_ms[0] * 1e6 / ref_tries, tp_ms[0] / list_ms[0])))
+    del t_cs, t_px, t_made, made_all, count, last
+
+    # (e) the same frame with abb_chromatic = 0.5: three channels per attempt (LENTIL_DRAWS_CHANNELS), beside the chunked
+    # pass's draw of that mode and beside the plain list above
+    pc = type(p).from_buffer_copy(p)
+    pc.abb_chromatic = 0.5
+    ctx.set_params(pc)
+    cdraw_ms = []
+    for k in range(a.repeats + 1):
+        ctx.clear_frame(); ctx.redistribute(); ctx.sync()
+        cc = ctx.counters()
+        assert cc.worklist_overflow == 0 and cc.streamed == 0
+        if k:
+            cdraw_ms.append(float(ctx.last_timing()[1]))
+    none, c_records, c_attempts = ctx.list_draws(capacity=0, channels=True)          # the counting call sizes the list
+    assert c_records == cc.accepted_draws and c_attempts == cc.attempted_draws, (c_records, c_attempts, cc.accepted_draws, cc.attempted_draws)
+    assert c_records <= 11 * totals[2]
+    clist_ms = timed(lambda: ctx.list_draws(capacity=c_records, device=True, channels=True))
+    say("(e) abb_chromatic 0.5: chunked pass draw %.2f ms (median; min %.2f max %.2f, %d passes); list_draws with LENTIL_DRAWS_CHANNELS (path %d), "
+        "device pointers, capacity %d: %.2f ms (median; min %.2f max %.2f, %d calls), %d records, %d attempts -> x %.2f the pass's draw, "
+        "x %.2f the plain list; %.3f ns per record against the plain list's %.3f"
+        % ((float(np.median(cdraw_ms)), min(cdraw_ms), max(cdraw_ms), len(cdraw_ms), ctx.list_draws_path(), c_records) + clist_ms
+           + (a.repeats, c_records, c_attempts, clist_ms[0] / float(np.median(cdraw_ms)), clist_ms[0] / list_ms[0],
+              clist_ms[0] * 1e6 / c_records, list_ms[0] * 1e6 / n_draws)))
     ctx.close()
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
