@@ -200,17 +200,7 @@ __global__ __launch_bounds__(kRayBlock) void camera_rays_kernel(CameraRayArgs a)
   __shared__ DevTerm s_terms[kTables ? kMaxTerms : 1];
   __shared__ DevLens s_k;
   __shared__ float s_io[kRayBlock * kRayOutFloats];
-  if (PO) {
-    if (kTables) {
-      const uint32_t nt = a.lens->n_terms;
-      for (uint32_t i = threadIdx.x; i < nt; i += kRayBlock) s_terms[i] = a.terms[i];
-    }
-    if (threadIdx.x == 0) {
-      s_k = *a.lens;
-      s_k.lambda_pow[0] = 1.0; s_k.lambda_pow[1] = a.lambda;
-      for (uint32_t e = 2; e <= kMaxExp; ++e) s_k.lambda_pow[e] = ipow_u(a.lambda, e);     // lens_ipow, like the host
-    }
-  }
+  if (PO) stage_lens<kTables>(a.lens, a.terms, a.lambda, kRayBlock, s_terms, &s_k, threadIdx.x == 0);      // (the barrier is the input's, below)
   const uint64_t ray0 = (uint64_t)blockIdx.x * kRayBlock;
   const uint32_t nb = (uint32_t)((a.n - ray0) < (uint64_t)kRayBlock ? (a.n - ray0) : (uint64_t)kRayBlock);   // >= 1: the grid is ceil(n / 256)
   for (uint32_t j = threadIdx.x; j < nb * kRayInFloats; j += kRayBlock) s_io[j] = a.in[ray0 * kRayInFloats + j];

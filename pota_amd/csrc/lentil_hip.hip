@@ -4109,6 +4109,29 @@ LENTIL_API int lentil_hip_camera_rays_path(lentil_hip_ctx *ctx, int *path) {
   return LENTIL_OK;
 }
 
+// ---- the lens path of the trace and list kernels -------------------------------------------------------------------------
+// f is called once, with a LensPath that names the kernel's template arguments: the compiled-in lens of the bound table, else
+// the table interpreter, else (po false) the thin lens.  -> the path as the *_path queries report it: 0 thin lens,
+// 1 interpreter, 2 compiled-in.  An f that does nothing leaves the path alone.
+template <class LensT_, bool kTables_, bool PO_>
+struct LensPath {
+  using LensT = LensT_;
+  static constexpr bool kTables = kTables_, PO = PO_;
+};
+
+template <class F>
+static int lens_dispatch(const lentil_hip_ctx *ctx, bool po, F &&f) {
+  if (!po) { f(LensPath<LdsLens, false, false>{}); return 0; }
+  if (ctx->use_generated) {
+#define LENTIL_DISPATCH_GEN(NAME) \
+    if (ctx->lens_hash == gen::Lens_##NAME::kTableHash) { f(LensPath<GenLens<gen::Lens_##NAME>, false, true>{}); return 2; }
+    LENTIL_GENERATED_LENSES(LENTIL_DISPATCH_GEN)
+#undef LENTIL_DISPATCH_GEN
+  }
+  f(LensPath<LdsLens, true, true>{});
+  return 1;
+}
+
 // ---- scene points traced backward in batches (lentil_trace_points.h) ----------------------------------------------------
 LENTIL_API int lentil_hip_trace_points(lentil_hip_ctx *ctx, const lentil_point_batch *batch) {
   CHECK_CTX(ctx);
@@ -4161,23 +4184,10 @@ LENTIL_API int lentil_hip_trace_points(lentil_hip_ctx *ctx, const lentil_point_b
   // a slab per wave, four waves per block; no more blocks than the device holds at once (eight waves per SIMD at the most)
   const uint64_t want = ((uint64_t)a.n_slabs + kTpBlock / 64 - 1) / (kTpBlock / 64), cap = (uint64_t)ctx->num_cu * 8u;
   const dim3 grid((unsigned)(want < cap ? want : cap));
-  int path = 0;
-  if (po) {
-#define LENTIL_LAUNCH_GEN(NAME)                                                                              \
-    if (!path && ctx->use_generated && ctx->lens_hash == gen::Lens_##NAME::kTableHash) {                      \
-      hipLaunchKernelGGL((trace_points_kernel<GenLens<gen::Lens_##NAME>, false, true>), grid, dim3(kTpBlock), 0, ctx->stream, a); \
-      path = 2;                                                                                              \
-    }
-    LENTIL_GENERATED_LENSES(LENTIL_LAUNCH_GEN)
-#undef LENTIL_LAUNCH_GEN
-    if (!path) {
-      hipLaunchKernelGGL((trace_points_kernel<LdsLens, true, true>), grid, dim3(kTpBlock), 0, ctx->stream, a);
-      path = 1;
-    }
-  } else {
-    hipLaunchKernelGGL((trace_points_kernel<LdsLens, false, false>), grid, dim3(kTpBlock), 0, ctx->stream, a);
-  }
-  ctx->points_path = path;
+  ctx->points_path = lens_dispatch(ctx, po, [&](auto lp) {
+    using T = decltype(lp);
+    hipLaunchKernelGGL((trace_points_kernel<typename T::LensT, T::kTables, T::PO>), grid, dim3(kTpBlock), 0, ctx->stream, a);
+  });
   HIP_TRY(ctx, hipGetLastError());
   if (device) return LENTIL_OK;
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -4242,23 +4252,10 @@ LENTIL_API int lentil_hip_plan_visits(lentil_hip_ctx *ctx, uint64_t first_visit,
 
 // One turn's walk of a probed list, on the lens path the unprobed list takes.
 static int list_probed_launch(lentil_hip_ctx *ctx, dim3 grid, bool po, const ListDrawArgs &a, const ProbeArgs &pr, const ListProbeArgs &b) {
-  int path = 0;
-  if (po) {
-#define LENTIL_LAUNCH_GEN(NAME)                                                                              \
-    if (!path && ctx->use_generated && ctx->lens_hash == gen::Lens_##NAME::kTableHash) {                      \
-      hipLaunchKernelGGL((list_draws_probed_kernel<GenLens<gen::Lens_##NAME>, false, true>), grid, dim3(kLdBlock), 0, ctx->stream, a, pr, b); \
-      path = 2;                                                                                              \
-    }
-    LENTIL_GENERATED_LENSES(LENTIL_LAUNCH_GEN)
-#undef LENTIL_LAUNCH_GEN
-    if (!path) {
-      hipLaunchKernelGGL((list_draws_probed_kernel<LdsLens, true, true>), grid, dim3(kLdBlock), 0, ctx->stream, a, pr, b);
-      path = 1;
-    }
-  } else {
-    hipLaunchKernelGGL((list_draws_probed_kernel<LdsLens, false, false>), grid, dim3(kLdBlock), 0, ctx->stream, a, pr, b);
-  }
-  ctx->draws_path = path;
+  ctx->draws_path = lens_dispatch(ctx, po, [&](auto lp) {
+    using T = decltype(lp);
+    hipLaunchKernelGGL((list_draws_probed_kernel<typename T::LensT, T::kTables, T::PO>), grid, dim3(kLdBlock), 0, ctx->stream, a, pr, b);
+  });
   HIP_TRY(ctx, hipGetLastError());
   return LENTIL_OK;
 }
@@ -4291,12 +4288,7 @@ static int list_draws_probed(lentil_hip_ctx *ctx, ListDrawArgs &a, dim3 grid, bo
   const uint64_t words = sized[0], most_seeds = sized[1];
   h[0] = h[1] = h[2] = 0;
   if (!words) {       // no visit of the range is redistributed: nothing is drawn, nobody is asked
-    ctx->draws_path = !po ? 0 : 1;
-    if (po && ctx->use_generated) {
-#define LENTIL_PATH_GEN(NAME) if (ctx->lens_hash == gen::Lens_##NAME::kTableHash) ctx->draws_path = 2;
-      LENTIL_GENERATED_LENSES(LENTIL_PATH_GEN)
-#undef LENTIL_PATH_GEN
-    }
+    ctx->draws_path = lens_dispatch(ctx, po, [](auto) {});      // (the path a walk would have taken)
     return LENTIL_OK;
   }
   // the store: two arrays of `words` 32-bit words; a seed's place in it is a 32-bit bit index
@@ -4424,53 +4416,31 @@ LENTIL_API int lentil_hip_list_draws(lentil_hip_ctx *ctx, const lentil_draw_list
   const uint64_t tickets = (list->n_visits + 63) / 64;
   const uint64_t want = (tickets + kLdBlock / 64 - 1) / (kLdBlock / 64), cap = (uint64_t)ctx->num_cu * 8u;
   const dim3 grid((unsigned)(want < cap ? want : cap));
-  int path = 0;
+  unsigned long long h[3] = {0, 0, 0};       // ListDrawArgs::ctr [0..2] when the list is complete
   if (probed) {
-    unsigned long long h[3] = {0, 0, 0};
     if ((rc = list_draws_probed(ctx, a, grid, po, tf, h))) return rc;
-    *list->n_draws = h[1];
-    if (list->attempts) *list->attempts = h[2];
-    const uint64_t written = h[1] < list->capacity ? h[1] : list->capacity;
-    if (!device && written) HIP_TRY(ctx, hipMemcpy(list->out, d_out, (size_t)written * sizeof(lentil_draw), hipMemcpyDeviceToHost));
-    return LENTIL_OK;
-  }
-  if (chroma) {
-    // the wavelengths are the pass's own (draw_channels_of); abb_chromatic < 0: the caller's lambda for all three, one trace
-    ListChromaArgs ch{};
-    draw_channels_of(ctx->P, ch.lambda, nullptr);
-    ch.n_traces = ctx->P.abb_chromatic > 0.0f ? 3u : 1u;
-    if (ch.n_traces == 1u) ch.lambda[0] = ch.lambda[1] = ch.lambda[2] = a.lambda;
-#define LENTIL_LAUNCH_GEN(NAME)                                                                              \
-    if (!path && ctx->use_generated && ctx->lens_hash == gen::Lens_##NAME::kTableHash) {                      \
-      hipLaunchKernelGGL((list_draws_chroma_kernel<GenLens<gen::Lens_##NAME>, false>), grid, dim3(kLdBlock), 0, ctx->stream, a, ch); \
-      path = 2;                                                                                              \
-    }
-    LENTIL_GENERATED_LENSES(LENTIL_LAUNCH_GEN)
-#undef LENTIL_LAUNCH_GEN
-    if (!path) {
-      hipLaunchKernelGGL((list_draws_chroma_kernel<LdsLens, true>), grid, dim3(kLdBlock), 0, ctx->stream, a, ch);
-      path = 1;
-    }
-  } else if (po) {
-#define LENTIL_LAUNCH_GEN(NAME)                                                                              \
-    if (!path && ctx->use_generated && ctx->lens_hash == gen::Lens_##NAME::kTableHash) {                      \
-      hipLaunchKernelGGL((list_draws_kernel<GenLens<gen::Lens_##NAME>, false, true>), grid, dim3(kLdBlock), 0, ctx->stream, a); \
-      path = 2;                                                                                              \
-    }
-    LENTIL_GENERATED_LENSES(LENTIL_LAUNCH_GEN)
-#undef LENTIL_LAUNCH_GEN
-    if (!path) {
-      hipLaunchKernelGGL((list_draws_kernel<LdsLens, true, true>), grid, dim3(kLdBlock), 0, ctx->stream, a);
-      path = 1;
-    }
   } else {
-    hipLaunchKernelGGL((list_draws_kernel<LdsLens, false, false>), grid, dim3(kLdBlock), 0, ctx->stream, a);
+    if (chroma) {
+      // the wavelengths are the pass's own (draw_channels_of); abb_chromatic < 0: the caller's lambda for all three, one trace
+      ListChromaArgs ch{};
+      draw_channels_of(ctx->P, ch.lambda, nullptr);
+      ch.n_traces = ctx->P.abb_chromatic > 0.0f ? 3u : 1u;
+      if (ch.n_traces == 1u) ch.lambda[0] = ch.lambda[1] = ch.lambda[2] = a.lambda;
+      ctx->draws_path = lens_dispatch(ctx, po, [&](auto lp) {
+        using T = decltype(lp);
+        if constexpr (T::PO)       // (chroma implies polynomial optics: the thin lens has no such kernel)
+          hipLaunchKernelGGL((list_draws_chroma_kernel<typename T::LensT, T::kTables>), grid, dim3(kLdBlock), 0, ctx->stream, a, ch);
+      });
+    } else {
+      ctx->draws_path = lens_dispatch(ctx, po, [&](auto lp) {
+        using T = decltype(lp);
+        hipLaunchKernelGGL((list_draws_kernel<typename T::LensT, T::kTables, T::PO>), grid, dim3(kLdBlock), 0, ctx->stream, a);
+      });
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpy(h, a.ctr, sizeof h, hipMemcpyDeviceToHost));
   }
-  ctx->draws_path = path;
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  unsigned long long h[3] = {0, 0, 0};
-  HIP_TRY(ctx, hipMemcpy(h, a.ctr, sizeof h, hipMemcpyDeviceToHost));
   *list->n_draws = h[1];
   if (list->attempts) *list->attempts = h[2];
   const uint64_t written = h[1] < list->capacity ? h[1] : list->capacity;

@@ -4929,20 +4929,28 @@ struct FocusArgs {
   double *best;            // [2]: winning shift, its miss (focus_argmin_kernel)
 };
 
+// A lens staged into LDS for one wavelength, by the whole block (`threads` of them): the term table where the lens reads one
+// (kTables), and -- by the one thread that is `owner` -- the header into `slot` with its lambda powers for `lambda`.  No
+// barrier: the caller's own __syncthreads() stands between this and the first use.
+template <bool kTables>
+LD_DEV void stage_lens(const DevLens *lens, const DevTerm *terms, double lambda, uint32_t threads, DevTerm *s_terms, DevLens *slot, bool owner) {
+  if (kTables) {
+    const uint32_t nt = lens->n_terms;
+    for (uint32_t i = threadIdx.x; i < nt; i += threads) s_terms[i] = terms[i];
+  }
+  if (owner) {
+    *slot = *lens;
+    slot->lambda_pow[0] = 1.0; slot->lambda_pow[1] = lambda;
+    for (uint32_t e = 2; e <= kMaxExp; ++e) slot->lambda_pow[e] = ipow_u(lambda, e);     // lens_ipow, like the host
+  }
+}
+
 // LensT: LdsLens (kTables: the term table staged into LDS) or GenLens<Gen> of a compiled-in lens (the header alone)
 template <class LensT, bool kTables>
 __global__ __launch_bounds__(256) void focus_miss_kernel(FocusArgs f) {
   __shared__ DevTerm s_terms[kTables ? kMaxTerms : 1];
   __shared__ DevLens s_k;
-  if (kTables) {
-    const uint32_t nt = f.lens->n_terms;
-    for (uint32_t i = threadIdx.x; i < nt; i += blockDim.x) s_terms[i] = f.terms[i];
-  }
-  if (threadIdx.x == 0) {
-    s_k = *f.lens;
-    s_k.lambda_pow[0] = 1.0; s_k.lambda_pow[1] = f.lambda;
-    for (uint32_t e = 2; e <= kMaxExp; ++e) s_k.lambda_pow[e] = ipow_u(f.lambda, e);     // lens_ipow, like the host
-  }
+  stage_lens<kTables>(f.lens, f.terms, f.lambda, blockDim.x, s_terms, &s_k, threadIdx.x == 0);
   __syncthreads();
   LensT L{};
   if constexpr (kTables) L.terms = s_terms;

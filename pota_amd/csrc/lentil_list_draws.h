@@ -14,19 +14,22 @@
 // list_draws_kernel.  A wave takes 64 consecutive visits on a dynamic ticket (one atomic per 64 visits), runs the prologue
 // with lane = visit, ballots the redistribute decisions and then serves the set lanes one after another: the visit's position,
 // pixel and draw count are handed to the whole wave through readlane (scalar registers), and the wave walks the visit's
-// attempts 64 at a time with lane = attempt.  A slab is traced with trace_points_kernel's loops, operation for operation (the
-// wave-uniform vignetting-retry loop, the per-lane Newton loop; the same device functions), its successes are balloted, and a
+// attempts 64 at a time with lane = attempt.  A slab is traced by trace_attempt (lentil_trace_points.h: the one backward trace
+// of an attempt, which trace_points_kernel and the three list kernels of this file call), its successes are balloted, and a
 // success is taken while accepted_so_far + popcount(ballot & lower lanes) < samples -- the attempts the reference's loop
 // would have accepted before it stopped.  The slab's records take consecutive slots of the list through one atomic
 // (probe_wave_slot's pattern on a 64-bit counter) and are written where the slot lies below the capacity; the counter runs on,
 // so the caller learns how many there are.  The attempts a visit made -- up to its last accepted draw if that was the
-// `samples`-th, else all 5 * samples -- are summed per wave: one atomic per 64 visits.
+// `samples`-th, else all 5 * samples -- are summed per wave and go out once, behind the ticket loop: one atomic per wave.
 // Every loop is bounded: ceil(n_visits / 64) tickets, at most 64 visits per ticket, at most ceil(5 * samples / 64) slabs per
 // visit, at most vignetting_retries + 1 tries, at most 100 Newton iterations (newton_continue).
 // What a record holds depends on its (visit, attempt) alone, so the list as a set does not depend on the grid, on the
 // capacity or on how the stream is split into ranges; the order of the records does.
+//
+// The walk over the visits -- ticket, prologue, broadcast, slab step, the attempts made, the record store -- is the ld_*
+// helpers below, shared by the three list kernels (the prologue also by plan_visits_kernel and ld_probe_alloc_kernel).
 #pragma once
-#include "lentil_kernels.h"
+#include "lentil_trace_points.h"
 
 constexpr int kLdBlock = 256;
 constexpr uint32_t kLdSlab = 64;    // attempts per slab = visits per ticket = lanes per wave
@@ -46,6 +49,25 @@ LD_DEV float plan_weight(float invd, bool redistribute, int samples) {
   return 1.0f * invd * inv_samples;                                       // src/lentil_filter.cpp:297
 }
 
+// A lane's visit: its columns through the pass's prologue (load_work_visit's line) and its pixel.  All zero, `redistribute`
+// false, on a lane without a visit.
+struct LdVisitLane {
+  VisitInfo I;
+  int px, py;
+  float invd;
+  float4 pos_z, raydir_time;
+};
+
+LD_DEV LdVisitLane ld_visit_lane(const lentil_params &P, const VisitsDev &V, double lens_length, uint64_t v) {
+  LdVisitLane x;
+  x.invd = V.inv_density ? V.inv_density[v] : P.inverse_sample_density;
+  x.pos_z = V.pos_z[v];
+  x.raydir_time = V.raydir_time[v];
+  x.I = visit_prologue(P, lens_length, V.rgba[v], x.pos_z, x.raydir_time, V.volume_ignore[v], V.transmission[v], x.invd, V.cam);
+  visit_pixel(V, v, x.px, x.py);
+  return x;
+}
+
 __global__ __launch_bounds__(kLdBlock) void plan_visits_kernel(PlanArgs a) {
   const VisitsDev &V = a.V;
   const uint32_t lane = threadIdx.x & 63u;
@@ -58,18 +80,15 @@ __global__ __launch_bounds__(kLdBlock) void plan_visits_kernel(PlanArgs a) {
     const bool valid = v < a.v_end;
     bool red = false;
     if (valid) {
-      const float invd = V.inv_density ? V.inv_density[v] : a.P.inverse_sample_density;
-      const VisitInfo I = visit_prologue(a.P, a.lens_length, V.rgba[v], V.pos_z[v], V.raydir_time[v], V.volume_ignore[v],
-                                         V.transmission[v], invd, V.cam);
-      int px, py;
-      visit_pixel(V, v, px, py);
+      const LdVisitLane x = ld_visit_lane(a.P, V, a.lens_length, v);
+      const VisitInfo &I = x.I;
       red = I.redistribute;
       lentil_visit_plan r;
       r.cs[0] = I.cs[0]; r.cs[1] = I.cs[1]; r.cs[2] = I.cs[2];
       r.add_energy = red ? I.add_energy : 0.0f;
-      r.weight = plan_weight(invd, red, I.samples);
+      r.weight = plan_weight(x.invd, red, I.samples);
       r.samples = (uint32_t)I.samples;
-      r.pixel = (uint32_t)((px & 0xFFFF) | (py << 16));
+      r.pixel = (uint32_t)((x.px & 0xFFFF) | (x.py << 16));
       r.flags = red ? LENTIL_PLAN_REDISTRIBUTE : 0u;
       a.out[v - a.v_begin] = r;
       if (red) sum_samples += (unsigned long long)(uint32_t)I.samples;
@@ -119,135 +138,111 @@ LD_DEV unsigned long long list_wave_slot(unsigned long long *count, unsigned lon
 
 // LensT / kTables / PO: as trace_points_kernel (LdsLens with the term table staged into LDS, the interpreter -- also the thin
 // lens's, which has no lens: PO false -- or GenLens<Gen> of a compiled-in lens).
+// ---- the visit walk of the list kernels ------------------------------------------------------------------------------------
+// A wave's next group of 64 visits, on a dynamic ticket: one atomic per group, handed to the wave through readlane; the
+// ticket loop ends at the first ticket that is no group.  Its body must not end in a branch on the lane: with
+// `if (lane == 0u)` twice in a row -- a wave sum's atomic at the body's end, then this one -- the compiler once sent lanes
+// 1 ... 63 straight back to the readlane here, past lane 0 and its atomic (jump threading over the two equal conditions): they
+// read ticket 0 again and never left.  So a wave's sums go out once, behind the ticket loop (ld_add_wave_sum).
+LD_DEV unsigned long long ld_take_ticket(unsigned long long *ticket, uint32_t lane) {
+  unsigned long long g = 0;
+  if (lane == 0u) g = atomicAdd(ticket, 1ull);
+  return ld_readlane(g, 0);
+}
+
+LD_DEV void ld_add_wave_sum(unsigned long long *total, unsigned long long sum, uint32_t lane) {
+  if (lane == 0u && sum) atomicAdd(total, sum);
+}
+
+// The visit of lane `src`, handed to the whole wave through readlane: scalar registers.
+struct LdWaveVisit {
+  float cs[3];
+  int px, py;
+  uint32_t samples;
+  uint32_t max_total;               // 5 * samples, unsigned, as the reference's max_total_samples
+  uint32_t visit;                   // its number in the stream; visit0: that of the group's lane 0
+};
+
+LD_DEV LdWaveVisit ld_broadcast_visit(const LdVisitLane &x, int src, uint32_t visit0) {
+  LdWaveVisit w;
+  w.cs[0] = ld_readlane(x.I.cs[0], src); w.cs[1] = ld_readlane(x.I.cs[1], src); w.cs[2] = ld_readlane(x.I.cs[2], src);
+  w.px = (int)ld_readlane((uint32_t)x.px, src); w.py = (int)ld_readlane((uint32_t)x.py, src);
+  w.samples = ld_readlane((uint32_t)x.I.samples, src);
+  w.max_total = w.samples * 5u;
+  w.visit = visit0 + (uint32_t)src;
+  return w;
+}
+
+// the slab behind the one at k0 < max_total, without the sum's wrap; lane = attempt commits while max_total - k0 > lane
+LD_DEV uint32_t ld_next_slab(uint32_t k0, uint32_t max_total) { return (max_total - k0 > kLdSlab) ? k0 + kLdSlab : max_total; }
+
+// The attempts a visit has made behind the slab at k0: its loop ends behind the attempt that brought its count to `samples`
+// (`reached`, on lane last_lane); a slab without it was attempted to its end.
+LD_DEV uint32_t ld_made(uint32_t k0, uint32_t max_total, bool reached, uint32_t last_lane) {
+  return reached ? k0 + last_lane + 1u : ld_next_slab(k0, max_total);
+}
+
+// a record at its slot, where the slot lies below the capacity (the counter runs on)
+LD_DEV void ld_store_draw(const ListDrawArgs &a, unsigned long long slot, uint32_t visit, uint32_t attempt, uint32_t code, int tries,
+                          double xy0, double xy1) {
+  if (slot < a.capacity) {
+    lentil_draw r;
+    r.visit = visit; r.attempt = attempt; r.pixel = code; r.tries = tries;
+    r.xy[0] = xy0; r.xy[1] = xy1;
+    a.out[slot] = r;
+  }
+}
+
 template <class LensT, bool kTables, bool PO>
 __global__ __launch_bounds__(kLdBlock) void list_draws_kernel(ListDrawArgs a) {
   __shared__ DevTerm s_terms[kTables ? kMaxTerms : 1];
   __shared__ DevLens s_k;
   if (PO) {
-    if (kTables) {
-      const uint32_t nt = a.lens->n_terms;
-      for (uint32_t i = threadIdx.x; i < nt; i += kLdBlock) s_terms[i] = a.terms[i];
-    }
-    if (threadIdx.x == 0) {
-      s_k = *a.lens;
-      s_k.lambda_pow[0] = 1.0; s_k.lambda_pow[1] = a.lambda;
-      for (uint32_t e = 2; e <= kMaxExp; ++e) s_k.lambda_pow[e] = ipow_u(a.lambda, e);     // lens_ipow, like the host
-    }
+    stage_lens<kTables>(a.lens, a.terms, a.lambda, kLdBlock, s_terms, &s_k, threadIdx.x == 0);
     __syncthreads();
   }
   LensT L{};
   if constexpr (kTables) L.terms = s_terms;
   L.k = &s_k;
-  const lentil_params &P = a.P;
-  const VisitsDev &V = a.V;
   const uint32_t lane = threadIdx.x & 63u;
   const unsigned long long below = (1ull << lane) - 1ull;
   const unsigned long long n_groups = (a.v_end - a.v_begin + 63u) / 64u;
-  const double qnan = __builtin_nan("");
+  unsigned long long wave_attempts = 0;
   for (;;) {
-    unsigned long long g = 0;
-    if (lane == 0u) g = atomicAdd(&a.ctr[0], 1ull);
-    g = ld_readlane(g, 0);
+    const unsigned long long g = ld_take_ticket(&a.ctr[0], lane);
     if (g >= n_groups) break;
     // ---- the prologue, lane = visit
     const uint64_t v = a.v_begin + g * 64u + lane;
-    VisitInfo I{};
-    int vpx = 0, vpy = 0;
-    if (v < a.v_end) {
-      const float invd = V.inv_density ? V.inv_density[v] : P.inverse_sample_density;
-      I = visit_prologue(P, a.lens_length, V.rgba[v], V.pos_z[v], V.raydir_time[v], V.volume_ignore[v], V.transmission[v], invd, V.cam);
-      visit_pixel(V, v, vpx, vpy);
-    } else {
-      I.redistribute = false;
-    }
-    unsigned long long todo = __ballot(I.redistribute);
-    unsigned long long wave_attempts = 0;
+    LdVisitLane x{};
+    if (v < a.v_end) x = ld_visit_lane(a.P, a.V, a.lens_length, v);
+    unsigned long long todo = __ballot(x.I.redistribute);
     // ---- the set lanes one after another, lane = attempt
     while (todo) {
       const int src = __builtin_ctzll(todo);
       todo &= todo - 1ull;
-      const float cs[3] = {ld_readlane(I.cs[0], src), ld_readlane(I.cs[1], src), ld_readlane(I.cs[2], src)};
-      const int px = (int)ld_readlane((uint32_t)vpx, src), py = (int)ld_readlane((uint32_t)vpy, src);
-      const uint32_t samples = ld_readlane((uint32_t)I.samples, src);
-      const uint32_t visit = (uint32_t)(a.v_begin + g * 64u) + (uint32_t)src;
-      const uint32_t max_total = samples * 5u;                           // unsigned, as the reference's max_total_samples
+      const LdWaveVisit w = ld_broadcast_visit(x, src, (uint32_t)(a.v_begin + g * 64u));
       uint32_t accepted = 0, made = 0;
-      for (uint32_t k0 = 0; k0 < max_total && accepted < samples; k0 = (max_total - k0 > kLdSlab) ? k0 + kLdSlab : max_total) {
+      for (uint32_t k0 = 0; k0 < w.max_total && accepted < w.samples; k0 = ld_next_slab(k0, w.max_total)) {
         const uint32_t attempt = k0 + lane;
-        const bool commit = max_total - k0 > lane;                      // attempt < max_total, without the sum's wrap
-
-        uint32_t code = LENTIL_POINT_VIGNETTED;
-        double xy0 = qnan, xy1 = qnan;
-        int tries = 0;
-        if (PO) {
-          const DevLens &k = L.consts();
-          const double target[3] = {-(double)cs[0] * 10.0, -(double)cs[1] * 10.0, -(double)cs[2] * 10.0};   // src/lentil_filter.cpp:271
-          bool ok = false;
-          bool trying = commit && tries <= P.vignetting_retries;
-          double sensor[4] = {0.0, 0.0, 0.0, 0.0};
-          while (__any(trying)) {
-            double ax, ay;
-            po_aperture_sample(P, a.bokeh, a.bokeh.cdfRow, (uint32_t)(px * py + px), attempt + (uint32_t)tries, ax, ay);
-            NewtonState s;
-            newton_init(s);
-            while (trying && newton_continue(s)) newton_iter(L, target, ax, ay, s);
-            double out4;
-            const float transmittance = (float)newton_finish(L, s, out4);
-            bool pass = !(transmittance <= 0);
-            const double ipx = s.x + s.dx * k.back_focal_length;
-            const double ipy = s.y + s.dy * k.back_focal_length;
-            if (ipx * ipx + ipy * ipy > k.inner_pupil_radius * k.inner_pupil_radius) pass = false;
-            if (trying) {
-              if (pass) {
-                sensor[0] = s.x; sensor[1] = s.y; sensor[2] = s.dx; sensor[3] = s.dy;
-                ok = true; trying = false;
-              } else {
-                ++tries; trying = tries <= P.vignetting_retries;
-              }
-            }
-          }
-          if (ok) {
-            const double sen0 = sensor[0] + sensor[2] * -P.sensor_shift;
-            const double sen1 = sensor[1] + sensor[3] * -P.sensor_shift;
-            uint32_t pn = 0;
-            code = po_sensor_to_pixel_xy(P, sen0, sen1, pn, xy0, xy1) ? pn : LENTIL_POINT_OUTSIDE;
-          }
-        } else if (commit) {
-          TlRay ray;
-          if (thinlens_ray(P, a.bokeh, a.bokeh.cdfRow, cs, px, py, attempt, ray)) {
-            const float image_dist_focusdist =
-                (float)(((double)-P.focal_length * -P.focus_distance) / ((double)-P.focal_length + -P.focus_distance));
-            uint32_t pn = 0;
-            float fx, fy;
-            code = thinlens_project_xy(P, ray, image_dist_focusdist, pn, fx, fy) ? pn : LENTIL_POINT_OUTSIDE;
-            xy0 = (double)fx; xy1 = (double)fy;
-          }
-        }
+        const bool commit = w.max_total - k0 > lane;
+        const AttemptTrace t = trace_attempt<PO>(a.P, L, a.bokeh, w.cs, w.px, w.py, attempt, commit, NoSeedAnswers{});
 
         // ---- the reference's selection: the successes in attempt order, until `samples` of them are in
-        const bool success = commit && code < LENTIL_POINT_OUTSIDE;
+        const bool success = commit && t.code < LENTIL_POINT_OUTSIDE;
         const unsigned long long okm = __ballot(success);
-        const bool take = success && accepted + (uint32_t)__builtin_popcountll(okm & below) < samples;
+        const bool take = success && accepted + (uint32_t)__builtin_popcountll(okm & below) < w.samples;
         const unsigned long long tm = __ballot(take);
-        const uint32_t nt = (uint32_t)__builtin_popcountll(tm);
         if (tm) {
           const unsigned long long slot = list_wave_slot(&a.ctr[1], tm, lane);
-          if (take && slot < a.capacity) {
-            lentil_draw r;
-            r.visit = visit; r.attempt = attempt; r.pixel = code; r.tries = tries;
-            r.xy[0] = xy0; r.xy[1] = xy1;
-            a.out[slot] = r;
-          }
+          if (take) ld_store_draw(a, slot, w.visit, attempt, t.code, t.tries, t.xy0, t.xy1);
         }
-        accepted += nt;
-        // (the loop ends behind its `samples`-th accepted draw; a slab without it was attempted to its end)
-        if (accepted >= samples) made = k0 + (uint32_t)(63 - __builtin_clzll(tm)) + 1u;
-        else made = (max_total - k0 > kLdSlab) ? k0 + kLdSlab : max_total;
+        accepted += (uint32_t)__builtin_popcountll(tm);
+        made = ld_made(k0, w.max_total, accepted >= w.samples, (uint32_t)(63 - __builtin_clzll(tm | 1ull)));   // (| 1: defined for an empty mask, whose lane nobody asks for)
       }
       wave_attempts += made;
     }
-    if (lane == 0u && wave_attempts) atomicAdd(&a.ctr[2], wave_attempts);
   }
+  ld_add_wave_sum(&a.ctr[2], wave_attempts, lane);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -259,8 +254,8 @@ __global__ __launch_bounds__(kLdBlock) void list_draws_kernel(ListDrawArgs a) {
 // ld_probe_alloc_kernel hands every visit of the range its word offset (a wave scan and one atomic per 64 visits) and its
 // LdVisitState; ld_probe_apply_kernel, behind the callback, turns every listed seed's (1, 0) into clear or occluded.
 //
-// list_draws_probed_kernel, one per turn: list_draws_kernel's ticket / readlane / slab structure over the visits that are not
-// settled.  A try at a seed known to be occluded fails without a solve.  A try that gets through the lens at a seed whose
+// list_draws_probed_kernel, one per turn: list_draws_kernel's walk (the ld_* helpers) over the visits that are not settled,
+// trace_attempt with the store's answers (SeedAnswers).  A try at a seed known to be occluded fails without a solve.  A try that gets through the lens at a seed whose
 // answer is not known leaves its lane `dirty`: what the attempt comes to is open.  The reference reaches attempt n only
 // while fewer than `samples` lower attempts were accepted, and an open attempt may yet be accepted (its seed clear) or not --
 // even one whose optimistic trace lands outside the frame, since an occluded seed hands the attempt to the next try, which may
@@ -309,9 +304,7 @@ __global__ __launch_bounds__(kLdBlock) void ld_probe_alloc_kernel(PlanArgs a, Li
     const bool valid = v < a.v_end;
     unsigned long long words = 0;
     if (valid) {
-      const float invd = V.inv_density ? V.inv_density[v] : a.P.inverse_sample_density;
-      const VisitInfo I = visit_prologue(a.P, a.lens_length, V.rgba[v], V.pos_z[v], V.raydir_time[v], V.volume_ignore[v],
-                                         V.transmission[v], invd, V.cam);
+      const VisitInfo I = ld_visit_lane(a.P, V, a.lens_length, v).I;
       if (I.redistribute) {
         const uint32_t seeds = ld_seed_count(a.P, (uint32_t)I.samples);
         words = ((unsigned long long)seeds + 31ull) / 32ull;
@@ -372,40 +365,42 @@ __global__ __launch_bounds__(256) void ld_probe_apply_kernel(ListProbeArgs b, co
 
 // a.ctr: [0] the ticket (reset every turn), [1] accepted draws and [2] attempts made (both run over the turns),
 // [3] the visits this turn left unsettled (reset every turn).  pr: the turn's list (seg, idx, cap, count) and the camera-to-world.
+// The probed list's seed answers (trace_attempt's policy): the visit's words of the answer store.  A visit seen from the
+// skydome is `exempt`: nothing of it is occluded, nothing is asked.  A, whose bits the asking lanes of this very turn set
+// (atomicOr), is read by a relaxed agent-scope atomic load.
+struct SeedAnswers {
+  const uint32_t *A, *B;
+  bool exempt;
+  LD_DEV void look(uint32_t m, bool &occluded, bool &known) const {
+    occluded = false; known = true;
+    if (!exempt) {
+      const uint32_t bit = 1u << (m & 31u);
+      const bool sa = (__hip_atomic_load(&A[m >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit) != 0u;
+      const bool sb = (B[m >> 5] & bit) != 0u;
+      occluded = sb && !sa;
+      known = sb;
+    }
+  }
+};
+
 template <class LensT, bool kTables, bool PO>
 __global__ __launch_bounds__(kLdBlock) void list_draws_probed_kernel(ListDrawArgs a, ProbeArgs pr, ListProbeArgs b) {
   __shared__ DevTerm s_terms[kTables ? kMaxTerms : 1];
   __shared__ DevLens s_k;
   if (PO) {
-    if (kTables) {
-      const uint32_t nt = a.lens->n_terms;
-      for (uint32_t i = threadIdx.x; i < nt; i += kLdBlock) s_terms[i] = a.terms[i];
-    }
-    if (threadIdx.x == 0) {
-      s_k = *a.lens;
-      s_k.lambda_pow[0] = 1.0; s_k.lambda_pow[1] = a.lambda;
-      for (uint32_t e = 2; e <= kMaxExp; ++e) s_k.lambda_pow[e] = ipow_u(a.lambda, e);     // lens_ipow, like the host
-    }
+    stage_lens<kTables>(a.lens, a.terms, a.lambda, kLdBlock, s_terms, &s_k, threadIdx.x == 0);
     __syncthreads();
   }
   LensT L{};
   if constexpr (kTables) L.terms = s_terms;
   L.k = &s_k;
   const lentil_params &P = a.P;
-  const VisitsDev &V = a.V;
   const uint32_t lane = threadIdx.x & 63u;
   const unsigned long long below = (1ull << lane) - 1ull;
   const unsigned long long n_groups = (a.v_end - a.v_begin + 63u) / 64u;
-  const double qnan = __builtin_nan("");
-  // The wave's sums go out once, behind the ticket loop.  Inside it, at its end, a second `if (lane == 0u)` in front of the
-  // ticket's own made the compiler send lanes 1 ... 63 straight back to the ticket's readlane, past lane 0 and its atomic
-  // (jump threading over the two equal conditions): they read ticket 0 again and never left.  The loop's body must not end
-  // in a branch on the lane.
   unsigned long long wave_attempts = 0, wave_open = 0;
   for (;;) {
-    unsigned long long g = 0;
-    if (lane == 0u) g = atomicAdd(&a.ctr[0], 1ull);
-    g = ld_readlane(g, 0);
+    const unsigned long long g = ld_take_ticket(&a.ctr[0], lane);
     if (g >= n_groups) break;
     // ---- the visits of the group that are not settled, lane = visit
     const uint64_t v = a.v_begin + g * 64u + lane;
@@ -414,118 +409,37 @@ __global__ __launch_bounds__(kLdBlock) void list_draws_probed_kernel(ListDrawArg
     if (v < a.v_end) S = b.st[v - a.v_begin];
     const bool open = S.k0 != kLdSettled;
     unsigned long long todo = __ballot(open);      // (a group with nothing open falls through the empty loop below)
-    VisitInfo I{};
-    int vpx = 0, vpy = 0;
-    float wpx = 0.f, wpy = 0.f, wpz = 0.f, wtime = 0.f;
+    LdVisitLane x{};
     uint32_t exempt_u = 0u;
     if (open) {
-      const float invd = V.inv_density ? V.inv_density[v] : P.inverse_sample_density;
-      const float4 pos_z = V.pos_z[v];
-      const float4 raydir_time = V.raydir_time[v];
-      I = visit_prologue(P, a.lens_length, V.rgba[v], pos_z, raydir_time, V.volume_ignore[v], V.transmission[v], invd, V.cam);
-      visit_pixel(V, v, vpx, vpy);
-      wpx = pos_z.x; wpy = pos_z.y; wpz = pos_z.z; wtime = raydir_time.w;
-      exempt_u = probe_from_skydome(pos_z) ? 1u : 0u;
+      x = ld_visit_lane(P, a.V, a.lens_length, v);
+      exempt_u = probe_from_skydome(x.pos_z) ? 1u : 0u;
     }
     // ---- the set lanes one after another, lane = attempt
     while (todo) {
       const int src = __builtin_ctzll(todo);
       todo &= todo - 1ull;
-      const float cs[3] = {ld_readlane(I.cs[0], src), ld_readlane(I.cs[1], src), ld_readlane(I.cs[2], src)};
-      const int px = (int)ld_readlane((uint32_t)vpx, src), py = (int)ld_readlane((uint32_t)vpy, src);
-      const uint32_t samples = ld_readlane((uint32_t)I.samples, src);
+      const LdWaveVisit w = ld_broadcast_visit(x, src, (uint32_t)(a.v_begin + g * 64u));
+      const uint32_t samples = w.samples, max_total = w.max_total;
       const uint32_t off = ld_readlane(S.off, src);
       const uint32_t k_first = ld_readlane(S.k0, src);
-      const bool exempt = ld_readlane(exempt_u, src) != 0u;
-      const float org[3] = {ld_readlane(wpx, src), ld_readlane(wpy, src), ld_readlane(wpz, src)};
-      const float time = ld_readlane(wtime, src);
-      const uint32_t visit = (uint32_t)(a.v_begin + g * 64u) + (uint32_t)src;
-      const uint32_t max_total = samples * 5u;                           // unsigned, as the reference's max_total_samples
-      const uint32_t *A = b.A + off, *B = b.B + off;
+      const float org[3] = {ld_readlane(x.pos_z.x, src), ld_readlane(x.pos_z.y, src), ld_readlane(x.pos_z.z, src)};
+      const float time = ld_readlane(x.raydir_time.w, src);
+      const SeedAnswers seeds{b.A + off, b.B + off, ld_readlane(exempt_u, src) != 0u};
       uint32_t accepted = ld_readlane(S.accepted, src);                  // exact while `clean`
       uint32_t bound = accepted;                                         // what the accepted count can be at most
       uint32_t made = 0, k_resume = k_first;
       bool clean = true;                                                 // every slab so far is final
-      for (uint32_t k0 = k_first; k0 < max_total && bound < samples; k0 = (max_total - k0 > kLdSlab) ? k0 + kLdSlab : max_total) {
+      for (uint32_t k0 = k_first; k0 < max_total && bound < samples; k0 = ld_next_slab(k0, max_total)) {
         const uint32_t attempt = k0 + lane;
-        const bool commit = max_total - k0 > lane;                      // attempt < max_total, without the sum's wrap
-
-        uint32_t code = LENTIL_POINT_VIGNETTED;
-        double xy0 = qnan, xy1 = qnan;
-        int tries = 0;
-        bool dirty = false;
-        uint32_t pend_m = 0;
-        float pend_lx = 0.f, pend_ly = 0.f;
-        if (PO) {
-          const DevLens &k = L.consts();
-          const double target[3] = {-(double)cs[0] * 10.0, -(double)cs[1] * 10.0, -(double)cs[2] * 10.0};   // src/lentil_filter.cpp:271
-          bool ok = false;
-          bool trying = commit && tries <= P.vignetting_retries;
-          double sensor[4] = {0.0, 0.0, 0.0, 0.0};
-          while (__any(trying)) {
-            const uint32_t m = attempt + (uint32_t)tries;
-            bool occluded = false, known = true;
-            if (trying && !exempt) {
-              const uint32_t bit = 1u << (m & 31u);
-              const bool sa = (__hip_atomic_load(&A[m >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit) != 0u;
-              const bool sb = (B[m >> 5] & bit) != 0u;
-              occluded = sb && !sa;
-              known = sb;
-            }
-            const bool solve = trying && !occluded;
-            double ax, ay;
-            po_aperture_sample(P, a.bokeh, a.bokeh.cdfRow, (uint32_t)(px * py + px), m, ax, ay);
-            NewtonState s;
-            newton_init(s);
-            while (solve && newton_continue(s)) newton_iter(L, target, ax, ay, s);
-            double out4;
-            const float transmittance = (float)newton_finish(L, s, out4);
-            bool pass = !(transmittance <= 0);
-            const double ipx = s.x + s.dx * k.back_focal_length;
-            const double ipy = s.y + s.dy * k.back_focal_length;
-            if (ipx * ipx + ipy * ipy > k.inner_pupil_radius * k.inner_pupil_radius) pass = false;
-            if (!solve) pass = false;
-            if (trying) {
-              if (pass) {
-                sensor[0] = s.x; sensor[1] = s.y; sensor[2] = s.dx; sensor[3] = s.dy;
-                ok = true; trying = false;
-                if (!known) { dirty = true; pend_m = m; pend_lx = (float)(-ax * 0.1); pend_ly = (float)(-ay * 0.1); }   // src/lentil.h:614
-              } else {
-                ++tries; trying = tries <= P.vignetting_retries;
-              }
-            }
-          }
-          if (ok) {
-            const double sen0 = sensor[0] + sensor[2] * -P.sensor_shift;
-            const double sen1 = sensor[1] + sensor[3] * -P.sensor_shift;
-            uint32_t pn = 0;
-            code = po_sensor_to_pixel_xy(P, sen0, sen1, pn, xy0, xy1) ? pn : LENTIL_POINT_OUTSIDE;
-          }
-        } else if (commit) {
-          TlRay ray;
-          if (thinlens_ray(P, a.bokeh, a.bokeh.cdfRow, cs, px, py, attempt, ray)) {
-            bool occluded = false, known = true;
-            if (!exempt) {
-              const uint32_t bit = 1u << (attempt & 31u);
-              const bool sa = (__hip_atomic_load(&A[attempt >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit) != 0u;
-              const bool sb = (B[attempt >> 5] & bit) != 0u;
-              occluded = sb && !sa;
-              known = sb;
-            }
-            if (!occluded) {                                              // (an occluded attempt is lost)
-              const float image_dist_focusdist =
-                  (float)(((double)-P.focal_length * -P.focus_distance) / ((double)-P.focal_length + -P.focus_distance));
-              uint32_t pn = 0;
-              float fx, fy;
-              code = thinlens_project_xy(P, ray, image_dist_focusdist, pn, fx, fy) ? pn : LENTIL_POINT_OUTSIDE;
-              xy0 = (double)fx; xy1 = (double)fy;
-              if (!known) { dirty = true; pend_m = attempt; pend_lx = ray.lx; pend_ly = ray.ly; }
-            }
-          }
-        }
+        const bool commit = max_total - k0 > lane;
+        // a pass at a seed whose answer is not known leaves the lane dirty: what the attempt comes to is open
+        const AttemptTrace t = trace_attempt<PO>(P, L, a.bokeh, w.cs, w.px, w.py, attempt, commit, seeds);
+        const bool dirty = t.open;
+        const uint32_t pend_m = attempt + (uint32_t)t.tries;
 
         // ---- who asks: the dirty lanes the reference reaches whatever the open answers are
-        const bool success = commit && !dirty && code < LENTIL_POINT_OUTSIDE;
+        const bool success = commit && !dirty && t.code < LENTIL_POINT_OUTSIDE;
         const unsigned long long okm = __ballot(success);
         const unsigned long long dm = __ballot(dirty);
         const bool ask = dirty && bound + (uint32_t)__builtin_popcountll((okm | dm) & below) < samples;
@@ -542,9 +456,9 @@ __global__ __launch_bounds__(kLdBlock) void list_draws_probed_kernel(ListDrawArg
             if (win) {
               if (slot < pr.cap) {
                 float c2w[4][4];
-                probe_cam_to_world(V.cam, pr, time, c2w);
+                probe_cam_to_world(a.V.cam, pr, time, c2w);
                 float tgt[3];
-                probe_target(P, c2w, pend_lx, pend_ly, 0.0f, tgt);
+                probe_target(P, c2w, t.lx, t.ly, 0.0f, tgt);
                 lentil_probe_segment sg;
                 sg.origin[0] = org[0]; sg.origin[1] = org[1]; sg.origin[2] = org[2];
                 sg.target[0] = tgt[0]; sg.target[1] = tgt[1]; sg.target[2] = tgt[2];
@@ -560,21 +474,14 @@ __global__ __launch_bounds__(kLdBlock) void list_draws_probed_kernel(ListDrawArg
           // ---- the reference's selection, as list_draws_kernel makes it
           const bool take = success && accepted + (uint32_t)__builtin_popcountll(okm & below) < samples;
           const unsigned long long tm = __ballot(take);
-          const uint32_t nt = (uint32_t)__builtin_popcountll(tm);
           if (tm) {
             const unsigned long long slot = list_wave_slot(&a.ctr[1], tm, lane);
-            if (take && slot < a.capacity) {
-              lentil_draw r;
-              r.visit = visit; r.attempt = attempt; r.pixel = code; r.tries = tries;
-              r.xy[0] = xy0; r.xy[1] = xy1;
-              a.out[slot] = r;
-            }
+            if (take) ld_store_draw(a, slot, w.visit, attempt, t.code, t.tries, t.xy0, t.xy1);
           }
-          accepted += nt;
+          accepted += (uint32_t)__builtin_popcountll(tm);
           bound = accepted;
-          if (accepted >= samples) made = k0 + (uint32_t)(63 - __builtin_clzll(tm)) + 1u;
-          else made = (max_total - k0 > kLdSlab) ? k0 + kLdSlab : max_total;
-          k_resume = (max_total - k0 > kLdSlab) ? k0 + kLdSlab : max_total;
+          made = ld_made(k0, max_total, accepted >= samples, (uint32_t)(63 - __builtin_clzll(tm | 1ull)));
+          k_resume = ld_next_slab(k0, max_total);
         } else {
           bound += (uint32_t)__builtin_popcountll(okm | dm);
         }
@@ -587,10 +494,8 @@ __global__ __launch_bounds__(kLdBlock) void list_draws_probed_kernel(ListDrawArg
       }
     }
   }
-  if (lane == 0u) {
-    if (wave_attempts) atomicAdd(&a.ctr[2], wave_attempts);
-    if (wave_open) atomicAdd(&a.ctr[3], wave_open);
-  }
+  ld_add_wave_sum(&a.ctr[2], wave_attempts, lane);
+  ld_add_wave_sum(&a.ctr[3], wave_open, lane);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -602,16 +507,15 @@ __global__ __launch_bounds__(kLdBlock) void list_draws_probed_kernel(ListDrawArg
 // running count before it was below `samples` (accept_item_chroma, lentil_kernels.h, selects the same way over the pass's
 // result pool).  A visit yields up to 11 * samples records: count_final + 2 * attempts.
 //
-// list_draws_chroma_kernel: list_draws_kernel's ticket / prologue / readlane / slab structure.  Per slab every lane traces its
-// attempt once per channel with trace_points_kernel's loops, operation for operation, through one of three DevLens copies in
-// LDS whose lambda_pow are filled as list_draws_kernel fills its one.  With abb_chromatic < 0 the three channels share one
+// list_draws_chroma_kernel: list_draws_kernel's walk (the ld_* helpers).  Per slab every lane traces its attempt once per
+// channel -- trace_attempt, called in the channel loop -- through one of three DevLens copies in LDS, each staged
+// (stage_lens) for its channel's wavelength.  With abb_chromatic < 0 the three channels share one
 // wavelength and the three traces are the same trace: it runs once (a wave-uniform decision) and stands for all three.
 // Selection: delta = successes - 2 on the lanes that commit, a signed inclusive prefix over the wave, running = count + prefix;
 // istar is the first lane whose running count reaches `samples`; the lanes up to istar were executed (all committed lanes if
 // none reaches it).  Their channels' records take consecutive slots through one atomic per slab (list_wave_slot3) and carry
 // the channel in bits 30-31 of `attempt`, as the pass's draw log does.  `count` is carried across slabs as int32.
-// The wave's attempts go out once, behind the ticket loop (the trap recorded at list_draws_probed_kernel: the loop's body must
-// not end in a branch on the lane).  Every loop is bounded as in list_draws_kernel, the channel loop by 3.
+// Every loop is bounded as in list_draws_kernel, the channel loop by 3.
 // ---------------------------------------------------------------------------------------
 struct ListChromaArgs {
   double lambda[3];                 // lentil_hip_draw_channels' wavelengths
@@ -637,58 +541,37 @@ template <class LensT, bool kTables>
 __global__ __launch_bounds__(kLdBlock) void list_draws_chroma_kernel(ListDrawArgs a, ListChromaArgs ch) {
   __shared__ DevTerm s_terms[kTables ? kMaxTerms : 1];
   __shared__ DevLens s_k[3];
-  if (kTables) {
-    const uint32_t nt = a.lens->n_terms;
-    for (uint32_t i = threadIdx.x; i < nt; i += kLdBlock) s_terms[i] = a.terms[i];
-  }
-  if (threadIdx.x < 3u) {
-    DevLens &k = s_k[threadIdx.x];
-    const double lam = ch.lambda[threadIdx.x];
-    k = *a.lens;
-    k.lambda_pow[0] = 1.0; k.lambda_pow[1] = lam;
-    for (uint32_t e = 2; e <= kMaxExp; ++e) k.lambda_pow[e] = ipow_u(lam, e);               // lens_ipow, like the host
+  {
+    const uint32_t c = threadIdx.x < 3u ? threadIdx.x : 0u;       // a slot per channel, filled by threads 0 ... 2
+    stage_lens<kTables>(a.lens, a.terms, ch.lambda[c], kLdBlock, s_terms, &s_k[c], threadIdx.x < 3u);
   }
   __syncthreads();
   LensT L{};
   if constexpr (kTables) L.terms = s_terms;
-  const lentil_params &P = a.P;
-  const VisitsDev &V = a.V;
   const uint32_t lane = threadIdx.x & 63u;
   const unsigned long long n_groups = (a.v_end - a.v_begin + 63u) / 64u;
   const uint32_t n_traces = ch.n_traces == 3u ? 3u : 1u;
   const double qnan = __builtin_nan("");
   unsigned long long wave_attempts = 0;
   for (;;) {
-    unsigned long long g = 0;
-    if (lane == 0u) g = atomicAdd(&a.ctr[0], 1ull);
-    g = ld_readlane(g, 0);
+    const unsigned long long g = ld_take_ticket(&a.ctr[0], lane);
     if (g >= n_groups) break;
     // ---- the prologue, lane = visit
     const uint64_t v = a.v_begin + g * 64u + lane;
-    VisitInfo I{};
-    int vpx = 0, vpy = 0;
-    if (v < a.v_end) {
-      const float invd = V.inv_density ? V.inv_density[v] : P.inverse_sample_density;
-      I = visit_prologue(P, a.lens_length, V.rgba[v], V.pos_z[v], V.raydir_time[v], V.volume_ignore[v], V.transmission[v], invd, V.cam);
-      visit_pixel(V, v, vpx, vpy);
-    } else {
-      I.redistribute = false;
-    }
-    unsigned long long todo = __ballot(I.redistribute);
+    LdVisitLane x{};
+    if (v < a.v_end) x = ld_visit_lane(a.P, a.V, a.lens_length, v);
+    unsigned long long todo = __ballot(x.I.redistribute);
     // ---- the set lanes one after another, lane = attempt
     while (todo) {
       const int src = __builtin_ctzll(todo);
       todo &= todo - 1ull;
-      const float cs[3] = {ld_readlane(I.cs[0], src), ld_readlane(I.cs[1], src), ld_readlane(I.cs[2], src)};
-      const int px = (int)ld_readlane((uint32_t)vpx, src), py = (int)ld_readlane((uint32_t)vpy, src);
-      const uint32_t samples = ld_readlane((uint32_t)I.samples, src);
-      const uint32_t visit = (uint32_t)(a.v_begin + g * 64u) + (uint32_t)src;
-      const uint32_t max_total = samples * 5u;                           // (the host keeps 5 * samples + retries below 2^30)
+      const LdWaveVisit w = ld_broadcast_visit(x, src, (uint32_t)(a.v_begin + g * 64u));
+      const uint32_t samples = w.samples, max_total = w.max_total, visit = w.visit;     // (the host keeps 5 * samples + retries below 2^30)
       int32_t count = 0;                                                 // the reference's `count`: signed, may go down
       uint32_t made = 0;
-      for (uint32_t k0 = 0; k0 < max_total && count < (int32_t)samples; k0 = (max_total - k0 > kLdSlab) ? k0 + kLdSlab : max_total) {
+      for (uint32_t k0 = 0; k0 < max_total && count < (int32_t)samples; k0 = ld_next_slab(k0, max_total)) {
         const uint32_t attempt = k0 + lane;
-        const bool commit = max_total - k0 > lane;                      // attempt < max_total
+        const bool commit = max_total - k0 > lane;
 
         uint32_t code0 = LENTIL_POINT_VIGNETTED, code1 = LENTIL_POINT_VIGNETTED, code2 = LENTIL_POINT_VIGNETTED;
         double xa0 = qnan, xb0 = qnan, xa1 = qnan, xb1 = qnan, xa2 = qnan, xb2 = qnan;
@@ -696,45 +579,11 @@ __global__ __launch_bounds__(kLdBlock) void list_draws_chroma_kernel(ListDrawArg
 #pragma unroll 1
         for (uint32_t c = 0; c < n_traces; ++c) {
           L.k = &s_k[c];
-          uint32_t code = LENTIL_POINT_VIGNETTED;
-          double xy0 = qnan, xy1 = qnan;
-          int tries = 0;
-          const DevLens &k = L.consts();
-          const double target[3] = {-(double)cs[0] * 10.0, -(double)cs[1] * 10.0, -(double)cs[2] * 10.0};   // src/lentil_filter.cpp:271
-          bool ok = false;
-          bool trying = commit && tries <= P.vignetting_retries;
-          double sensor[4] = {0.0, 0.0, 0.0, 0.0};
-          while (__any(trying)) {
-            double ax, ay;
-            po_aperture_sample(P, a.bokeh, a.bokeh.cdfRow, (uint32_t)(px * py + px), attempt + (uint32_t)tries, ax, ay);
-            NewtonState s;
-            newton_init(s);
-            while (trying && newton_continue(s)) newton_iter(L, target, ax, ay, s);
-            double out4;
-            const float transmittance = (float)newton_finish(L, s, out4);
-            bool pass = !(transmittance <= 0);
-            const double ipx = s.x + s.dx * k.back_focal_length;
-            const double ipy = s.y + s.dy * k.back_focal_length;
-            if (ipx * ipx + ipy * ipy > k.inner_pupil_radius * k.inner_pupil_radius) pass = false;
-            if (trying) {
-              if (pass) {
-                sensor[0] = s.x; sensor[1] = s.y; sensor[2] = s.dx; sensor[3] = s.dy;
-                ok = true; trying = false;
-              } else {
-                ++tries; trying = tries <= P.vignetting_retries;
-              }
-            }
-          }
-          if (ok) {
-            const double sen0 = sensor[0] + sensor[2] * -P.sensor_shift;
-            const double sen1 = sensor[1] + sensor[3] * -P.sensor_shift;
-            uint32_t pn = 0;
-            code = po_sensor_to_pixel_xy(P, sen0, sen1, pn, xy0, xy1) ? pn : LENTIL_POINT_OUTSIDE;
-          }
+          const AttemptTrace t = trace_attempt<true>(a.P, L, a.bokeh, w.cs, w.px, w.py, attempt, commit, NoSeedAnswers{});
           // (selects, not an indexed array: the results stay in registers)
-          if (c == 0u) { code0 = code; xa0 = xy0; xb0 = xy1; tries0 = tries; }
-          if (c == 1u) { code1 = code; xa1 = xy0; xb1 = xy1; tries1 = tries; }
-          if (c == 2u) { code2 = code; xa2 = xy0; xb2 = xy1; tries2 = tries; }
+          if (c == 0u) { code0 = t.code; xa0 = t.xy0; xb0 = t.xy1; tries0 = t.tries; }
+          if (c == 1u) { code1 = t.code; xa1 = t.xy0; xb1 = t.xy1; tries1 = t.tries; }
+          if (c == 2u) { code2 = t.code; xa2 = t.xy0; xb2 = t.xy1; tries2 = t.tries; }
         }
         if (n_traces == 1u) {
           code1 = code2 = code0; xa1 = xa2 = xa0; xb1 = xb2 = xb0; tries1 = tries2 = tries0;
@@ -757,27 +606,15 @@ __global__ __launch_bounds__(kLdBlock) void list_draws_chroma_kernel(ListDrawArg
         const unsigned long long m0 = __ballot(executed && ok0), m1 = __ballot(executed && ok1), m2 = __ballot(executed && ok2);
         if (m0 | m1 | m2) {
           unsigned long long slot = list_wave_slot3(&a.ctr[1], m0, m1, m2, lane);
-          lentil_draw r;
-          r.visit = visit;
-          if (executed && ok0) {
-            if (slot < a.capacity) { r.attempt = attempt; r.pixel = code0; r.tries = tries0; r.xy[0] = xa0; r.xy[1] = xb0; a.out[slot] = r; }
-            ++slot;
-          }
-          if (executed && ok1) {
-            if (slot < a.capacity) { r.attempt = attempt | (1u << 30); r.pixel = code1; r.tries = tries1; r.xy[0] = xa1; r.xy[1] = xb1; a.out[slot] = r; }
-            ++slot;
-          }
-          if (executed && ok2) {
-            if (slot < a.capacity) { r.attempt = attempt | (2u << 30); r.pixel = code2; r.tries = tries2; r.xy[0] = xa2; r.xy[1] = xb2; a.out[slot] = r; }
-          }
+          if (executed && ok0) ld_store_draw(a, slot++, visit, attempt, code0, tries0, xa0, xb0);
+          if (executed && ok1) ld_store_draw(a, slot++, visit, attempt | (1u << 30), code1, tries1, xa1, xb1);
+          if (executed && ok2) ld_store_draw(a, slot, visit, attempt | (2u << 30), code2, tries2, xa2, xb2);
         }
         count = __builtin_amdgcn_readlane(running, istar);
-        // (the loop ends behind the attempt that brought the count to `samples`; a slab without it was attempted to its end)
-        if (rmask) made = k0 + (uint32_t)istar + 1u;
-        else made = (max_total - k0 > kLdSlab) ? k0 + kLdSlab : max_total;
+        made = ld_made(k0, max_total, rmask != 0ull, (uint32_t)istar);
       }
       wave_attempts += made;
     }
   }
-  if (lane == 0u && wave_attempts) atomicAdd(&a.ctr[2], wave_attempts);
+  ld_add_wave_sum(&a.ctr[2], wave_attempts, lane);
 }
