@@ -743,6 +743,18 @@ int lentil_hip_camera_rays(lentil_hip_ctx *ctx, const lentil_camera_ray_batch *b
  * environment; without it, or with LENTIL_RAYS_COMPILED=0, camera rays run path 1 (the default until the compiled kernels'
  * rate has been measured against the interpreter's).  lentil_hip_set_lens_mode(ctx, 1) forces path 1 too. */
 int lentil_hip_camera_rays_path(lentil_hip_ctx *ctx, int *path);
+/* lentil_hip_camera_rays with a wavelength per ray, for a spectral renderer that draws one per path: ray i is, word for word
+ * of its 21 floats and its tries, the ray lentil_hip_camera_rays gives for id first_ray + i with lambda = lambdas[i].
+ *   lambdas [n]  micrometres; host or device memory as LENTIL_RAYS_DEVICE_POINTERS says for in / out / tries.  The values are
+ *                used as given: there is no range check (a NaN or a wavelength far outside the fit gives what the polynomials
+ *                give for it, weight 0 where a NaN comes out).  batch->lambda is ignored.
+ * The per-ray xor128 state, the flags and the independence from how a batch is split are lentil_hip_camera_rays' (the split
+ * moves lambdas along with in).  Thin lens: the wavelengths are ignored as the scalar one is, lambdas may be NULL, the result
+ * is the scalar call's.  Observes the context like the scalar call; takes no part in the streamed passes' turns.
+ * LENTIL_ERR_INVALID: where lentil_hip_camera_rays returns it, and for lambdas NULL with polynomial optics and n > 0.
+ * n == 0 launches nothing.  lentil_hip_camera_rays_path reports this call too: 0, 1, or 2 (LENTIL_RAYS_COMPILED=1 and a
+ * compiled-in lens); a table compiled at run time is served by the interpreter (1) -- there is no spectral run-time kernel. */
+int lentil_hip_camera_rays_spectral(lentil_hip_ctx *ctx, const lentil_camera_ray_batch *batch, const double *lambdas);
 
 /* --- scene points traced backward through the lens in batches --------------------------
  * The backward counterpart of lentil_hip_camera_rays: for a camera-space point and a draw number, where on the sensor a draw
@@ -801,6 +813,16 @@ int lentil_hip_trace_points(lentil_hip_ctx *ctx, const lentil_point_batch *batch
  * passes run for them by default too.  A table compiled at run time (lentil_hip_lens_jit_status) is served by the
  * interpreter; lentil_hip_set_lens_mode(ctx, 1) forces the interpreter.  The results are the same bit for bit. */
 int lentil_hip_trace_points_path(lentil_hip_ctx *ctx, int *path);
+/* lentil_hip_trace_points with a wavelength per point, for a spectral film: all `attempts` queries of point j are, bit for
+ * bit in out_pixel, out_xy, out_sensor and out_tries, what lentil_hip_trace_points gives with lambda = lambdas[j].
+ *   lambdas [n_points]  micrometres; an entry of 0 means params.lambda_bw, as the scalar field does.  Host or device memory
+ *                       as LENTIL_POINTS_DEVICE_POINTERS says for the batch's own pointers.  The values are used as given:
+ *                       there is no range check.  batch->lambda is ignored.
+ * Thin lens: the wavelengths are ignored as the scalar one is, lambdas may be NULL, the result is the scalar call's.
+ * Observes the context like the scalar call; takes no part in the streamed passes' turns.
+ * LENTIL_ERR_INVALID: where lentil_hip_trace_points returns it, and for lambdas NULL with polynomial optics and n_points > 0.
+ * n_points == 0 launches nothing.  lentil_hip_trace_points_path reports this call too (0, 1 or 2). */
+int lentil_hip_trace_points_spectral(lentil_hip_ctx *ctx, const lentil_point_batch *batch, const double *lambdas);
 
 /* --- a visit range's plan and its accepted draws, for a renderer with its own film ---------------
  * lentil_hip_trace_points answers where attempt m of a point lands.  These two calls answer what the pass makes of the

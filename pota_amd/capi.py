@@ -31,6 +31,7 @@ EXPORTS = [
     "lentil_hip_lens_is_compiled", "lentil_hip_set_lens_mode",
     "lentil_hip_focus_search", "lentil_hip_test_y0_intersection", "lentil_hip_camera_rays", "lentil_hip_camera_rays_path",
     "lentil_hip_trace_points", "lentil_hip_trace_points_path",
+    "lentil_hip_camera_rays_spectral", "lentil_hip_trace_points_spectral",
     "lentil_hip_plan_visits", "lentil_hip_list_draws", "lentil_hip_list_draws_path", "lentil_hip_draw_channels",
     "lentil_hip_set_xor128_state", "lentil_hip_get_xor128_state", "lentil_hip_tl_chroma_stats", "lentil_hip_test_xor128_jump",
     "lentil_hip_host_alloc", "lentil_hip_host_free", "lentil_hip_visits_begin", "lentil_hip_visits_append",
@@ -190,6 +191,8 @@ def load_library():
         "lentil_hip_camera_rays_path": (i, [vp, C.POINTER(C.c_int)]),
         "lentil_hip_trace_points": (i, [vp, C.POINTER(_abi.PointBatch)]),
         "lentil_hip_trace_points_path": (i, [vp, C.POINTER(C.c_int)]),
+        "lentil_hip_camera_rays_spectral": (i, [vp, C.POINTER(_abi.CameraRayBatch), vp]),
+        "lentil_hip_trace_points_spectral": (i, [vp, C.POINTER(_abi.PointBatch), vp]),
         "lentil_hip_plan_visits": (i, [vp, u64, u64, vp, C.c_uint32, C.POINTER(u64)]),
         "lentil_hip_list_draws": (i, [vp, C.POINTER(_abi.DrawList)]),
         "lentil_hip_list_draws_path": (i, [vp, C.POINTER(C.c_int)]),
@@ -307,6 +310,36 @@ def lens_jit_compile(table, compile=True):
     sec, nb = C.c_double(0.0), C.c_uint64(0)
     rc = lib.lentil_hip_debug_lens_jit_compile(C.byref(table), 1 if compile else 0, src, int(n.value) + 1, None, log, 1 << 16, C.byref(sec), C.byref(nb))
     return int(rc), src.value.decode(), log.value.decode(errors="replace"), float(sec.value), int(nb.value)
+
+
+def _lambdas_arg(call, lambdas, n, device):
+    """The lambdas argument of the spectral calls, checked against the call's other arrays: n entries of float64, and of their
+    kind -- device None: they are numpy (host pointers), so lambdas is a numpy float64 array (or a plain sequence); else they
+    are torch tensors on GPU `device`, so lambdas is a contiguous float64 tensor there.  -> (the array to keep alive, its
+    pointer).  ValueError otherwise: a numpy array handed over as device memory, or the reverse, would be read as what it is
+    not."""
+    is_tensor = hasattr(lambdas, "data_ptr") and not isinstance(lambdas, np.ndarray)
+    if device is None:
+        if is_tensor:
+            raise ValueError("%s: lambdas is a tensor, the other arrays are numpy" % call)
+        if isinstance(lambdas, np.ndarray) and lambdas.dtype != np.float64:
+            raise ValueError("%s: lambdas must be float64, not %s" % (call, lambdas.dtype))
+        lam = np.ascontiguousarray(lambdas, np.float64)
+        if lam.shape != (n,):
+            raise ValueError("%s: lambdas must be [%d], one per %s" % (call, n, "ray" if call == "camera_rays" else "point"))
+        return lam, lam.ctypes.data
+    import torch
+    if not is_tensor:
+        raise ValueError("%s: lambdas is not a tensor, the other arrays are" % call)
+    if lambdas.dtype != torch.float64:
+        raise ValueError("%s: lambdas must be float64, not %s" % (call, lambdas.dtype))
+    if not lambdas.is_cuda or lambdas.device.index != device:
+        raise ValueError("%s: lambdas is on %s, the context on GPU %d" % (call, lambdas.device, device))
+    if not lambdas.is_contiguous():
+        raise ValueError("%s: lambdas must be contiguous" % call)
+    if tuple(lambdas.shape) != (n,):
+        raise ValueError("%s: lambdas must be [%d], one per %s" % (call, n, "ray" if call == "camera_rays" else "point"))
+    return lambdas, lambdas.data_ptr()
 
 
 class Context:
@@ -472,7 +505,7 @@ class Context:
         self._chk(self.lib.lentil_hip_focus_search(self.h, focal_distance, lam, C.byref(best)))
         return best.value
 
-    def camera_rays(self, inp, first_ray=0, lam=0.55, exposure=1.0, seed=0, differentials=True, want_tries=False):
+    def camera_rays(self, inp, first_ray=0, lam=0.55, exposure=1.0, seed=0, differentials=True, want_tries=False, lambdas=None):
         """Forward camera rays in a batch (lentil_hip_camera_rays): camera_create_ray for every row of inp, fp32 [n, 6] =
         sx, sy, dsx, dsy, lensx, lensy -> fp32 [n, 21] = origin, dir, weight, dOdx, dOdy, dDdx, dDdy (and, want_tries, int32
         [n]: the vignetted tries of each ray's own trace).  Ray i draws its retries from its own xor128 state, the four
@@ -480,7 +513,9 @@ class Context:
         numpy in: host pointers, numpy out, complete on return.  A contiguous torch tensor on this context's device: device
         pointers, torch tensors out, enqueued on the context's stream (stream()) without waiting.  The caller orders both ends:
         whatever produced inp must be complete on, or ordered before, the context's stream; sync() or the stream orders the
-        results; and inp and the returned tensors must stay alive until the stream has passed the call."""
+        results; and inp and the returned tensors must stay alive until the stream has passed the call.
+        lambdas: float64 [n], micrometres, of inp's kind (numpy with numpy, a contiguous tensor on the same GPU with a tensor;
+        it stays alive like inp): ray i at lambdas[i] instead of every ray at lam (lentil_hip_camera_rays_spectral)."""
         flags = 0 if differentials else _abi.RAYS_NO_DIFFERENTIALS
         b = _abi.CameraRayBatch()
         if isinstance(inp, np.ndarray) or not hasattr(inp, "data_ptr"):
@@ -491,6 +526,7 @@ class Context:
             out = np.empty((n, _abi.RAY_OUT_FLOATS), np.float32)
             tries = np.empty((n,), np.int32) if want_tries else None
             ptrs = (a.ctypes.data, out.ctypes.data, tries.ctypes.data if want_tries else None)
+            kind = None
         else:
             import torch
             if inp.dtype != torch.float32 or inp.dim() != 2 or inp.shape[1] != _abi.RAY_IN_FLOATS:
@@ -505,10 +541,16 @@ class Context:
             tries = torch.empty((n,), dtype=torch.int32, device=a.device) if want_tries else None
             ptrs = (a.data_ptr(), out.data_ptr(), tries.data_ptr() if want_tries else None)
             flags |= _abi.RAYS_DEVICE_POINTERS
+            kind = self.device
+        if lambdas is not None:
+            lambdas, lam_ptr = _lambdas_arg("camera_rays", lambdas, n, kind)
         b.n, b.first_ray = n, int(first_ray)
         b.inp, b.out, b.tries = (p if n else None for p in ptrs)
         b.lam, b.exposure, b.rng_seed, b.flags = float(lam), float(exposure), int(seed) & 0xFFFFFFFF, flags
-        self._chk(self.lib.lentil_hip_camera_rays(self.h, C.byref(b)))
+        if lambdas is not None:
+            self._chk(self.lib.lentil_hip_camera_rays_spectral(self.h, C.byref(b), lam_ptr if n else None))
+        else:
+            self._chk(self.lib.lentil_hip_camera_rays(self.h, C.byref(b)))
         return (out, tries) if want_tries else out
 
     def camera_rays_path(self):
@@ -518,7 +560,8 @@ class Context:
         self._chk(self.lib.lentil_hip_camera_rays_path(self.h, C.byref(path)))
         return path.value
 
-    def trace_points(self, cs, pixel, attempts, first_attempt=None, lam=0.0, want_xy=True, want_sensor=False, want_tries=False):
+    def trace_points(self, cs, pixel, attempts, first_attempt=None, lam=0.0, want_xy=True, want_sensor=False, want_tries=False,
+                     lambdas=None):
         """Scene points traced backward through the lens in a batch (lentil_hip_trace_points): for every point (cs fp32 [n, 3],
         camera space, cm; pixel uint32 [n] = px | py << 16, the source pixel that seeds the draws) and every attempt
         first_attempt[point] ... + attempts - 1 (uint32 [n]; None: from 0), where a draw of the pass puts it.
@@ -528,7 +571,9 @@ class Context:
         (polynomial optics: mm on the sensor) and "tries" int32 [n, attempts].  lam: micrometres, 0 = params.lambda_bw.
         numpy in: host pointers, numpy out, complete on return.  Contiguous torch tensors on this context's device: device
         pointers, torch tensors out, enqueued on the context's stream (stream()) without waiting; the caller orders both ends as
-        for camera_rays, and with device pointers the seeds first_attempt + attempts + vignetting_retries must fit 32 bits."""
+        for camera_rays, and with device pointers the seeds first_attempt + attempts + vignetting_retries must fit 32 bits.
+        lambdas: float64 [n], micrometres, 0 = params.lambda_bw, of cs's kind (numpy with numpy, a contiguous tensor on the same
+        GPU with tensors): point j at lambdas[j] instead of every point at lam (lentil_hip_trace_points_spectral)."""
         b = _abi.PointBatch()
         attempts = int(attempts)
         if isinstance(cs, np.ndarray) or not hasattr(cs, "data_ptr"):
@@ -549,7 +594,7 @@ class Context:
             if want_tries:
                 out["tries"] = np.empty((n, k), np.int32)
             ptr = lambda t: None if t is None else t.ctypes.data      # noqa: E731
-            flags = 0
+            flags, kind = 0, None
         else:
             import torch
             if cs.dtype != torch.float32 or cs.dim() != 2 or cs.shape[1] != 3:
@@ -574,12 +619,17 @@ class Context:
             if want_tries:
                 out["tries"] = torch.empty((n, k), dtype=torch.int32, device=a.device)
             ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
-            flags = _abi.POINTS_DEVICE_POINTERS
+            flags, kind = _abi.POINTS_DEVICE_POINTERS, self.device
+        if lambdas is not None:
+            lambdas, lam_ptr = _lambdas_arg("trace_points", lambdas, n, kind)
         b.n_points, b.attempts, b.flags, b.lam = n, attempts & 0xFFFFFFFF, flags, float(lam)
         if n:
             b.cs, b.pixel, b.first_attempt = ptr(a), ptr(px), ptr(fa)
             b.out_pixel, b.out_xy, b.out_sensor, b.out_tries = (ptr(out.get(key)) for key in ("pixel", "xy", "sensor", "tries"))
-        self._chk(self.lib.lentil_hip_trace_points(self.h, C.byref(b)))
+        if lambdas is not None:
+            self._chk(self.lib.lentil_hip_trace_points_spectral(self.h, C.byref(b), lam_ptr if n else None))
+        else:
+            self._chk(self.lib.lentil_hip_trace_points(self.h, C.byref(b)))
         return out
 
     def trace_points_path(self):

@@ -244,3 +244,67 @@ __global__ __launch_bounds__(kRayBlock) void camera_rays_kernel(CameraRayArgs a)
   for (uint32_t j = threadIdx.x; j < nb * kRayOutFloats; j += kRayBlock) a.out[ray0 * kRayOutFloats + j] = s_io[j];
   if (a.tries && active) a.tries[ray0 + threadIdx.x] = tries_main;
 }
+
+// lentil_hip_camera_rays_spectral: ray i at lambdas[i] (a.lambda is not read), polynomial optics.  camera_rays_kernel line
+// for line but for the lens it hands trace_ray_fw_po (a kernel of its own, not a parameter of that one: the scalar call's
+// code stays what it is).  The wavelength differs from lane to lane, so the lambda powers are the lane's own and the block
+// shares the header's constants alone: a compiled-in lens (LensT = GenLensAt<Gen>) gets the powers as a local array that its
+// straight-line code indexes with constants -- registers -- and the interpreter (LdsLensAt<LambdaLane>) raises the lane's
+// wavelength at the term, the exponent being wave-uniform like the others (DESIGN.md 4.6 has the LDS table it was weighed
+// against).
+template <class LensT, bool kTables>
+__global__ __launch_bounds__(kRayBlock) void camera_rays_spectral_kernel(CameraRayArgs a, const double *lambdas) {
+  __shared__ DevTerm s_terms[kTables ? kMaxTerms : 1];
+  __shared__ DevLens s_k;
+  __shared__ float s_io[kRayBlock * kRayOutFloats];
+  stage_lens<kTables>(a.lens, a.terms, 0.0, kRayBlock, s_terms, &s_k, threadIdx.x == 0);      // (the barrier is the input's, below)
+  const uint64_t ray0 = (uint64_t)blockIdx.x * kRayBlock;
+  const uint32_t nb = (uint32_t)((a.n - ray0) < (uint64_t)kRayBlock ? (a.n - ray0) : (uint64_t)kRayBlock);   // >= 1: the grid is ceil(n / 256)
+  for (uint32_t j = threadIdx.x; j < nb * kRayInFloats; j += kRayBlock) s_io[j] = a.in[ray0 * kRayInFloats + j];
+  __syncthreads();
+  const bool active = threadIdx.x < nb;
+  const uint32_t li = active ? threadIdx.x : nb - 1u;          // lanes past the end walk along on the last ray
+  float in[kRayInFloats];
+#pragma unroll
+  for (int c = 0; c < kRayInFloats; ++c) in[c] = s_io[li * kRayInFloats + c];
+  __syncthreads();                                             // (s_io takes the output next)
+
+  const double lambda = lambdas[ray0 + li];
+  double lp[kMaxExp + 1];
+  LensT L{};
+  L.k = &s_k;
+  if constexpr (kTables) {
+    L.terms = s_terms;
+    L.lam.lambda = lambda;
+  } else {
+    lambda_powers(lambda, lp);
+    L.lam.lp = lp;
+  }
+  RayRng rng = ray_rng_init(a.first_ray + (uint32_t)ray0 + li, a.rng_seed);
+  double r1 = (double)in[4], r2 = (double)in[5];
+  const float step = 0.001f;
+  const float sxd = in[0] + (in[2] * step), syd = in[1] + (in[3] * step);
+  const float inv = 1.0f / step;                               // AtVector / float multiplies by 1 / f
+  float res[kRayOutFloats];
+#pragma unroll
+  for (int c = 9; c < kRayOutFloats; ++c) res[c] = 0.0f;
+  int tries_main = 0;
+  const int n_traces = a.differentials ? 3 : 1;
+  for (int t = 0; t < n_traces; ++t) {
+    const double sx = (double)(t == 1 ? sxd : in[0]), sy = (double)(t == 2 ? syd : in[1]);
+    FwRay ray;
+    trace_ray_fw_po(a.P, L, a.bokeh, rng, sx, sy, r1, r2, t != 0, active, ray);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      if (t == 0) { res[c] = ray.o[c]; res[3 + c] = ray.d[c]; res[6 + c] = ray.w * a.exposure; }
+      else if (t == 1) { res[9 + c] = (ray.o[c] - res[c]) * inv; res[15 + c] = (ray.d[c] - res[3 + c]) * inv; }
+      else { res[12 + c] = (ray.o[c] - res[c]) * inv; res[18 + c] = (ray.d[c] - res[3 + c]) * inv; }
+    }
+    if (t == 0) tries_main = ray.tries;
+  }
+#pragma unroll
+  for (int c = 0; c < kRayOutFloats; ++c) s_io[threadIdx.x * kRayOutFloats + c] = res[c];
+  __syncthreads();
+  for (uint32_t j = threadIdx.x; j < nb * kRayOutFloats; j += kRayBlock) a.out[ray0 * kRayOutFloats + j] = s_io[j];
+  if (a.tries && active) a.tries[ray0 + threadIdx.x] = tries_main;
+}

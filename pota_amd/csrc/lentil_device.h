@@ -532,6 +532,111 @@ struct GenLens {
 };
 
 // ---------------------------------------------------------------------------------------
+// Spectral batches (lentil_hip_camera_rays_spectral, lentil_hip_trace_points_spectral): the same lenses with the lambda
+// powers taken from somewhere other than the block's header, which keeps only the constants.  The wavelength enters a
+// polynomial through lens_ipow(lambda, e) alone, so nothing else differs, and every power has the bits stage_lens and the
+// host compute: 1, lambda, ipow_u(lambda, e).
+//   LambdaTable  a table of kMaxExp + 1 powers: a wave's row in LDS (trace points: one wavelength per wave), or a lane's own
+//                array, which must be indexed with constants only (camera rays through GenLensAt: registers)
+//   LambdaLane   the lane's wavelength itself, raised at the term (camera rays through the interpreter: the exponent is
+//                wave-uniform, the wavelength is not)
+// ---------------------------------------------------------------------------------------
+struct LambdaTable {
+  const double *lp;
+  LD_DEV double pow(uint32_t el) const { return lp[el]; }
+};
+struct LambdaLane {
+  double lambda;
+  LD_DEV double pow(uint32_t el) const { return ipow_u(lambda, el); }      // (el >= 1; ipow_u(x, 1) is x)
+};
+
+// lambda powers 0 ... kMaxExp of one wavelength, as stage_lens writes them
+LD_DEV void lambda_powers(double lambda, double lp[kMaxExp + 1]) {
+  lp[0] = 1.0; lp[1] = lambda;
+#pragma unroll
+  for (uint32_t e = 2; e <= (uint32_t)kMaxExp; ++e) lp[e] = ipow_u(lambda, e);
+}
+
+// LdsLens with the lambda factor of a term from Lam: the same terms, the same operations in the same order
+template <class Lam>
+struct LdsLensAt {
+  const DevTerm *terms;   // LDS
+  const DevLens *k;       // LDS copy of the header (its lambda powers are not read)
+  Lam lam;
+
+  LD_DEV double eval(int pid, const double v[4]) const {
+    const uint32_t first = k->first[pid], count = k->count[pid];
+    double sum = 0.0;
+    for (uint32_t i = 0; i < count; ++i) {
+      const DevTerm t = terms[first + i];
+      const uint32_t e = __builtin_amdgcn_readfirstlane(t.e);
+      double term = t.c;
+#pragma unroll
+      for (int var = 0; var < 4; ++var) {
+        const uint32_t ev = (e >> (4 * var)) & 15u;
+        if (ev == 1) term = term * v[var];
+        else if (ev > 1) term = term * ipow_u(v[var], ev);
+      }
+      const uint32_t el = (e >> 16) & 15u;
+      if (el) term = term * lam.pow(el);
+      sum = (i == 0) ? term : sum + term;
+    }
+    return sum;
+  }
+  LD_DEV void eval_bw(const double v[4], double pred_ap[2], double Jap[4], double out[4], double Jout[4]) const {
+    pred_ap[0] = eval(P_AP_X, v);
+    pred_ap[1] = eval(P_AP_Y, v);
+    Jap[0] = eval(P_DAP_00, v); Jap[1] = eval(P_DAP_01, v);
+    Jap[2] = eval(P_DAP_10, v); Jap[3] = eval(P_DAP_11, v);
+    out[0] = eval(P_OUT_X, v); out[1] = eval(P_OUT_Y, v);
+    out[2] = eval(P_OUT_DX, v); out[3] = eval(P_OUT_DY, v);
+    Jout[0] = eval(P_DOUT_00, v); Jout[1] = eval(P_DOUT_01, v);
+    Jout[2] = eval(P_DOUT_10, v); Jout[3] = eval(P_DOUT_11, v);
+  }
+  LD_DEV double transmittance(const double v[4]) const { return eval(P_OUT_T, v); }
+  LD_DEV void eval_fw_newton(const double v[4], double pred_ap[2], double pred_dir[2], double Jap[4], double Jappos[4]) const {
+    pred_ap[0] = eval(P_AP_X, v); pred_ap[1] = eval(P_AP_Y, v);
+    pred_dir[0] = eval(P_AP_DX, v); pred_dir[1] = eval(P_AP_DY, v);
+    Jap[0] = eval(P_DAP_00, v); Jappos[0] = eval(P_DAPPOS_00, v);
+    Jap[1] = eval(P_DAP_01, v); Jappos[1] = eval(P_DAPPOS_01, v);
+    Jap[2] = eval(P_DAP_10, v); Jappos[2] = eval(P_DAPPOS_10, v);
+    Jap[3] = eval(P_DAP_11, v); Jappos[3] = eval(P_DAPPOS_11, v);
+  }
+  LD_DEV void eval_out(const double v[4], double out[4]) const {
+    out[0] = eval(P_OUT_X, v); out[1] = eval(P_OUT_Y, v);
+    out[2] = eval(P_OUT_DX, v); out[3] = eval(P_OUT_DY, v);
+  }
+  LD_DEV const DevLens &consts() const { return *k; }
+};
+
+// GenLens with the lambda powers from lam.lp: the generated code indexes them with constants
+template <class Gen>
+struct GenLensAt {
+  const DevLens *k;       // LDS copy of the header (constants)
+  LambdaTable lam;
+  LD_DEV void eval_bw(const double v[4], double pred_ap[2], double Jap[4], double out[4], double Jout[4]) const {
+    Gen::eval_bw(v, lam.lp, pred_ap, Jap, out, Jout);
+  }
+  LD_DEV double transmittance(const double v[4]) const { return Gen::transmittance(v, lam.lp); }
+  LD_DEV void eval_fw_newton(const double v[4], double pred_ap[2], double pred_dir[2], double Jap[4], double Jappos[4]) const {
+    Gen::eval_fw_newton(v, lam.lp, pred_ap, pred_dir, Jap, Jappos);
+  }
+  LD_DEV void eval_out(const double v[4], double out[4]) const { Gen::eval_out(v, lam.lp, out); }
+  LD_DEV const DevLens &consts() const { return *k; }
+};
+
+// the spectral counterparts of a scalar call's lens type: Lane for one wavelength per lane, Wave for one per wave
+template <class LensT> struct SpectralLens;
+template <> struct SpectralLens<LdsLens> {
+  using Lane = LdsLensAt<LambdaLane>;
+  using Wave = LdsLensAt<LambdaTable>;
+};
+template <class Gen> struct SpectralLens<GenLens<Gen>> {
+  using Lane = GenLensAt<Gen>;
+  using Wave = GenLensAt<Gen>;
+};
+
+// ---------------------------------------------------------------------------------------
 // Aperture draw of trace_ray_bw_po, src/lentil.h:596-609 (GCC argument order: see oracle)
 // ---------------------------------------------------------------------------------------
 LD_DEV void po_aperture_sample(const lentil_params &P, const DevBokeh &B, const float *cdfRow, uint32_t a,

@@ -4028,7 +4028,9 @@ LENTIL_API int lentil_hip_test_aperture_sample(lentil_hip_ctx *ctx, uint64_t n, 
 }
 
 // ---- forward camera rays in batches (lentil_camera_rays.h) -------------------------------------------------------------
-LENTIL_API int lentil_hip_camera_rays(lentil_hip_ctx *ctx, const lentil_camera_ray_batch *batch) {
+// The scalar and the spectral call: `spectral` takes ray i at lambdas[i] (polynomial optics; the thin lens reads no wavelength
+// and runs what the scalar call runs), else every ray at batch->lambda.
+static int camera_rays_call(lentil_hip_ctx *ctx, const lentil_camera_ray_batch *batch, const double *lambdas, bool spectral) {
   CHECK_CTX(ctx);
   if (!batch) return fail(ctx, LENTIL_ERR_INVALID, "batch is null");
   if (!ctx->have_params) return fail(ctx, LENTIL_ERR_INVALID, "set_params first");
@@ -4040,6 +4042,8 @@ LENTIL_API int lentil_hip_camera_rays(lentil_hip_ctx *ctx, const lentil_camera_r
     return fail(ctx, LENTIL_ERR_INVALID, "ray ids first_ray ... first_ray + n - 1 must fit 32 bits");
   if (!n) return LENTIL_OK;
   if (!batch->in || !batch->out) return fail(ctx, LENTIL_ERR_INVALID, "in / out is null");
+  spectral = spectral && po;
+  if (spectral && !lambdas) return fail(ctx, LENTIL_ERR_INVALID, "lambdas is null");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   CameraRayArgs a{};
   a.P = ctx->P; a.lens = po ? ctx->d_lens : nullptr; a.terms = po ? ctx->d_terms : nullptr; a.bokeh = ctx->bokeh;
@@ -4049,11 +4053,14 @@ LENTIL_API int lentil_hip_camera_rays(lentil_hip_ctx *ctx, const lentil_camera_r
   TmpFree tf;
   float *d_in = nullptr, *d_out = nullptr;
   int32_t *d_tries = nullptr;
+  double *d_lambdas = nullptr;
   if (device) {
     a.in = batch->in; a.out = batch->out; a.tries = batch->tries;
   } else {
     int rc;
     if ((rc = dev_copy_in(ctx, batch->in, (size_t)n * kRayInFloats, &d_in, tf.v))) return rc;
+    if (spectral && (rc = dev_copy_in(ctx, lambdas, (size_t)n, &d_lambdas, tf.v))) return rc;
+    lambdas = d_lambdas;
     if ((rc = dev_alloc(ctx, (size_t)n * kRayOutFloats, &d_out, tf.v))) return rc;
     if (batch->tries && (rc = dev_alloc(ctx, (size_t)n, &d_tries, tf.v))) return rc;
     a.in = d_in; a.out = d_out; a.tries = d_tries;
@@ -4064,12 +4071,13 @@ LENTIL_API int lentil_hip_camera_rays(lentil_hip_ctx *ctx, const lentil_camera_r
     const bool compiled = ctx->use_generated && ctx->rays_compiled;
 #define LENTIL_LAUNCH_GEN(NAME)                                                                              \
     if (!path && compiled && ctx->lens_hash == gen::Lens_##NAME::kTableHash) {                               \
-      hipLaunchKernelGGL((camera_rays_kernel<GenLens<gen::Lens_##NAME>, false, true>), grid, dim3(kRayBlock), 0, ctx->stream, a); \
+      if (spectral) hipLaunchKernelGGL((camera_rays_spectral_kernel<SpectralLens<GenLens<gen::Lens_##NAME>>::Lane, false>), grid, dim3(kRayBlock), 0, ctx->stream, a, lambdas); \
+      else hipLaunchKernelGGL((camera_rays_kernel<GenLens<gen::Lens_##NAME>, false, true>), grid, dim3(kRayBlock), 0, ctx->stream, a); \
       path = 2;                                                                                              \
     }
     LENTIL_GENERATED_LENSES(LENTIL_LAUNCH_GEN)
 #undef LENTIL_LAUNCH_GEN
-    if (!path && compiled) {
+    if (!path && compiled && !spectral) {      // (a spectral call of such a table goes through the interpreter)
       // the kernel specialised for this table at run time (lentil_lens_jit.h), once its code object is there
       if (hipFunction_t fn = jit_rays_function(ctx)) {
         CameraRayArgs args = a;
@@ -4087,7 +4095,8 @@ LENTIL_API int lentil_hip_camera_rays(lentil_hip_ctx *ctx, const lentil_camera_r
       }
     }
     if (!path) {
-      hipLaunchKernelGGL((camera_rays_kernel<LdsLens, true, true>), grid, dim3(kRayBlock), 0, ctx->stream, a);
+      if (spectral) hipLaunchKernelGGL((camera_rays_spectral_kernel<SpectralLens<LdsLens>::Lane, true>), grid, dim3(kRayBlock), 0, ctx->stream, a, lambdas);
+      else hipLaunchKernelGGL((camera_rays_kernel<LdsLens, true, true>), grid, dim3(kRayBlock), 0, ctx->stream, a);
       path = 1;
     }
   } else {
@@ -4100,6 +4109,14 @@ LENTIL_API int lentil_hip_camera_rays(lentil_hip_ctx *ctx, const lentil_camera_r
   HIP_TRY(ctx, hipMemcpy(batch->out, d_out, (size_t)n * kRayOutFloats * sizeof(float), hipMemcpyDeviceToHost));
   if (batch->tries) HIP_TRY(ctx, hipMemcpy(batch->tries, d_tries, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
   return LENTIL_OK;
+}
+
+LENTIL_API int lentil_hip_camera_rays(lentil_hip_ctx *ctx, const lentil_camera_ray_batch *batch) {
+  return camera_rays_call(ctx, batch, nullptr, false);
+}
+
+LENTIL_API int lentil_hip_camera_rays_spectral(lentil_hip_ctx *ctx, const lentil_camera_ray_batch *batch, const double *lambdas) {
+  return camera_rays_call(ctx, batch, lambdas, true);
 }
 
 LENTIL_API int lentil_hip_camera_rays_path(lentil_hip_ctx *ctx, int *path) {
@@ -4133,7 +4150,9 @@ static int lens_dispatch(const lentil_hip_ctx *ctx, bool po, F &&f) {
 }
 
 // ---- scene points traced backward in batches (lentil_trace_points.h) ----------------------------------------------------
-LENTIL_API int lentil_hip_trace_points(lentil_hip_ctx *ctx, const lentil_point_batch *batch) {
+// The scalar and the spectral call: `spectral` takes point j at lambdas[j] (0: params.lambda_bw; polynomial optics -- the thin
+// lens reads no wavelength and runs what the scalar call runs), else every point at batch->lambda.
+static int trace_points_call(lentil_hip_ctx *ctx, const lentil_point_batch *batch, const double *lambdas, bool spectral) {
   CHECK_CTX(ctx);
   if (!batch) return fail(ctx, LENTIL_ERR_INVALID, "batch is null");
   if (!ctx->have_params) return fail(ctx, LENTIL_ERR_INVALID, "set_params first");
@@ -4145,6 +4164,8 @@ LENTIL_API int lentil_hip_trace_points(lentil_hip_ctx *ctx, const lentil_point_b
   if (np >= (1ull << 32) || np * K >= (1ull << 32)) return fail(ctx, LENTIL_ERR_INVALID, "n_points * attempts must be below 2^32");
   if (!np) return LENTIL_OK;
   if (!batch->cs || !batch->pixel || !batch->out_pixel) return fail(ctx, LENTIL_ERR_INVALID, "cs / pixel / out_pixel is null");
+  spectral = spectral && po;
+  if (spectral && !lambdas) return fail(ctx, LENTIL_ERR_INVALID, "lambdas is null");
   const bool device = (batch->flags & LENTIL_POINTS_DEVICE_POINTERS) != 0u;
   // the seeds of a point's tries, first_attempt ... first_attempt + attempts - 1 + retries, must not wrap
   const uint64_t reach = K + (uint64_t)(ctx->P.vignetting_retries > 0 ? ctx->P.vignetting_retries : 0);
@@ -4160,11 +4181,11 @@ LENTIL_API int lentil_hip_trace_points(lentil_hip_ctx *ctx, const lentil_point_b
   a.attempts = (uint32_t)K;
   a.slabs_per_point = (uint32_t)((K + kTpSlab - 1) / kTpSlab);
   a.n_slabs = (uint32_t)(np * a.slabs_per_point);              // <= n_points * attempts < 2^32
-  a.lambda = batch->lambda != 0.0 ? batch->lambda : (double)ctx->P.lambda_bw;
+  a.lambda = (!spectral && batch->lambda != 0.0) ? batch->lambda : (double)ctx->P.lambda_bw;
   TmpFree tf;
   float *d_cs = nullptr;
   uint32_t *d_pixel = nullptr, *d_first = nullptr, *d_out = nullptr;
-  double *d_xy = nullptr, *d_sensor = nullptr;
+  double *d_xy = nullptr, *d_sensor = nullptr, *d_lambdas = nullptr;
   int32_t *d_tries = nullptr;
   if (device) {
     a.cs = batch->cs; a.pixel = batch->pixel; a.first_attempt = batch->first_attempt;
@@ -4174,6 +4195,8 @@ LENTIL_API int lentil_hip_trace_points(lentil_hip_ctx *ctx, const lentil_point_b
     if ((rc = dev_copy_in(ctx, batch->cs, (size_t)np * 3, &d_cs, tf.v))) return rc;
     if ((rc = dev_copy_in(ctx, batch->pixel, (size_t)np, &d_pixel, tf.v))) return rc;
     if ((rc = dev_copy_in(ctx, batch->first_attempt, (size_t)np, &d_first, tf.v))) return rc;
+    if (spectral && (rc = dev_copy_in(ctx, lambdas, (size_t)np, &d_lambdas, tf.v))) return rc;
+    lambdas = d_lambdas;
     if ((rc = dev_alloc(ctx, (size_t)nq, &d_out, tf.v))) return rc;
     if (batch->out_xy && (rc = dev_alloc(ctx, (size_t)nq * 2, &d_xy, tf.v))) return rc;
     if (batch->out_sensor && (rc = dev_alloc(ctx, (size_t)nq * 2, &d_sensor, tf.v))) return rc;
@@ -4186,6 +4209,12 @@ LENTIL_API int lentil_hip_trace_points(lentil_hip_ctx *ctx, const lentil_point_b
   const dim3 grid((unsigned)(want < cap ? want : cap));
   ctx->points_path = lens_dispatch(ctx, po, [&](auto lp) {
     using T = decltype(lp);
+    if constexpr (T::PO) {
+      if (spectral) {
+        hipLaunchKernelGGL((trace_points_spectral_kernel<typename SpectralLens<typename T::LensT>::Wave, T::kTables>), grid, dim3(kTpBlock), 0, ctx->stream, a, lambdas);
+        return;
+      }
+    }
     hipLaunchKernelGGL((trace_points_kernel<typename T::LensT, T::kTables, T::PO>), grid, dim3(kTpBlock), 0, ctx->stream, a);
   });
   HIP_TRY(ctx, hipGetLastError());
@@ -4196,6 +4225,14 @@ LENTIL_API int lentil_hip_trace_points(lentil_hip_ctx *ctx, const lentil_point_b
   if (batch->out_sensor) HIP_TRY(ctx, hipMemcpy(batch->out_sensor, d_sensor, (size_t)nq * 2 * sizeof(double), hipMemcpyDeviceToHost));
   if (batch->out_tries) HIP_TRY(ctx, hipMemcpy(batch->out_tries, d_tries, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost));
   return LENTIL_OK;
+}
+
+LENTIL_API int lentil_hip_trace_points(lentil_hip_ctx *ctx, const lentil_point_batch *batch) {
+  return trace_points_call(ctx, batch, nullptr, false);
+}
+
+LENTIL_API int lentil_hip_trace_points_spectral(lentil_hip_ctx *ctx, const lentil_point_batch *batch, const double *lambdas) {
+  return trace_points_call(ctx, batch, lambdas, true);
 }
 
 LENTIL_API int lentil_hip_trace_points_path(lentil_hip_ctx *ctx, int *path) {

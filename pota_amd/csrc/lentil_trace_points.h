@@ -168,3 +168,57 @@ __global__ __launch_bounds__(kTpBlock) void trace_points_kernel(TracePointArgs a
     }
   }
 }
+
+// lentil_hip_trace_points_spectral: point j at lambdas[j] (0: a.lambda, which the host sets to params.lambda_bw), polynomial
+// optics.  trace_points_kernel's slab loop line for line (a kernel of its own, not a parameter of that one: the scalar call's
+// code stays what it is) with the staging of the wavelength in front.  A wave traces one point at a time, so the wavelength is
+// wave-uniform: every wave keeps the lambda powers of its point in a row of LDS of its own (LensT = LdsLensAt<LambdaTable> or
+// GenLensAt<Gen>; the block shares the header's constants alone) and rewrites the row when its next slab belongs to another
+// point.  The waves of a block make different numbers of trips through the loop, so nothing in it may wait for the block.
+// Nothing has to: the row is the wave's own, written by its lanes 0 ... kMaxExp and read by all of them, and LDS serves a
+// wave's accesses in the order it issues them.  What is needed is that the compiler keeps the reads of the last slab, the
+// writes, and the reads of this slab in that order; the two wave-scope fences say so (DESIGN.md 4.7 has what the loop compiles
+// to).
+template <class LensT, bool kTables>
+__global__ __launch_bounds__(kTpBlock) void trace_points_spectral_kernel(TracePointArgs a, const double *lambdas) {
+  __shared__ DevTerm s_terms[kTables ? kMaxTerms : 1];
+  __shared__ DevLens s_k;
+  __shared__ double s_lp[kTpBlock / 64][kMaxExp + 1];
+  stage_lens<kTables>(a.lens, a.terms, a.lambda, kTpBlock, s_terms, &s_k, threadIdx.x == 0);
+  __syncthreads();
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t waves = gridDim.x * (kTpBlock / 64);
+  LensT L{};
+  if constexpr (kTables) L.terms = s_terms;
+  L.k = &s_k;
+  L.lam.lp = s_lp[wave];
+  uint32_t staged = 0xFFFFFFFFu;      // (no point: n_points < 2^32)
+  // (slab < n_slabs - waves before the step: the sum cannot wrap)
+  for (uint32_t slab = blockIdx.x * (kTpBlock / 64) + wave; slab < a.n_slabs; slab = (a.n_slabs - slab > waves) ? slab + waves : a.n_slabs) {
+    const uint32_t point = slab / a.slabs_per_point;
+    if (point != staged) {            // wave-uniform
+      double lambda = lambdas[point];
+      if (lambda == 0.0) lambda = a.lambda;
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      if (lane <= (uint32_t)kMaxExp) s_lp[wave][lane] = lane == 0u ? 1.0 : ipow_u(lambda, lane);      // (ipow_u(x, 1) is x)
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      staged = point;
+    }
+    const uint32_t k0 = (slab - point * a.slabs_per_point) * kTpSlab;
+    const float cs[3] = {a.cs[(size_t)point * 3], a.cs[(size_t)point * 3 + 1], a.cs[(size_t)point * 3 + 2]};
+    const uint32_t pix = a.pixel[point];
+    const int px = (int)(pix & 0xFFFFu), py = (int)(pix >> 16);
+    const uint32_t attempt = (a.first_attempt ? a.first_attempt[point] : 0u) + k0 + lane;
+    const bool commit = k0 + lane < a.attempts;
+    const uint64_t q = (uint64_t)point * a.attempts + k0 + lane;
+    const AttemptTrace t = trace_attempt<true>(a.P, L, a.bokeh, cs, px, py, attempt, commit, NoSeedAnswers{});
+    if (commit) {
+      a.out_pixel[q] = t.code;
+      if (a.out_xy) { a.out_xy[q * 2] = t.xy0; a.out_xy[q * 2 + 1] = t.xy1; }            // (the caller's arrays are 8-byte aligned, no more)
+      if (a.out_sensor) { a.out_sensor[q * 2] = t.sen0; a.out_sensor[q * 2 + 1] = t.sen1; }
+      if (a.out_tries) a.out_tries[q] = t.tries;
+    }
+  }
+}
