@@ -964,6 +964,27 @@ typedef struct lentil_draw_list {
 } lentil_draw_list;
 int lentil_hip_list_draws(lentil_hip_ctx *ctx, const lentil_draw_list *list);
 int lentil_hip_list_draws_path(lentil_hip_ctx *ctx, int *path);   /* 0 thin lens / none yet, 1 interpreter, 2 compiled-in lens */
+/* lentil_hip_list_draws with a wavelength per visit, for a spectral film: the records of visit v are, bit for bit in visit,
+ * attempt, pixel, tries and xy, those that lentil_hip_list_draws gives for the range [v, v + 1) with
+ * lambda = lambdas[v - first_visit]; *n_draws and *attempts are the sums over the visits.
+ *   lambdas [n_visits]  micrometres; lambdas[i] belongs to visit first_visit + i (the index is relative to the range).  An
+ *                       entry of 0 means params.lambda_bw, as the scalar field does.  Host or device memory as
+ *                       LENTIL_DRAWS_DEVICE_POINTERS says for `out`.  The values are used as given: there is no range check.
+ *                       list->lambda is ignored.
+ * Everything else is the scalar call's: capacity and the counting call, the unspecified order of the records, the independence
+ * of the list as a set from the grid, the capacity and the split into ranges, and lentil_hip_list_draws_path, which reports
+ * this call too.
+ * LENTIL_DRAWS_PROBED, with a host or a device callback: the list of the reference's pass under the probe with each visit at
+ * its own wavelength.  The turns, the answer store, the statistics and the promises about segments are the scalar probed
+ * list's: one segment per (visit, seed) that the walk reaches and that got through the lens, at most once per call.  A
+ * segment does not depend on the wavelength; which seeds get through the lens does.
+ * Thin lens: the wavelengths are ignored as the scalar one is, lambdas may be NULL, the result is the scalar call's.
+ * LENTIL_DRAWS_CHANNELS follows the scalar call: where the plain list serves the mode, the flag changes nothing.  Polynomial
+ * optics with abb_chromatic != 0 are refused here with LENTIL_ERR_UNSUPPORTED and a message, with or without the flag: the
+ * three channels are RGB, each at a wavelength of the mode's own, which a spectral film has no use for.
+ * LENTIL_ERR_INVALID: where lentil_hip_list_draws returns it, and for lambdas NULL with polynomial optics and n_visits > 0.
+ * n_visits == 0 launches nothing. */
+int lentil_hip_list_draws_spectral(lentil_hip_ctx *ctx, const lentil_draw_list *list, const double *lambdas);
 /* The colour channels the draw loop of these parameters traces per attempt (src/lentil_filter.cpp:254-268); needs no context
  * and no GPU.  *n_channels: 3 for polynomial optics with abb_chromatic != 0, else 1 (the thin lens with abb_chromatic > 0
  * picks a channel per attempt from xor128: not described here).  lambda[c]: the channel's wavelength in micrometres, the

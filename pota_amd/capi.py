@@ -33,6 +33,7 @@ EXPORTS = [
     "lentil_hip_trace_points", "lentil_hip_trace_points_path",
     "lentil_hip_camera_rays_spectral", "lentil_hip_trace_points_spectral",
     "lentil_hip_plan_visits", "lentil_hip_list_draws", "lentil_hip_list_draws_path", "lentil_hip_draw_channels",
+    "lentil_hip_list_draws_spectral",
     "lentil_hip_set_xor128_state", "lentil_hip_get_xor128_state", "lentil_hip_tl_chroma_stats", "lentil_hip_test_xor128_jump",
     "lentil_hip_host_alloc", "lentil_hip_host_free", "lentil_hip_visits_begin", "lentil_hip_visits_append",
     "lentil_hip_visits_wait", "lentil_hip_visits_end",
@@ -195,6 +196,7 @@ def load_library():
         "lentil_hip_trace_points_spectral": (i, [vp, C.POINTER(_abi.PointBatch), vp]),
         "lentil_hip_plan_visits": (i, [vp, u64, u64, vp, C.c_uint32, C.POINTER(u64)]),
         "lentil_hip_list_draws": (i, [vp, C.POINTER(_abi.DrawList)]),
+        "lentil_hip_list_draws_spectral": (i, [vp, C.POINTER(_abi.DrawList), vp]),
         "lentil_hip_list_draws_path": (i, [vp, C.POINTER(C.c_int)]),
         "lentil_hip_draw_channels": (i, [C.POINTER(_abi.Params), C.POINTER(u32), C.POINTER(C.c_double), C.POINTER(C.c_float)]),
         "lentil_hip_set_xor128_state": (i, [vp, C.POINTER(C.c_uint32)]),
@@ -312,6 +314,9 @@ def lens_jit_compile(table, compile=True):
     return int(rc), src.value.decode(), log.value.decode(errors="replace"), float(sec.value), int(nb.value)
 
 
+_LAMBDAS_PER = {"camera_rays": "ray", "trace_points": "point", "list_draws": "visit"}
+
+
 def _lambdas_arg(call, lambdas, n, device):
     """The lambdas argument of the spectral calls, checked against the call's other arrays: n entries of float64, and of their
     kind -- device None: they are numpy (host pointers), so lambdas is a numpy float64 array (or a plain sequence); else they
@@ -326,7 +331,7 @@ def _lambdas_arg(call, lambdas, n, device):
             raise ValueError("%s: lambdas must be float64, not %s" % (call, lambdas.dtype))
         lam = np.ascontiguousarray(lambdas, np.float64)
         if lam.shape != (n,):
-            raise ValueError("%s: lambdas must be [%d], one per %s" % (call, n, "ray" if call == "camera_rays" else "point"))
+            raise ValueError("%s: lambdas must be [%d], one per %s" % (call, n, _LAMBDAS_PER[call]))
         return lam, lam.ctypes.data
     import torch
     if not is_tensor:
@@ -338,7 +343,7 @@ def _lambdas_arg(call, lambdas, n, device):
     if not lambdas.is_contiguous():
         raise ValueError("%s: lambdas must be contiguous" % call)
     if tuple(lambdas.shape) != (n,):
-        raise ValueError("%s: lambdas must be [%d], one per %s" % (call, n, "ray" if call == "camera_rays" else "point"))
+        raise ValueError("%s: lambdas must be [%d], one per %s" % (call, n, _LAMBDAS_PER[call]))
     return lambdas, lambdas.data_ptr()
 
 
@@ -667,7 +672,7 @@ class Context:
         self._chk(self.lib.lentil_hip_plan_visits(self.h, first, n, ptr, flags, tot))
         return out, (tuple(int(t) for t in tot) if totals else None)
 
-    def list_draws(self, first=0, n=None, capacity=None, lam=0.0, device=False, probed=False, channels=False):
+    def list_draws(self, first=0, n=None, capacity=None, lam=0.0, device=False, probed=False, channels=False, lambdas=None):
         """The accepted draws of the bound visits first ... first + n - 1 (lentil_hip_list_draws) -> (records, n_draws,
         attempts): records a numpy array of _abi.Draw (visit, attempt, pixel, tries, xy), in no particular order, the first
         min(n_draws, capacity) of it filled and returned; n_draws the accepted draws found (above capacity: ask again with more
@@ -677,15 +682,24 @@ class Context:
         probe -- tries then counts occluded tries too, and the probe's callback is called once per turn, on this thread.
         channels=True (_abi.DRAWS_CHANNELS): the caller reads attempt as n | channel << 30 -- what polynomial optics with
         abb_chromatic != 0 need (up to three records per attempt, a channel's tries / xy / pixel its own); any other mode gives
-        the plain list.  totals[2] does not bound that list, so capacity None then sizes it by a counting call (capacity 0)."""
+        the plain list.  totals[2] does not bound that list, so capacity None then sizes it by a counting call (capacity 0).
+        lambdas: float64 [n], micrometres, 0 = params.lambda_bw -- visit first + i at lambdas[i] instead of every visit at lam
+        (lentil_hip_list_draws_spectral); numpy with device=False, a contiguous tensor on this context's GPU with device=True."""
         first, n = self._visit_range(first, n)
         flags = (_abi.DRAWS_PROBED if probed else 0) | (_abi.DRAWS_CHANNELS if channels else 0)
+        if lambdas is not None:
+            lambdas, lam_ptr = _lambdas_arg("list_draws", lambdas, n, self.device if device else None)
+            call = lambda b: self.lib.lentil_hip_list_draws_spectral(self.h, C.byref(b), lam_ptr if n else None)      # noqa: E731
+        else:
+            call = lambda b: self.lib.lentil_hip_list_draws(self.h, C.byref(b))      # noqa: E731
         if capacity is None and channels and n:
             cnt = C.c_uint64()
             b = _abi.DrawList()
             b.first_visit, b.n_visits, b.capacity, b.lam, b.flags = first, n, 0, float(lam), flags
+            if device and lambdas is not None:      # (no `out` here: the flag says where lambdas lie)
+                b.flags |= _abi.DRAWS_DEVICE_POINTERS
             b.n_draws = C.pointer(cnt)
-            self._chk(self.lib.lentil_hip_list_draws(self.h, C.byref(b)))
+            self._chk(call(b))
             capacity = cnt.value
         elif capacity is None:
             capacity = self.plan_visits(first, n)[1][2] if n else 0
@@ -701,7 +715,7 @@ class Context:
             out = np.empty(capacity, _abi.Draw)
             b.out, b.flags = (out.ctypes.data if capacity else None), 0
         b.flags |= flags
-        self._chk(self.lib.lentil_hip_list_draws(self.h, C.byref(b)))
+        self._chk(call(b))
         if not device:
             out = out[:min(nd.value, capacity)]
         return out, nd.value, att.value

@@ -4287,10 +4287,19 @@ LENTIL_API int lentil_hip_plan_visits(lentil_hip_ctx *ctx, uint64_t first_visit,
   return LENTIL_OK;
 }
 
-// One turn's walk of a probed list, on the lens path the unprobed list takes.
-static int list_probed_launch(lentil_hip_ctx *ctx, dim3 grid, bool po, const ListDrawArgs &a, const ProbeArgs &pr, const ListProbeArgs &b) {
+// One turn's walk of a probed list, on the lens path the unprobed list takes.  lambdas (device memory, polynomial optics):
+// a wavelength per visit of the range; NULL: a.lambda for all of them.
+static int list_probed_launch(lentil_hip_ctx *ctx, dim3 grid, bool po, const ListDrawArgs &a, const ProbeArgs &pr, const ListProbeArgs &b,
+                              const double *lambdas) {
   ctx->draws_path = lens_dispatch(ctx, po, [&](auto lp) {
     using T = decltype(lp);
+    if constexpr (T::PO) {
+      if (lambdas) {
+        hipLaunchKernelGGL((list_draws_probed_spectral_kernel<typename SpectralLens<typename T::LensT>::Wave, T::kTables>), grid, dim3(kLdBlock), 0,
+                           ctx->stream, a, pr, b, lambdas);
+        return;
+      }
+    }
     hipLaunchKernelGGL((list_draws_probed_kernel<typename T::LensT, T::kTables, T::PO>), grid, dim3(kLdBlock), 0, ctx->stream, a, pr, b);
   });
   HIP_TRY(ctx, hipGetLastError());
@@ -4302,7 +4311,9 @@ static int list_probed_launch(lentil_hip_ctx *ctx, dim3 grid, bool po, const Lis
 // (host: segments out, answers in, as probe_ask moves them; device: probe_call_device, nothing else crosses), the apply kernel
 // -- until a turn leaves no visit unsettled.  The turn's buffers are the context's (ld_pb), kept between calls; a turn that
 // wanted more than they hold asks the rest in a later turn, into larger ones.  h: ListDrawArgs::ctr [0..2] at the end.
-static int list_draws_probed(lentil_hip_ctx *ctx, ListDrawArgs &a, dim3 grid, bool po, TmpFree &tf, unsigned long long h[3]) {
+// lambdas: as list_probed_launch takes them.
+static int list_draws_probed(lentil_hip_ctx *ctx, ListDrawArgs &a, dim3 grid, bool po, TmpFree &tf, unsigned long long h[3],
+                             const double *lambdas) {
   hipStream_t st = ctx->stream;
   const uint64_t n_visits = a.v_end - a.v_begin;
   int rc;
@@ -4362,7 +4373,7 @@ static int list_draws_probed(lentil_hip_ctx *ctx, ListDrawArgs &a, dim3 grid, bo
     HIP_TRY(ctx, hipMemsetAsync(pb.count, 0, sizeof(unsigned int), st));
     HIP_TRY(ctx, hipMemsetAsync(a.ctr + 0, 0, sizeof(unsigned long long), st));
     HIP_TRY(ctx, hipMemsetAsync(a.ctr + 3, 0, sizeof(unsigned long long), st));
-    if ((rc = list_probed_launch(ctx, grid, po, a, pr, b))) return rc;
+    if ((rc = list_probed_launch(ctx, grid, po, a, pr, b, lambdas))) return rc;
     hipLaunchKernelGGL(ld_probe_clamp_kernel, dim3(1), dim3(64), 0, st, pb.count, pr.cap, b.x);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(t, a.ctr, sizeof t, hipMemcpyDeviceToHost, st));
@@ -4402,7 +4413,10 @@ static int list_draws_probed(lentil_hip_ctx *ctx, ListDrawArgs &a, dim3 grid, bo
   return LENTIL_OK;
 }
 
-LENTIL_API int lentil_hip_list_draws(lentil_hip_ctx *ctx, const lentil_draw_list *list) {
+// The scalar and the spectral call: `spectral` takes visit first_visit + i at lambdas[i] (0: params.lambda_bw; polynomial optics
+// with abb_chromatic == 0 -- the thin lens reads no wavelength and runs what the scalar call runs), else every visit at
+// list->lambda.
+static int list_draws_call(lentil_hip_ctx *ctx, const lentil_draw_list *list, const double *lambdas, bool spectral) {
   CHECK_CTX(ctx);
   if (!list) return fail(ctx, LENTIL_ERR_INVALID, "list is null");
   if (!list->n_draws) return fail(ctx, LENTIL_ERR_INVALID, "n_draws is null");
@@ -4412,6 +4426,10 @@ LENTIL_API int lentil_hip_list_draws(lentil_hip_ctx *ctx, const lentil_draw_list
   const bool po = ctx->P.cameraType == LENTIL_POLYNOMIAL_OPTICS;
   if (ctx->P.bokeh_enable_image && !ctx->have_bokeh) return fail(ctx, LENTIL_ERR_INVALID, "bokeh_enable_image needs set_bokeh first");
   const bool probed = (list->flags & LENTIL_DRAWS_PROBED) != 0u;
+  spectral = spectral && po;
+  if (spectral && ctx->P.abb_chromatic != 0.0f)
+    return fail(ctx, LENTIL_ERR_UNSUPPORTED, "list_draws_spectral: polynomial optics with abb_chromatic != 0 trace three RGB channels per attempt, each at a "
+                                             "wavelength of the mode's own; the chromatic list has no wavelength per visit");
   // polynomial optics with abb_chromatic != 0: the chromatic list, for a caller who reads the channel bits of `attempt`
   const bool chroma = po && ctx->P.abb_chromatic != 0.0f && (list->flags & LENTIL_DRAWS_CHANNELS) != 0u;
   if (po && ctx->P.abb_chromatic != 0.0f && !chroma)
@@ -4436,17 +4454,25 @@ LENTIL_API int lentil_hip_list_draws(lentil_hip_ctx *ctx, const lentil_draw_list
   *list->n_draws = 0;
   if (list->attempts) *list->attempts = 0;
   if (!list->n_visits) return LENTIL_OK;
+  if (spectral && !lambdas) return fail(ctx, LENTIL_ERR_INVALID, "list_draws_spectral: lambdas is null");
   const bool device = (list->flags & LENTIL_DRAWS_DEVICE_POINTERS) != 0u;
   ListDrawArgs a{};
   a.P = ctx->P; a.V = ctx->V; a.lens_length = ctx->have_lens ? ctx->hlens.length : 0.0;
   a.lens = po ? ctx->d_lens : nullptr; a.terms = po ? ctx->d_terms : nullptr; a.bokeh = ctx->bokeh;
   a.v_begin = list->first_visit; a.v_end = list->first_visit + list->n_visits;
   a.capacity = list->capacity;
-  a.lambda = list->lambda != 0.0 ? list->lambda : (double)ctx->P.lambda_bw;
+  a.lambda = (!spectral && list->lambda != 0.0) ? list->lambda : (double)ctx->P.lambda_bw;
   TmpFree tf;
   lentil_draw *d_out = list->out;
   if (!device && list->capacity && (rc = dev_alloc(ctx, (size_t)list->capacity, &d_out, tf.v))) return rc;
   a.out = d_out;
+  // the wavelengths on the device, or NULL: the scalar kernels
+  double *d_lambdas = nullptr;
+  if (!spectral) lambdas = nullptr;
+  else if (!device) {
+    if ((rc = dev_copy_in(ctx, lambdas, (size_t)list->n_visits, &d_lambdas, tf.v))) return rc;
+    lambdas = d_lambdas;
+  }
   a.ctr = ctx->d_list_ctr + 4;
   HIP_TRY(ctx, hipMemsetAsync(a.ctr, 0, 3 * sizeof(unsigned long long), ctx->stream));
   // a wave takes 64 visits per ticket: no more waves than tickets, no more blocks than the device holds at once
@@ -4455,9 +4481,16 @@ LENTIL_API int lentil_hip_list_draws(lentil_hip_ctx *ctx, const lentil_draw_list
   const dim3 grid((unsigned)(want < cap ? want : cap));
   unsigned long long h[3] = {0, 0, 0};       // ListDrawArgs::ctr [0..2] when the list is complete
   if (probed) {
-    if ((rc = list_draws_probed(ctx, a, grid, po, tf, h))) return rc;
+    if ((rc = list_draws_probed(ctx, a, grid, po, tf, h, lambdas))) return rc;
   } else {
-    if (chroma) {
+    if (lambdas) {
+      ctx->draws_path = lens_dispatch(ctx, po, [&](auto lp) {
+        using T = decltype(lp);
+        if constexpr (T::PO)       // (spectral implies polynomial optics: the thin lens runs the scalar kernel)
+          hipLaunchKernelGGL((list_draws_spectral_kernel<typename SpectralLens<typename T::LensT>::Wave, T::kTables>), grid, dim3(kLdBlock), 0, ctx->stream,
+                             a, lambdas);
+      });
+    } else if (chroma) {
       // the wavelengths are the pass's own (draw_channels_of); abb_chromatic < 0: the caller's lambda for all three, one trace
       ListChromaArgs ch{};
       draw_channels_of(ctx->P, ch.lambda, nullptr);
@@ -4483,6 +4516,14 @@ LENTIL_API int lentil_hip_list_draws(lentil_hip_ctx *ctx, const lentil_draw_list
   const uint64_t written = h[1] < list->capacity ? h[1] : list->capacity;
   if (!device && written) HIP_TRY(ctx, hipMemcpy(list->out, d_out, (size_t)written * sizeof(lentil_draw), hipMemcpyDeviceToHost));
   return LENTIL_OK;
+}
+
+LENTIL_API int lentil_hip_list_draws(lentil_hip_ctx *ctx, const lentil_draw_list *list) {
+  return list_draws_call(ctx, list, nullptr, false);
+}
+
+LENTIL_API int lentil_hip_list_draws_spectral(lentil_hip_ctx *ctx, const lentil_draw_list *list, const double *lambdas) {
+  return list_draws_call(ctx, list, lambdas, true);
 }
 
 LENTIL_API int lentil_hip_list_draws_path(lentil_hip_ctx *ctx, int *path) {
