@@ -761,7 +761,7 @@ int lentil_hip_camera_rays_spectral(lentil_hip_ctx *ctx, const lentil_camera_ray
  * of the redistribution pass puts it -- for a renderer that keeps its own film (another reconstruction filter, a tiled or
  * spectral film, deep output, light-tracing connections) and wants the library's lens, not its frame.  Uses the context's
  * parameters, the table of set_lens (polynomial optics) and the tables of set_bokeh (bokeh_enable_image); needs no frame and
- * no visits, touches no accumulator, and does not consult an occlusion probe.
+ * no visits, touches no accumulator, and does not consult an occlusion probe (lentil_hip_trace_points_probed, below, does).
  * Queries: n_points * attempts of them, point-major: query q is point q / attempts, attempt number
  * first_attempt[point] + q % attempts (the reference's total_samples_taken of that draw).  The draws are seeded as the pass
  * seeds them, tea<8>(px * py + px, attempt + tries) with (px, py) the point's source pixel, so query (point, m) is what the
@@ -792,7 +792,7 @@ int lentil_hip_camera_rays_spectral(lentil_hip_ctx *ctx, const lentil_camera_ray
  * max(vignetting_retries, 0) does not fit 32 bits (checked for host pointers; with device pointers it is the caller's duty:
  * the seeds wrap).  n_points == 0 launches nothing. */
 #define LENTIL_POINTS_DEVICE_POINTERS 1u
-#define LENTIL_POINT_VIGNETTED 0xFFFFFFFFu   /* every try of the attempt failed in the lens */
+#define LENTIL_POINT_VIGNETTED 0xFFFFFFFFu   /* every try of the attempt failed in the lens (the probed call: or at the probe) */
 #define LENTIL_POINT_OUTSIDE   0xFFFFFFFEu   /* got through the lens, landed outside the frame (or NaN) */
 typedef struct lentil_point_batch {
   uint64_t n_points;
@@ -823,6 +823,48 @@ int lentil_hip_trace_points_path(lentil_hip_ctx *ctx, int *path);
  * LENTIL_ERR_INVALID: where lentil_hip_trace_points returns it, and for lambdas NULL with polynomial optics and n_points > 0.
  * n_points == 0 launches nothing.  lentil_hip_trace_points_path reports this call too (0, 1 or 2). */
 int lentil_hip_trace_points_spectral(lentil_hip_ctx *ctx, const lentil_point_batch *batch, const double *lambdas);
+/* lentil_hip_trace_points under the context's occlusion probe (lentil_hip_set_occlusion_probe or _device): query (point, m) is
+ * Camera::trace_ray_bw_po as the reference runs it in a scene -- vignetting_retries + 1 tries at seeds m + tries, and a try
+ * whose segment, from `origin` to camera_to_world * (-aperture * 0.1 / unit), is occluded fails like one the lens vignettes
+ * (src/lentil.h:613-629) -- then the sensor -> pixel mapping.  Thin lens: one try per attempt, the segment goes to
+ * camera_to_world * (lens / unit), an occluded attempt is lost (src/lentil_filter.cpp:356-375).  A caller cannot do this with
+ * the unprobed call: no call hands out the aperture point, and an occluded try hands the attempt on to the next seed, which
+ * lands elsewhere.  The answers agree with the pass and with lentil_hip_list_draws(LENTIL_DRAWS_PROBED) for a visit of that
+ * position, source pixel and time.
+ *   Outputs: lentil_point_batch's.  out_tries counts occluded tries too; LENTIL_POINT_VIGNETTED reads "every try failed, in the
+ *   lens or at the probe"; out_xy and out_sensor are those of the try that got through.  For a query that no occluded seed
+ *   touches every output is the unprobed call's, bit for bit; with `exempt` set for every point the whole batch is, and the
+ *   callback is never called.
+ *   What is asked: only seeds that got through the lens, each (point, seed) at most once per call, and exactly these: (point,
+ *   s) is asked if and only if the batch has a query m with m <= s <= m + retries whose seeds in [m, s) all fail, in the lens
+ *   or at the probe, and s gets through the lens.  The segments are bit for bit what the probed list writes for a visit with
+ *   that position, source pixel and time (camera_to_world: the one given to the setter, or the fp64 inverse; motion keys
+ *   blended and clamped at `time` as the pass blends them).
+ *   Turns: the batch is traced in turns; every open query asks about its next seed in every turn, so while a turn's list fits
+ *   the buffers the callback is called at most max(vignetting_retries, 0) + 1 times (thin lens: once), on the calling thread,
+ *   never with an empty list.  lentil_hip_probe_stats and lentil_hip_probe_device_stats grow as for the probed list.
+ *   With LENTIL_POINTS_DEVICE_POINTERS every pointer of the batch and of lentil_point_probe is device memory; the call still
+ *   returns only when the outputs are final (it waits once per turn).  With lambdas (polynomial optics) point j is traced at
+ *   lambdas[j] as lentil_hip_trace_points_spectral traces it and batch->lambda is ignored; the thin lens ignores them.
+ * Observes the context like the scalar call; takes no part in the streamed passes' turns; leaves frame, visits, xor128 state
+ * and pass counters alone.  lentil_hip_trace_points_path reports this call too.  The thin lens with abb_chromatic > 0 is
+ * projected as lentil_hip_trace_points projects it.
+ * LENTIL_ERR_INVALID: where lentil_hip_trace_points returns it; no occlusion probe set; probe or probe->origin NULL with
+ * n_points > 0; a device callback that returns non-zero (the context stays usable).  LENTIL_ERR_UNSUPPORTED: polynomial
+ * optics with abb_chromatic != 0 (the pass and the probed list refuse the pair too).  LENTIL_ERR_NOMEM: an answer store (two
+ * bits per seed offset 0 ... attempts + max(vignetting_retries, 0) - 1 of every point) of 2^27 words or more per array, or
+ * one that does not fit: split the batch.  n_points == 0 launches nothing. */
+typedef struct lentil_point_probe {
+  const float   *origin;   /* [n_points][3] world space: the segment's origin, the sample's world position as the renderer holds
+                              it (what the visit stream carries in pos_z.xyz).  Required. */
+  const float   *time;     /* optional [n_points]: the sample's time, for lentil_hip_set_camera_motion's keys (blended and clamped
+                              as the pass blends them); NULL: 0 for every point */
+  const uint8_t *exempt;   /* optional [n_points]: non-zero = the skydome supplied the sample (src/lentil_filter.cpp:119-133):
+                              nothing of it is occluded, nothing of it is asked */
+  const double  *lambdas;  /* optional [n_points], polynomial optics: a wavelength per point, 0 = params.lambda_bw, as
+                              lentil_hip_trace_points_spectral takes them; NULL: batch->lambda for all */
+} lentil_point_probe;
+int lentil_hip_trace_points_probed(lentil_hip_ctx *ctx, const lentil_point_batch *batch, const lentil_point_probe *probe);
 
 /* --- a visit range's plan and its accepted draws, for a renderer with its own film ---------------
  * lentil_hip_trace_points answers where attempt m of a point lands.  These two calls answer what the pass makes of the

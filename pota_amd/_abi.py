@@ -128,6 +128,10 @@ class PointBatch(C.Structure):
                 ("out_pixel", C.c_void_p), ("out_xy", C.c_void_p), ("out_sensor", C.c_void_p), ("out_tries", C.c_void_p)]
 
 
+class PointProbe(C.Structure):
+    _fields_ = [("origin", C.c_void_p), ("time", C.c_void_p), ("exempt", C.c_void_p), ("lambdas", C.c_void_p)]
+
+
 class DrawList(C.Structure):
     _fields_ = [("first_visit", C.c_uint64), ("n_visits", C.c_uint64), ("flags", C.c_uint32), ("capacity", C.c_uint64),
                 ("out", C.c_void_p), ("lam", C.c_double), ("n_draws", C.POINTER(C.c_uint64)), ("attempts", C.POINTER(C.c_uint64))]

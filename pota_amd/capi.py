@@ -33,7 +33,7 @@ EXPORTS = [
     "lentil_hip_trace_points", "lentil_hip_trace_points_path",
     "lentil_hip_camera_rays_spectral", "lentil_hip_trace_points_spectral",
     "lentil_hip_plan_visits", "lentil_hip_list_draws", "lentil_hip_list_draws_path", "lentil_hip_draw_channels",
-    "lentil_hip_list_draws_spectral",
+    "lentil_hip_list_draws_spectral", "lentil_hip_trace_points_probed",
     "lentil_hip_set_xor128_state", "lentil_hip_get_xor128_state", "lentil_hip_tl_chroma_stats", "lentil_hip_test_xor128_jump",
     "lentil_hip_host_alloc", "lentil_hip_host_free", "lentil_hip_visits_begin", "lentil_hip_visits_append",
     "lentil_hip_visits_wait", "lentil_hip_visits_end",
@@ -194,6 +194,7 @@ def load_library():
         "lentil_hip_trace_points_path": (i, [vp, C.POINTER(C.c_int)]),
         "lentil_hip_camera_rays_spectral": (i, [vp, C.POINTER(_abi.CameraRayBatch), vp]),
         "lentil_hip_trace_points_spectral": (i, [vp, C.POINTER(_abi.PointBatch), vp]),
+        "lentil_hip_trace_points_probed": (i, [vp, C.POINTER(_abi.PointBatch), C.POINTER(_abi.PointProbe)]),
         "lentil_hip_plan_visits": (i, [vp, u64, u64, vp, C.c_uint32, C.POINTER(u64)]),
         "lentil_hip_list_draws": (i, [vp, C.POINTER(_abi.DrawList)]),
         "lentil_hip_list_draws_spectral": (i, [vp, C.POINTER(_abi.DrawList), vp]),
@@ -642,6 +643,93 @@ class Context:
         path = C.c_int()
         self._chk(self.lib.lentil_hip_trace_points_path(self.h, C.byref(path)))
         return path.value
+
+    def trace_points_probed(self, cs, pixel, attempts, origin, first_attempt=None, time=None, exempt=None, lam=0.0, lambdas=None,
+                            want_xy=True, want_sensor=False, want_tries=True):
+        """trace_points under the context's occlusion probe (lentil_hip_trace_points_probed): a try whose segment from
+        origin[point] (float32 [n, 3], world space) to the try's aperture point is occluded fails like one the lens vignettes.
+        time: float32 [n], the samples' times (None: 0); exempt: uint8 [n], non-zero = supplied by the skydome, never occluded
+        and never asked about (None: no point); lambdas: float64 [n], a wavelength per point (None: lam for all).  The other
+        arguments and the dict that comes back are trace_points'.  numpy arrays: host pointers; contiguous torch tensors on
+        this context's device: device pointers, torch tensors out (the caller orders the inputs before the context's stream, as
+        for trace_points) -- either way the outputs are final on return.  Every array is of cs's kind; ValueError before any
+        call otherwise."""
+        b, pp = _abi.PointBatch(), _abi.PointProbe()
+        attempts = int(attempts)
+        extra = (("origin", origin), ("time", time), ("exempt", exempt))
+        if isinstance(cs, np.ndarray) or not hasattr(cs, "data_ptr"):
+            for name, t in (("pixel", pixel), ("first_attempt", first_attempt)) + extra:
+                if hasattr(t, "data_ptr") and not isinstance(t, np.ndarray):
+                    raise ValueError("trace_points_probed: %s is a tensor, cs is not" % name)
+            if origin is None:
+                raise ValueError("trace_points_probed: origin is required")
+            a = np.ascontiguousarray(cs, np.float32)
+            if a.ndim != 2 or a.shape[1] != 3:
+                raise ValueError("trace_points_probed: cs must be [n, 3]")
+            n = a.shape[0]
+            px = np.ascontiguousarray(pixel, np.uint32)
+            fa = None if first_attempt is None else np.ascontiguousarray(first_attempt, np.uint32)
+            if px.shape != (n,) or (fa is not None and fa.shape != (n,)):
+                raise ValueError("trace_points_probed: pixel and first_attempt must be [n]")
+            org = np.ascontiguousarray(origin, np.float32)
+            if org.shape != (n, 3):
+                raise ValueError("trace_points_probed: origin must be [n, 3]")
+            tm = None if time is None else np.ascontiguousarray(time, np.float32)
+            ex = None if exempt is None else np.ascontiguousarray(exempt, np.uint8)
+            if (tm is not None and tm.shape != (n,)) or (ex is not None and ex.shape != (n,)):
+                raise ValueError("trace_points_probed: time and exempt must be [n]")
+            k = max(attempts, 0)
+            out = {"pixel": np.empty((n, k), np.uint32)}
+            if want_xy:
+                out["xy"] = np.empty((n, k, 2), np.float64)
+            if want_sensor:
+                out["sensor"] = np.empty((n, k, 2), np.float64)
+            if want_tries:
+                out["tries"] = np.empty((n, k), np.int32)
+            ptr = lambda t: None if t is None else t.ctypes.data      # noqa: E731
+            flags, kind = 0, None
+        else:
+            import torch
+            if cs.dtype != torch.float32 or cs.dim() != 2 or cs.shape[1] != 3:
+                raise ValueError("trace_points_probed: cs must be a float32 [n, 3] tensor")
+            n = cs.shape[0]
+            if origin is None:
+                raise ValueError("trace_points_probed: origin is required")
+            a, px, fa, org, tm, ex = cs, pixel, first_attempt, origin, time, exempt
+            ints = (torch.int32, getattr(torch, "uint32", torch.int32))
+            want = {"cs": ((torch.float32,), (n, 3)), "pixel": (ints, (n,)), "first_attempt": (ints, (n,)), "origin": ((torch.float32,), (n, 3)),
+                    "time": ((torch.float32,), (n,)), "exempt": ((torch.uint8,), (n,))}
+            for name, t in (("cs", a), ("pixel", px), ("first_attempt", fa)) + extra:
+                if t is None:
+                    continue
+                if not hasattr(t, "data_ptr") or isinstance(t, np.ndarray):
+                    raise ValueError("trace_points_probed: %s is not a tensor, cs is" % name)
+                if not t.is_cuda or t.device.index != self.device:
+                    raise ValueError("trace_points_probed: %s is on %s, the context on GPU %d" % (name, t.device, self.device))
+                if not t.is_contiguous():      # (a copy here would run on torch's stream, unordered with the context's)
+                    raise ValueError("trace_points_probed: %s must be contiguous" % name)
+                if t.dtype not in want[name][0] or tuple(t.shape) != want[name][1]:
+                    raise ValueError("trace_points_probed: %s must be a %s %s tensor" % (name, want[name][0][0], list(want[name][1])))
+            k = max(attempts, 0)
+            out = {"pixel": torch.empty((n, k), dtype=torch.int32, device=a.device)}      # (the bits of a uint32)
+            if want_xy:
+                out["xy"] = torch.empty((n, k, 2), dtype=torch.float64, device=a.device)
+            if want_sensor:
+                out["sensor"] = torch.empty((n, k, 2), dtype=torch.float64, device=a.device)
+            if want_tries:
+                out["tries"] = torch.empty((n, k), dtype=torch.int32, device=a.device)
+            ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+            flags, kind = _abi.POINTS_DEVICE_POINTERS, self.device
+        lam_ptr = None
+        if lambdas is not None:
+            lambdas, lam_ptr = _lambdas_arg("trace_points", lambdas, n, kind)
+        b.n_points, b.attempts, b.flags, b.lam = n, attempts & 0xFFFFFFFF, flags, float(lam)
+        if n:
+            b.cs, b.pixel, b.first_attempt = ptr(a), ptr(px), ptr(fa)
+            b.out_pixel, b.out_xy, b.out_sensor, b.out_tries = (ptr(out.get(key)) for key in ("pixel", "xy", "sensor", "tries"))
+            pp.origin, pp.time, pp.exempt, pp.lambdas = ptr(org), ptr(tm), ptr(ex), lam_ptr
+        self._chk(self.lib.lentil_hip_trace_points_probed(self.h, C.byref(b), C.byref(pp)))
+        return out
 
     def _visit_range(self, first, n):
         first = int(first)

@@ -381,6 +381,7 @@ struct lentil_hip_ctx {
   lentil_probe_device_fn probe_dev_fn = nullptr;
   uint64_t n_dev_lists = 0, n_dev_waits = 0, n_dev_overflows = 0, dev_longest = 0;
   uint64_t probe_dev_cap = 0;                 // LENTIL_PROBE_DEVICE_CAP: a blind pass's list capacity at most (0: no cap; tests)
+  uint64_t points_probe_cap = 0;              // LENTIL_POINTS_PROBE_CAP: the first buffers of a probed trace_points call at most (0: no cap; tests)
   struct LentilUpload *upload = nullptr;   // lentil_upload.h: the visit stream handed over piece by piece
   struct LentilComm *comm = nullptr; // lentil_comm.h: this context's RCCL communicator, if one was asked for
   struct LentilCrypto *crypto = nullptr;   // lentil_crypto.h: cryptomatte AOVs, if any were allocated
@@ -655,6 +656,7 @@ LENTIL_API int lentil_hip_create(int device, lentil_hip_ctx **out_ctx) {
   { const int rc = pick_concurrent_streams(ctx); if (rc) return rc; }
   if (const char *e = getenv("LENTIL_INJECT_STALL")) ctx->inject_stall_at = atoi(e);
   if (const char *e = getenv("LENTIL_PROBE_DEVICE_CAP")) { const long long v = atoll(e); ctx->probe_dev_cap = v > 0 ? (uint64_t)v : 0; }
+  if (const char *e = getenv("LENTIL_POINTS_PROBE_CAP")) { const long long v = atoll(e); ctx->points_probe_cap = v > 0 ? (uint64_t)v : 0; }
   if (const char *ft = getenv("LENTIL_FORCE_TABLES")) ctx->use_generated = !(ft[0] == '1');
   if (const char *fc = getenv("LENTIL_FIRST_CHUNK_FRAC")) {
     const double f = atof(fc);
@@ -4524,6 +4526,190 @@ LENTIL_API int lentil_hip_list_draws(lentil_hip_ctx *ctx, const lentil_draw_list
 
 LENTIL_API int lentil_hip_list_draws_spectral(lentil_hip_ctx *ctx, const lentil_draw_list *list, const double *lambdas) {
   return list_draws_call(ctx, list, lambdas, true);
+}
+
+// ---- scene points traced backward under the occlusion probe (lentil_trace_points.h: trace_points_probed_kernel) ---------------
+// The validation of trace_points_call and the probe's own, the inputs on the device, the answer store allocated and zeroed,
+// then the turns, shaped like list_draws_probed's: counter reset, the kernel, the clamp, the turn's length and the unsettled
+// slabs read back in one wait, the callback on this thread (host: segments out, answers in; device: probe_call_device), the
+// apply kernel -- until a turn leaves no slab unsettled.  The buffers are the probed list's (ld_pb), kept between calls; a turn
+// that wanted more than they hold asks the rest in a later turn, into larger ones.  LENTIL_POINTS_PROBE_CAP caps the first
+// turn's capacity (tests: the growth).
+static int trace_points_probed_call(lentil_hip_ctx *ctx, const lentil_point_batch *batch, const lentil_point_probe *probe) {
+  CHECK_CTX(ctx);
+  if (!batch) return fail(ctx, LENTIL_ERR_INVALID, "batch is null");
+  if (!ctx->have_params) return fail(ctx, LENTIL_ERR_INVALID, "set_params first");
+  const bool po = ctx->P.cameraType == LENTIL_POLYNOMIAL_OPTICS;
+  if (po && !ctx->have_lens) return fail(ctx, LENTIL_ERR_INVALID, "a polynomial-optics camera needs set_lens first");
+  if (ctx->P.bokeh_enable_image && !ctx->have_bokeh) return fail(ctx, LENTIL_ERR_INVALID, "bokeh_enable_image needs set_bokeh first");
+  if (!batch->attempts) return fail(ctx, LENTIL_ERR_INVALID, "attempts is 0");
+  const uint64_t np = batch->n_points, K = batch->attempts;
+  if (np >= (1ull << 32) || np * K >= (1ull << 32)) return fail(ctx, LENTIL_ERR_INVALID, "n_points * attempts must be below 2^32");
+  if (!probing(ctx))
+    return fail(ctx, LENTIL_ERR_INVALID, "trace_points_probed needs an occlusion probe (set_occlusion_probe or set_occlusion_probe_device)");
+  if (po && ctx->P.abb_chromatic != 0.0f)
+    return fail(ctx, LENTIL_ERR_UNSUPPORTED, "trace_points_probed: polynomial optics with abb_chromatic != 0 (every channel's tries under the probe) "
+                                             "is not built; the pass and the probed list refuse the pair too");
+  if (!np) return LENTIL_OK;
+  if (!batch->cs || !batch->pixel || !batch->out_pixel) return fail(ctx, LENTIL_ERR_INVALID, "cs / pixel / out_pixel is null");
+  if (!probe || !probe->origin) return fail(ctx, LENTIL_ERR_INVALID, "trace_points_probed: probe / probe->origin is null");
+  const bool spectral = po && probe->lambdas != nullptr;
+  const bool device = (batch->flags & LENTIL_POINTS_DEVICE_POINTERS) != 0u;
+  // the seeds of a point's tries, first_attempt ... first_attempt + attempts - 1 + retries, must not wrap
+  const uint64_t retries = po && ctx->P.vignetting_retries > 0 ? (uint64_t)ctx->P.vignetting_retries : 0ull;
+  const uint64_t reach = K + (uint64_t)(ctx->P.vignetting_retries > 0 ? ctx->P.vignetting_retries : 0);
+  if (reach >= (1ull << 32)) return fail(ctx, LENTIL_ERR_INVALID, "attempts + vignetting_retries does not fit 32 bits");
+  if (!device && batch->first_attempt)
+    for (uint64_t i = 0; i < np; ++i)
+      if ((uint64_t)batch->first_attempt[i] + reach >= (1ull << 32))
+        return fail(ctx, LENTIL_ERR_INVALID, "first_attempt + attempts + vignetting_retries of point " + std::to_string(i) + " does not fit 32 bits");
+  // the store: two arrays of `words` 32-bit words; a seed's place in it is a 32-bit bit index
+  const uint64_t seeds = K + retries, wpp = (seeds + 31u) / 32u, words = np * wpp;
+  const std::string split = "trace_points_probed: the answer store of this batch (" + std::to_string(words * 8u) + " bytes) does not fit; split the batch";
+  if (words >= (1ull << 27)) return fail(ctx, LENTIL_ERR_NOMEM, split);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  if (!ctx->d_list_ctr) HIP_TRY(ctx, hipMalloc(&ctx->d_list_ctr, 16 * sizeof(unsigned long long)));
+  const uint64_t nq = np * K;
+  TracePointArgs a{};
+  a.P = ctx->P; a.lens = po ? ctx->d_lens : nullptr; a.terms = po ? ctx->d_terms : nullptr; a.bokeh = ctx->bokeh;
+  a.attempts = (uint32_t)K;
+  a.slabs_per_point = (uint32_t)((K + kTpSlab - 1) / kTpSlab);
+  a.n_slabs = (uint32_t)(np * a.slabs_per_point);              // <= n_points * attempts < 2^32
+  a.lambda = (!spectral && batch->lambda != 0.0) ? batch->lambda : (double)ctx->P.lambda_bw;
+  TracePointProbeArgs b{};
+  b.cam = CamMotion{ctx->n_cam_keys >= 2 ? ctx->d_cam_keys : nullptr, ctx->n_cam_keys >= 2 ? ctx->n_cam_keys : 0u, ctx->shutter_t0, ctx->shutter_inv_dt};
+  b.words_per_point = (uint32_t)wpp;
+  b.unsettled = ctx->d_list_ctr + 7;
+  ListProbeArgs lb{};                                          // what ld_probe_apply_kernel and ld_probe_clamp_kernel take
+  lb.x = ctx->d_list_ctr + 8;
+  int rc;
+  ProbeArgs pr{};
+  if ((rc = probe_prepare(ctx, pr, st))) return rc;
+  TmpFree tf;
+  float *d_cs = nullptr, *d_origin = nullptr, *d_time = nullptr;
+  uint8_t *d_exempt = nullptr;
+  uint32_t *d_pixel = nullptr, *d_first = nullptr, *d_out = nullptr;
+  double *d_xy = nullptr, *d_sensor = nullptr, *d_lambdas = nullptr;
+  int32_t *d_tries = nullptr;
+  const double *lambdas = spectral ? probe->lambdas : nullptr;
+  if (device) {
+    a.cs = batch->cs; a.pixel = batch->pixel; a.first_attempt = batch->first_attempt;
+    a.out_pixel = batch->out_pixel; a.out_xy = batch->out_xy; a.out_sensor = batch->out_sensor; a.out_tries = batch->out_tries;
+    b.origin = probe->origin; b.time = probe->time; b.exempt = probe->exempt;
+  } else {
+    if ((rc = dev_copy_in(ctx, batch->cs, (size_t)np * 3, &d_cs, tf.v))) return rc;
+    if ((rc = dev_copy_in(ctx, batch->pixel, (size_t)np, &d_pixel, tf.v))) return rc;
+    if ((rc = dev_copy_in(ctx, batch->first_attempt, (size_t)np, &d_first, tf.v))) return rc;
+    if ((rc = dev_copy_in(ctx, probe->origin, (size_t)np * 3, &d_origin, tf.v))) return rc;
+    if ((rc = dev_copy_in(ctx, probe->time, (size_t)np, &d_time, tf.v))) return rc;
+    if ((rc = dev_copy_in(ctx, probe->exempt, (size_t)np, &d_exempt, tf.v))) return rc;
+    if (spectral && (rc = dev_copy_in(ctx, lambdas, (size_t)np, &d_lambdas, tf.v))) return rc;
+    lambdas = d_lambdas;
+    if ((rc = dev_alloc(ctx, (size_t)nq, &d_out, tf.v))) return rc;
+    if (batch->out_xy && (rc = dev_alloc(ctx, (size_t)nq * 2, &d_xy, tf.v))) return rc;
+    if (batch->out_sensor && (rc = dev_alloc(ctx, (size_t)nq * 2, &d_sensor, tf.v))) return rc;
+    if (batch->out_tries && (rc = dev_alloc(ctx, (size_t)nq, &d_tries, tf.v))) return rc;
+    a.cs = d_cs; a.pixel = d_pixel; a.first_attempt = d_first;
+    a.out_pixel = d_out; a.out_xy = d_xy; a.out_sensor = d_sensor; a.out_tries = d_tries;
+    b.origin = d_origin; b.time = d_time; b.exempt = d_exempt;
+  }
+  {
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
+    if (words * 8u + a.n_slabs > free_b / 2u) return fail(ctx, LENTIL_ERR_NOMEM, split);
+    uint32_t *store = nullptr;
+    if (hipMalloc((void **)&store, (size_t)words * 8u + a.n_slabs) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, LENTIL_ERR_NOMEM, split); }
+    tf.v.push_back(store);
+    b.A = store; b.B = store + words;
+    b.settled = reinterpret_cast<uint8_t *>(store + 2u * words);       // a byte per slab behind the two arrays
+    lb.A = b.A; lb.B = b.B;
+    HIP_TRY(ctx, hipMemsetAsync(store, 0, (size_t)words * 8u + a.n_slabs, st));
+  }
+  HIP_TRY(ctx, hipMemsetAsync(ctx->d_list_ctr + 7, 0, 5 * sizeof(unsigned long long), st));      // (unsettled and ListProbeArgs::x)
+  ProbeBuf &pb = ctx->ld_pb;
+  const bool host = ctx->probe_fn != nullptr;
+  constexpr uint64_t kFirstMost = 1ull << 22, kMost = 1ull << 24;
+  const uint64_t all_seeds = np * seeds;
+  uint64_t want_cap = all_seeds < 4096u ? 4096u : (all_seeds > kFirstMost ? kFirstMost : all_seeds);
+  if (ctx->points_probe_cap) { if (want_cap > ctx->points_probe_cap) want_cap = ctx->points_probe_cap; }
+  else if (want_cap < pb.cap) want_cap = pb.cap;
+  // a slab that is not settled has an open query; every turn answers what it asks, or hands it to a later turn because the
+  // buffers were full -- and then a buffer's worth of the store's seeds has been retired
+  const uint64_t max_turns = retries + 2u + 64u + all_seeds / 64u;
+  // a slab per wave, four waves per block; no more blocks than the device holds at once (eight waves per SIMD at the most)
+  const uint64_t want = ((uint64_t)a.n_slabs + kTpBlock / 64 - 1) / (kTpBlock / 64), most = (uint64_t)ctx->num_cu * 8u;
+  const dim3 grid((unsigned)(want < most ? want : most));
+  const dim3 pgrid((unsigned)ctx->num_cu * 4u), pblock(256);
+  unsigned long long t[5] = {0, 0, 0, 0, 0};
+  for (uint64_t turn = 0;; ++turn) {
+    if (turn >= max_turns) return fail(ctx, LENTIL_ERR_INVALID, "trace_points_probed: the turns did not end (internal)");
+    if (pb.cap < want_cap || (host && pb.h_cap < want_cap) || !pb.count) {
+      HIP_TRY(ctx, hipStreamSynchronize(st));       // (the last turn's apply kernel reads the buffers that go)
+      if ((rc = probe_buf_reserve(ctx, pb, want_cap, host))) return rc;
+    }
+    const uint64_t cap = want_cap < 64u ? 64u : want_cap;      // (at most pb.cap: probe_buf_reserve's floor)
+    if (pb.occ_dirty) { HIP_TRY(ctx, hipMemsetAsync(pb.occ, 0, pb.cap, st)); pb.occ_dirty = false; }
+    probe_bind(pb, cap, pr);
+    HIP_TRY(ctx, hipMemsetAsync(pb.count, 0, sizeof(unsigned int), st));
+    HIP_TRY(ctx, hipMemsetAsync(b.unsettled, 0, sizeof(unsigned long long), st));
+    ctx->points_path = lens_dispatch(ctx, po, [&](auto lp) {
+      using T = decltype(lp);
+      if constexpr (T::PO) {
+        if (spectral) {
+          hipLaunchKernelGGL((trace_points_probed_spectral_kernel<typename SpectralLens<typename T::LensT>::Wave, T::kTables>), grid, dim3(kTpBlock), 0, st,
+                             a, pr, b, lambdas);
+          return;
+        }
+      }
+      hipLaunchKernelGGL((trace_points_probed_kernel<typename T::LensT, T::kTables, T::PO>), grid, dim3(kTpBlock), 0, st, a, pr, b);
+    });
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(ld_probe_clamp_kernel, dim3(1), dim3(64), 0, st, pb.count, pr.cap, lb.x);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(t, ctx->d_list_ctr + 7, sizeof t, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (!host) ++ctx->n_dev_waits;
+    const uint64_t raw = t[4], unsettled = t[0];
+    const uint64_t n = raw < cap ? raw : cap;
+    if (n) {
+      if (host) {
+        HIP_TRY(ctx, hipMemcpyAsync(pb.h_seg, pb.seg, (size_t)n * sizeof(lentil_probe_segment), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        memset(pb.h_occ, 0, (size_t)n);
+        ctx->probe_fn(ctx->probe_user, n, pb.h_seg, pb.h_occ);
+        uint64_t occ = 0;
+        for (uint64_t i = 0; i < n; ++i) occ += pb.h_occ[i] ? 1u : 0u;
+        ctx->n_probes += n; ctx->n_probes_occluded += occ; ++ctx->n_probe_calls;
+        if (occ) HIP_TRY(ctx, hipMemcpyAsync(pb.occ, pb.h_occ, (size_t)n, hipMemcpyHostToDevice, st));
+      } else {
+        if ((rc = probe_call_device(ctx, pb, cap, st))) { pb.occ_dirty = true; return rc; }
+        ctx->n_probes += n;
+        if (n > ctx->dev_longest) ctx->dev_longest = n;
+      }
+      hipLaunchKernelGGL(ld_probe_apply_kernel, pgrid, pblock, 0, st, lb, (const uint32_t *)pb.idx, pb.occ, (const unsigned int *)pb.count, pr.cap);
+      HIP_TRY(ctx, hipGetLastError());
+    }
+    if (!unsettled) break;
+    if (!n) return fail(ctx, LENTIL_ERR_INVALID, "trace_points_probed: a turn left queries open and asked nothing (internal)");
+    if (raw > cap) want_cap = raw * 2u > kMost ? (cap > kMost ? cap : kMost) : raw * 2u;
+  }
+  HIP_TRY(ctx, hipStreamSynchronize(st));       // (the last apply, and the host form's upload from the pinned answers)
+  if (!host) {
+    unsigned long long occ = 0;
+    HIP_TRY(ctx, hipMemcpy(&occ, lb.x + 2, sizeof occ, hipMemcpyDeviceToHost));
+    ctx->n_probes_occluded += occ;
+  }
+  if (device) return LENTIL_OK;
+  HIP_TRY(ctx, hipMemcpy(batch->out_pixel, d_out, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (batch->out_xy) HIP_TRY(ctx, hipMemcpy(batch->out_xy, d_xy, (size_t)nq * 2 * sizeof(double), hipMemcpyDeviceToHost));
+  if (batch->out_sensor) HIP_TRY(ctx, hipMemcpy(batch->out_sensor, d_sensor, (size_t)nq * 2 * sizeof(double), hipMemcpyDeviceToHost));
+  if (batch->out_tries) HIP_TRY(ctx, hipMemcpy(batch->out_tries, d_tries, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return LENTIL_OK;
+}
+
+LENTIL_API int lentil_hip_trace_points_probed(lentil_hip_ctx *ctx, const lentil_point_batch *batch, const lentil_point_probe *probe) {
+  return trace_points_probed_call(ctx, batch, probe);
 }
 
 LENTIL_API int lentil_hip_list_draws_path(lentil_hip_ctx *ctx, int *path) {

@@ -2,7 +2,8 @@
 // camera-space point and an attempt number, where on the sensor a draw of the redistribution pass would put it --
 // Camera::trace_ray_bw_po (src/lentil.h:573-661) and the sensor -> pixel mapping of src/lentil_filter.cpp:271-290 for
 // polynomial optics, the thin-lens draw of src/lentil_filter.cpp:311-434 (abb_chromatic == 0) for the thin lens.  The
-// backward counterpart of lentil_camera_rays.h: no frame, no visits, no accumulators, no probes.
+// backward counterpart of lentil_camera_rays.h: no frame, no visits, no accumulators; an occlusion probe only in the probed
+// call (lentil_hip_trace_points_probed, at the end of this file).
 //
 // Mapping.  A query is (point, attempt); a point's K attempts are consecutive.  A wave takes one slab -- one point and 64
 // consecutive attempts of it -- so the point's position, source pixel and first attempt are wave-uniform (read once, through
@@ -221,4 +222,182 @@ __global__ __launch_bounds__(kTpBlock) void trace_points_spectral_kernel(TracePo
       if (a.out_tries) a.out_tries[q] = t.tries;
     }
   }
+}
+
+// ---------------------------------------------------------------------------------------
+// lentil_hip_trace_points_probed: the batch under the context's occlusion probe.  Query (point, m) makes its tries at seeds
+// m + tries, and a try whose segment -- from the point's world position to the try's aperture point -- is occluded fails like
+// one the lens vignettes (thin lens: the attempt is lost).  Which seeds a query reaches depends on the answers, so the batch is
+// traced in turns (lentil_hip.hip: trace_points_probed_call).
+//
+// The answer store.  Two bits per seed offset 0 ... attempts + max(vignetting_retries, 0) - 1 of every point, in the probed
+// list's encoding (lentil_list_draws.h: (A, B) = (0, 0) never asked about, (1, 0) asked in this turn, (1, 1) clear, (0, 1)
+// occluded), so that ld_probe_apply_kernel serves unchanged.  Every point has the same number of words; point j's begin at
+// j * words_per_point.  A seed's offset is m - first_attempt[point], subtracted on the seed itself.
+//
+// One turn.  trace_points_kernel's slab loop over the slabs that are not settled, trace_attempt with the store's answers.  A
+// lane whose trace comes back `open` -- it got through the lens at a seed whose answer is not known -- asks about that seed:
+// an atomicOr on the A bit elects one lister per (point, seed), across the lanes of a slab, the waves that hold neighbouring
+// slabs of a point, and the blocks; the elected lanes take slots by probe_wave_slot, and one whose slot lies beyond the
+// turn's buffers takes its bit back (the seed is asked about in a later turn; the host grows the buffers from the count).  A
+// lane that is not open has its final outputs -- a known answer never changes -- and writes them (every turn until its slab
+// settles: the same values).  A slab none of whose lanes is open is settled, a byte per slab; the others are counted for the
+// host.  Every open query asks about, or finds asked, its next seed in every turn, so a query is open for at most
+// max(vignetting_retries, 0) + 1 turns whose lists fit.  A try at a seed known to be occluded fails without a solve
+// (trace_attempt).  Every loop is bounded as in trace_points_kernel.
+// ---------------------------------------------------------------------------------------
+struct TracePointProbeArgs {
+  const float *origin;            // [n_points][3] world space: the segment's origin
+  const float *time;              // optional [n_points]: the sample's time (the motion keys' blend)
+  const uint8_t *exempt;          // optional [n_points]: non-zero = the skydome supplied the sample
+  uint32_t *A, *B;                // the answer store
+  uint32_t words_per_point;
+  uint8_t *settled;               // [n_slabs]
+  unsigned long long *unsettled;  // the slabs this turn left open (reset every turn)
+  CamMotion cam;                  // the context's motion keys and shutter, as a visit stream carries them
+};
+
+// trace_attempt's policy over a point's words of the store
+struct PointSeedAnswers {
+  const uint32_t *A, *B;
+  uint32_t first;                 // first_attempt[point]
+  bool exempt;
+  LD_DEV void look(uint32_t m, bool &occluded, bool &known) const {
+    occluded = false; known = true;
+    if (!exempt) {
+      const uint32_t o = m - first;
+      const uint32_t bit = 1u << (o & 31u);
+      const bool sa = (__hip_atomic_load(&A[o >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit) != 0u;
+      const bool sb = (B[o >> 5] & bit) != 0u;
+      occluded = sb && !sa;
+      known = sb;
+    }
+  }
+};
+
+// What a slab does with its trace: the lanes that are not open commit, the open ones ask.  Called by the whole wave; returns
+// whether some lane is open.
+LD_DEV bool tp_probed_slab(const TracePointArgs &a, const ProbeArgs &pr, const TracePointProbeArgs &b, const AttemptTrace &t, uint32_t point,
+                           uint32_t first, uint32_t attempt, bool commit, uint64_t q, uint32_t lane) {
+  if (commit && !t.open) {
+    a.out_pixel[q] = t.code;
+    if (a.out_xy) { a.out_xy[q * 2] = t.xy0; a.out_xy[q * 2 + 1] = t.xy1; }
+    if (a.out_sensor) { a.out_sensor[q * 2] = t.sen0; a.out_sensor[q * 2 + 1] = t.sen1; }
+    if (a.out_tries) a.out_tries[q] = t.tries;
+  }
+  const unsigned long long om = __ballot(t.open);
+  if (!om) return false;
+  const uint32_t off = point * b.words_per_point;                      // (the host refuses a store of 2^27 words or more per array)
+  const uint32_t o = attempt + (uint32_t)t.tries - first;              // < attempts + max(vignetting_retries, 0)
+  const uint32_t bit = 1u << (o & 31u);
+  uint32_t *wa = b.A + off + (o >> 5);
+  bool win = false;
+  if (t.open) win = (atomicOr(wa, bit) & bit) == 0u;
+  const unsigned long long wm = __ballot(win);
+  if (wm) {
+    const uint32_t slot = probe_wave_slot(pr.count, wm, lane);
+    if (win) {
+      if (slot < pr.cap) {
+        float c2w[4][4];
+        probe_cam_to_world(b.cam, pr, b.time ? b.time[point] : 0.0f, c2w);
+        float tgt[3];
+        probe_target(a.P, c2w, t.lx, t.ly, 0.0f, tgt);
+        lentil_probe_segment sg;
+        sg.origin[0] = b.origin[(size_t)point * 3]; sg.origin[1] = b.origin[(size_t)point * 3 + 1]; sg.origin[2] = b.origin[(size_t)point * 3 + 2];
+        sg.target[0] = tgt[0]; sg.target[1] = tgt[1]; sg.target[2] = tgt[2];
+        pr.seg[slot] = sg;
+        pr.idx[slot] = off * 32u + o;
+      } else {
+        atomicAnd(wa, ~bit);
+      }
+    }
+  }
+  return true;
+}
+
+// LensT / kTables / PO: as trace_points_kernel.  One launch per turn.
+template <class LensT, bool kTables, bool PO>
+__global__ __launch_bounds__(kTpBlock) void trace_points_probed_kernel(TracePointArgs a, ProbeArgs pr, TracePointProbeArgs b) {
+  __shared__ DevTerm s_terms[kTables ? kMaxTerms : 1];
+  __shared__ DevLens s_k;
+  if (PO) {
+    stage_lens<kTables>(a.lens, a.terms, a.lambda, kTpBlock, s_terms, &s_k, threadIdx.x == 0);
+    __syncthreads();
+  }
+  LensT L{};
+  if constexpr (kTables) L.terms = s_terms;
+  L.k = &s_k;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t waves = gridDim.x * (kTpBlock / 64);
+  unsigned long long wave_open = 0;
+  // (slab < n_slabs - waves before the step: the sum cannot wrap)
+  for (uint32_t slab = blockIdx.x * (kTpBlock / 64) + wave; slab < a.n_slabs; slab = (a.n_slabs - slab > waves) ? slab + waves : a.n_slabs) {
+    if (b.settled[slab]) continue;      // wave-uniform
+    const uint32_t point = slab / a.slabs_per_point;
+    const uint32_t k0 = (slab - point * a.slabs_per_point) * kTpSlab;
+    const float cs[3] = {a.cs[(size_t)point * 3], a.cs[(size_t)point * 3 + 1], a.cs[(size_t)point * 3 + 2]};
+    const uint32_t pix = a.pixel[point];
+    const int px = (int)(pix & 0xFFFFu), py = (int)(pix >> 16);
+    const uint32_t first = a.first_attempt ? a.first_attempt[point] : 0u;
+    const uint32_t attempt = first + k0 + lane;
+    const bool commit = k0 + lane < a.attempts;
+    const uint64_t q = (uint64_t)point * a.attempts + k0 + lane;
+    const size_t off = (size_t)point * b.words_per_point;
+    const PointSeedAnswers seeds{b.A + off, b.B + off, first, b.exempt && b.exempt[point] != 0};
+    const AttemptTrace t = trace_attempt<PO>(a.P, L, a.bokeh, cs, px, py, attempt, commit, seeds);
+    if (tp_probed_slab(a, pr, b, t, point, first, attempt, commit, q, lane)) ++wave_open;
+    else if (lane == 0u) b.settled[slab] = 1;
+  }
+  if (lane == 0u && wave_open) atomicAdd(b.unsettled, wave_open);
+}
+
+// The probed call with a wavelength per point (lentil_point_probe::lambdas), polynomial optics: trace_points_probed_kernel's
+// loop line for line (a kernel of its own: the scalar kernels' code stays what it is) with the wave's own LDS row of lambda
+// powers in front, rewritten when the next slab that is not settled belongs to another point -- what
+// trace_points_spectral_kernel does for trace_points_kernel, fences and all.
+template <class LensT, bool kTables>
+__global__ __launch_bounds__(kTpBlock) void trace_points_probed_spectral_kernel(TracePointArgs a, ProbeArgs pr, TracePointProbeArgs b, const double *lambdas) {
+  __shared__ DevTerm s_terms[kTables ? kMaxTerms : 1];
+  __shared__ DevLens s_k;
+  __shared__ double s_lp[kTpBlock / 64][kMaxExp + 1];
+  stage_lens<kTables>(a.lens, a.terms, a.lambda, kTpBlock, s_terms, &s_k, threadIdx.x == 0);
+  __syncthreads();
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t waves = gridDim.x * (kTpBlock / 64);
+  LensT L{};
+  if constexpr (kTables) L.terms = s_terms;
+  L.k = &s_k;
+  L.lam.lp = s_lp[wave];
+  uint32_t staged = 0xFFFFFFFFu;      // (no point: n_points < 2^32)
+  unsigned long long wave_open = 0;
+  // (slab < n_slabs - waves before the step: the sum cannot wrap)
+  for (uint32_t slab = blockIdx.x * (kTpBlock / 64) + wave; slab < a.n_slabs; slab = (a.n_slabs - slab > waves) ? slab + waves : a.n_slabs) {
+    if (b.settled[slab]) continue;      // wave-uniform
+    const uint32_t point = slab / a.slabs_per_point;
+    if (point != staged) {            // wave-uniform
+      double lambda = lambdas[point];
+      if (lambda == 0.0) lambda = a.lambda;
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      if (lane <= (uint32_t)kMaxExp) s_lp[wave][lane] = lane == 0u ? 1.0 : ipow_u(lambda, lane);      // (ipow_u(x, 1) is x)
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      staged = point;
+    }
+    const uint32_t k0 = (slab - point * a.slabs_per_point) * kTpSlab;
+    const float cs[3] = {a.cs[(size_t)point * 3], a.cs[(size_t)point * 3 + 1], a.cs[(size_t)point * 3 + 2]};
+    const uint32_t pix = a.pixel[point];
+    const int px = (int)(pix & 0xFFFFu), py = (int)(pix >> 16);
+    const uint32_t first = a.first_attempt ? a.first_attempt[point] : 0u;
+    const uint32_t attempt = first + k0 + lane;
+    const bool commit = k0 + lane < a.attempts;
+    const uint64_t q = (uint64_t)point * a.attempts + k0 + lane;
+    const size_t off = (size_t)point * b.words_per_point;
+    const PointSeedAnswers seeds{b.A + off, b.B + off, first, b.exempt && b.exempt[point] != 0};
+    const AttemptTrace t = trace_attempt<true>(a.P, L, a.bokeh, cs, px, py, attempt, commit, seeds);
+    if (tp_probed_slab(a, pr, b, t, point, first, attempt, commit, q, lane)) ++wave_open;
+    else if (lane == 0u) b.settled[slab] = 1;
+  }
+  if (lane == 0u && wave_open) atomicAdd(b.unsettled, wave_open);
 }
