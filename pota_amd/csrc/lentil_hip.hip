@@ -4152,9 +4152,26 @@ static int lens_dispatch(const lentil_hip_ctx *ctx, bool po, F &&f) {
 }
 
 // ---- scene points traced backward in batches (lentil_trace_points.h) ----------------------------------------------------
-// The scalar and the spectral call: `spectral` takes point j at lambdas[j] (0: params.lambda_bw; polynomial optics -- the thin
-// lens reads no wavelength and runs what the scalar call runs), else every point at batch->lambda.
-static int trace_points_call(lentil_hip_ctx *ctx, const lentil_point_batch *batch, const double *lambdas, bool spectral) {
+// A point batch between its caller and the trace kernels, for the unprobed and the probed call alike: point_batch_check is
+// the validation, point_batch_stage the kernel's arguments, the grid and -- for a batch of host pointers -- the inputs
+// uploaded and the outputs allocated, point_batch_finish the download of those outputs.
+struct PointBatch {
+  bool po = false, spectral = false, device = false;
+  uint64_t np = 0, K = 0;
+  const double *lambdas = nullptr;     // spectral: a wavelength per point, device memory once staged
+  TracePointArgs a{};
+  dim3 grid;
+  TmpFree tf;
+  uint32_t *d_out = nullptr;
+  double *d_xy = nullptr, *d_sensor = nullptr;
+  int32_t *d_tries = nullptr;
+};
+
+// `spectral` takes point j at lambdas[j] (0: params.lambda_bw; polynomial optics -- the thin lens reads no wavelength and runs
+// what the scalar call runs), else every point at batch->lambda.  `probed`: the probed call's own checks, where its validation
+// has them, and probe->lambdas for the wavelengths.  An empty batch comes back LENTIL_OK with s.np == 0.
+static int point_batch_check(lentil_hip_ctx *ctx, const lentil_point_batch *batch, const double *lambdas, bool spectral, bool probed,
+                             const lentil_point_probe *probe, PointBatch &s) {
   CHECK_CTX(ctx);
   if (!batch) return fail(ctx, LENTIL_ERR_INVALID, "batch is null");
   if (!ctx->have_params) return fail(ctx, LENTIL_ERR_INVALID, "set_params first");
@@ -4164,69 +4181,105 @@ static int trace_points_call(lentil_hip_ctx *ctx, const lentil_point_batch *batc
   if (!batch->attempts) return fail(ctx, LENTIL_ERR_INVALID, "attempts is 0");
   const uint64_t np = batch->n_points, K = batch->attempts;
   if (np >= (1ull << 32) || np * K >= (1ull << 32)) return fail(ctx, LENTIL_ERR_INVALID, "n_points * attempts must be below 2^32");
+  if (probed) {
+    if (!probing(ctx))
+      return fail(ctx, LENTIL_ERR_INVALID, "trace_points_probed needs an occlusion probe (set_occlusion_probe or set_occlusion_probe_device)");
+    if (po && ctx->P.abb_chromatic != 0.0f)
+      return fail(ctx, LENTIL_ERR_UNSUPPORTED, "trace_points_probed: polynomial optics with abb_chromatic != 0 (every channel's tries under the probe) "
+                                               "is not built; the pass and the probed list refuse the pair too");
+  }
   if (!np) return LENTIL_OK;
   if (!batch->cs || !batch->pixel || !batch->out_pixel) return fail(ctx, LENTIL_ERR_INVALID, "cs / pixel / out_pixel is null");
-  spectral = spectral && po;
-  if (spectral && !lambdas) return fail(ctx, LENTIL_ERR_INVALID, "lambdas is null");
-  const bool device = (batch->flags & LENTIL_POINTS_DEVICE_POINTERS) != 0u;
+  if (probed) {
+    if (!probe || !probe->origin) return fail(ctx, LENTIL_ERR_INVALID, "trace_points_probed: probe / probe->origin is null");
+    // (from here on the probed call is a spectral call whose wavelengths are the probe's: "lambdas is null" below cannot fire)
+    lambdas = probe->lambdas;
+    spectral = lambdas != nullptr;
+  }
+  s.spectral = spectral && po;
+  if (s.spectral && !lambdas) return fail(ctx, LENTIL_ERR_INVALID, "lambdas is null");
+  s.lambdas = s.spectral ? lambdas : nullptr;
+  s.device = (batch->flags & LENTIL_POINTS_DEVICE_POINTERS) != 0u;
   // the seeds of a point's tries, first_attempt ... first_attempt + attempts - 1 + retries, must not wrap
   const uint64_t reach = K + (uint64_t)(ctx->P.vignetting_retries > 0 ? ctx->P.vignetting_retries : 0);
   if (reach >= (1ull << 32)) return fail(ctx, LENTIL_ERR_INVALID, "attempts + vignetting_retries does not fit 32 bits");
-  if (!device && batch->first_attempt)
+  if (!s.device && batch->first_attempt)
     for (uint64_t i = 0; i < np; ++i)
       if ((uint64_t)batch->first_attempt[i] + reach >= (1ull << 32))
         return fail(ctx, LENTIL_ERR_INVALID, "first_attempt + attempts + vignetting_retries of point " + std::to_string(i) + " does not fit 32 bits");
+  s.po = po; s.np = np; s.K = K;
+  return LENTIL_OK;
+}
+
+static int point_batch_stage(lentil_hip_ctx *ctx, const lentil_point_batch *batch, PointBatch &s) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const uint64_t nq = np * K;
-  TracePointArgs a{};
+  const uint64_t np = s.np, K = s.K, nq = np * K;
+  const bool po = s.po;
+  TracePointArgs &a = s.a;
   a.P = ctx->P; a.lens = po ? ctx->d_lens : nullptr; a.terms = po ? ctx->d_terms : nullptr; a.bokeh = ctx->bokeh;
   a.attempts = (uint32_t)K;
   a.slabs_per_point = (uint32_t)((K + kTpSlab - 1) / kTpSlab);
   a.n_slabs = (uint32_t)(np * a.slabs_per_point);              // <= n_points * attempts < 2^32
-  a.lambda = (!spectral && batch->lambda != 0.0) ? batch->lambda : (double)ctx->P.lambda_bw;
-  TmpFree tf;
-  float *d_cs = nullptr;
-  uint32_t *d_pixel = nullptr, *d_first = nullptr, *d_out = nullptr;
-  double *d_xy = nullptr, *d_sensor = nullptr, *d_lambdas = nullptr;
-  int32_t *d_tries = nullptr;
-  if (device) {
+  a.lambda = (!s.spectral && batch->lambda != 0.0) ? batch->lambda : (double)ctx->P.lambda_bw;
+  if (s.device) {
     a.cs = batch->cs; a.pixel = batch->pixel; a.first_attempt = batch->first_attempt;
     a.out_pixel = batch->out_pixel; a.out_xy = batch->out_xy; a.out_sensor = batch->out_sensor; a.out_tries = batch->out_tries;
   } else {
     int rc;
-    if ((rc = dev_copy_in(ctx, batch->cs, (size_t)np * 3, &d_cs, tf.v))) return rc;
-    if ((rc = dev_copy_in(ctx, batch->pixel, (size_t)np, &d_pixel, tf.v))) return rc;
-    if ((rc = dev_copy_in(ctx, batch->first_attempt, (size_t)np, &d_first, tf.v))) return rc;
-    if (spectral && (rc = dev_copy_in(ctx, lambdas, (size_t)np, &d_lambdas, tf.v))) return rc;
-    lambdas = d_lambdas;
-    if ((rc = dev_alloc(ctx, (size_t)nq, &d_out, tf.v))) return rc;
-    if (batch->out_xy && (rc = dev_alloc(ctx, (size_t)nq * 2, &d_xy, tf.v))) return rc;
-    if (batch->out_sensor && (rc = dev_alloc(ctx, (size_t)nq * 2, &d_sensor, tf.v))) return rc;
-    if (batch->out_tries && (rc = dev_alloc(ctx, (size_t)nq, &d_tries, tf.v))) return rc;
+    float *d_cs = nullptr;
+    uint32_t *d_pixel = nullptr, *d_first = nullptr;
+    double *d_lambdas = nullptr;
+    std::vector<void *> &tmp = s.tf.v;
+    if ((rc = dev_copy_in(ctx, batch->cs, (size_t)np * 3, &d_cs, tmp))) return rc;
+    if ((rc = dev_copy_in(ctx, batch->pixel, (size_t)np, &d_pixel, tmp))) return rc;
+    if ((rc = dev_copy_in(ctx, batch->first_attempt, (size_t)np, &d_first, tmp))) return rc;
+    if (s.spectral && (rc = dev_copy_in(ctx, s.lambdas, (size_t)np, &d_lambdas, tmp))) return rc;
+    s.lambdas = d_lambdas;
+    if ((rc = dev_alloc(ctx, (size_t)nq, &s.d_out, tmp))) return rc;
+    if (batch->out_xy && (rc = dev_alloc(ctx, (size_t)nq * 2, &s.d_xy, tmp))) return rc;
+    if (batch->out_sensor && (rc = dev_alloc(ctx, (size_t)nq * 2, &s.d_sensor, tmp))) return rc;
+    if (batch->out_tries && (rc = dev_alloc(ctx, (size_t)nq, &s.d_tries, tmp))) return rc;
     a.cs = d_cs; a.pixel = d_pixel; a.first_attempt = d_first;
-    a.out_pixel = d_out; a.out_xy = d_xy; a.out_sensor = d_sensor; a.out_tries = d_tries;
+    a.out_pixel = s.d_out; a.out_xy = s.d_xy; a.out_sensor = s.d_sensor; a.out_tries = s.d_tries;
   }
   // a slab per wave, four waves per block; no more blocks than the device holds at once (eight waves per SIMD at the most)
   const uint64_t want = ((uint64_t)a.n_slabs + kTpBlock / 64 - 1) / (kTpBlock / 64), cap = (uint64_t)ctx->num_cu * 8u;
-  const dim3 grid((unsigned)(want < cap ? want : cap));
-  ctx->points_path = lens_dispatch(ctx, po, [&](auto lp) {
+  s.grid = dim3((unsigned)(want < cap ? want : cap));
+  return LENTIL_OK;
+}
+
+// behind the kernels, the stream waited for: a batch of host pointers gets its outputs
+static int point_batch_finish(lentil_hip_ctx *ctx, const lentil_point_batch *batch, const PointBatch &s) {
+  if (s.device) return LENTIL_OK;
+  const uint64_t nq = s.np * s.K;
+  HIP_TRY(ctx, hipMemcpy(batch->out_pixel, s.d_out, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (batch->out_xy) HIP_TRY(ctx, hipMemcpy(batch->out_xy, s.d_xy, (size_t)nq * 2 * sizeof(double), hipMemcpyDeviceToHost));
+  if (batch->out_sensor) HIP_TRY(ctx, hipMemcpy(batch->out_sensor, s.d_sensor, (size_t)nq * 2 * sizeof(double), hipMemcpyDeviceToHost));
+  if (batch->out_tries) HIP_TRY(ctx, hipMemcpy(batch->out_tries, s.d_tries, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return LENTIL_OK;
+}
+
+// the scalar and the spectral call
+static int trace_points_call(lentil_hip_ctx *ctx, const lentil_point_batch *batch, const double *lambdas, bool spectral) {
+  PointBatch s;
+  int rc;
+  if ((rc = point_batch_check(ctx, batch, lambdas, spectral, false, nullptr, s)) || !s.np) return rc;
+  if ((rc = point_batch_stage(ctx, batch, s))) return rc;
+  const TracePointArgs &a = s.a;
+  ctx->points_path = lens_dispatch(ctx, s.po, [&](auto lp) {
     using T = decltype(lp);
     if constexpr (T::PO) {
-      if (spectral) {
-        hipLaunchKernelGGL((trace_points_spectral_kernel<typename SpectralLens<typename T::LensT>::Wave, T::kTables>), grid, dim3(kTpBlock), 0, ctx->stream, a, lambdas);
+      if (s.spectral) {
+        hipLaunchKernelGGL((trace_points_spectral_kernel<typename SpectralLens<typename T::LensT>::Wave, T::kTables>), s.grid, dim3(kTpBlock), 0, ctx->stream, a, s.lambdas);
         return;
       }
     }
-    hipLaunchKernelGGL((trace_points_kernel<typename T::LensT, T::kTables, T::PO>), grid, dim3(kTpBlock), 0, ctx->stream, a);
+    hipLaunchKernelGGL((trace_points_kernel<typename T::LensT, T::kTables, T::PO>), s.grid, dim3(kTpBlock), 0, ctx->stream, a);
   });
   HIP_TRY(ctx, hipGetLastError());
-  if (device) return LENTIL_OK;
+  if (s.device) return LENTIL_OK;
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  HIP_TRY(ctx, hipMemcpy(batch->out_pixel, d_out, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  if (batch->out_xy) HIP_TRY(ctx, hipMemcpy(batch->out_xy, d_xy, (size_t)nq * 2 * sizeof(double), hipMemcpyDeviceToHost));
-  if (batch->out_sensor) HIP_TRY(ctx, hipMemcpy(batch->out_sensor, d_sensor, (size_t)nq * 2 * sizeof(double), hipMemcpyDeviceToHost));
-  if (batch->out_tries) HIP_TRY(ctx, hipMemcpy(batch->out_tries, d_tries, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost));
-  return LENTIL_OK;
+  return point_batch_finish(ctx, batch, s);
 }
 
 LENTIL_API int lentil_hip_trace_points(lentil_hip_ctx *ctx, const lentil_point_batch *batch) {
@@ -4289,6 +4342,82 @@ LENTIL_API int lentil_hip_plan_visits(lentil_hip_ctx *ctx, uint64_t first_visit,
   return LENTIL_OK;
 }
 
+// ---- the turns of a probed list and of a probed point batch ----------------------------------------------------------------
+// Which seeds a visit or a query reaches depends on the probe's answers, so both are made in turns, until a turn leaves
+// nothing unsettled.  A turn: the buffers reserved and bound, the list's counter reset, `turn(pr)` -- the caller's own counters
+// reset and its kernel launched into ctx->stream, -> an error code --, the clamp, the turn's counters read back (64 bytes,
+// one wait), the callback on this thread (host: segments out, answers in, as probe_ask moves them; device:
+// probe_call_device, nothing else crosses), the apply kernel.  The buffers are the context's (ld_pb), kept between calls; a
+// turn that wanted more than they hold took the A bits beyond them back, and asks the rest in a later turn, into larger ones.
+//   ctx->d_list_ctr  [4..6] the list's ticket, accepted draws and attempts made (ListDrawArgs::ctr [0..2]), [7] what this turn
+//                    left unsettled -- the caller's kernel counts it, the caller's `turn` resets it --, [8..11] b.x, of
+//                    which [11] is the turn's raw length; list_ctr (the list; NULL: the points, whose slots 4 ... 6 nobody
+//                    reads): slots 4 ... 6 as the last turn left them
+//   want_cap         the first turn's capacity; cap_limit (0: none) holds it down, else the buffers kept from earlier calls
+//                    hold it up -- and then every turn's capacity is pb.cap
+//   max_turns        the caller's bound on the turns; did_not_end and asked_nothing: its texts for the two internal errors
+template <class Turn>
+static int probe_turns(lentil_hip_ctx *ctx, ProbeArgs &pr, const ListProbeArgs &b, uint64_t want_cap, uint64_t cap_limit, uint64_t max_turns,
+                       const char *did_not_end, const char *asked_nothing, unsigned long long *list_ctr, Turn turn) {
+  hipStream_t st = ctx->stream;
+  ProbeBuf &pb = ctx->ld_pb;
+  const bool host = ctx->probe_fn != nullptr;
+  constexpr uint64_t kMost = 1ull << 24;
+  if (cap_limit) { if (want_cap > cap_limit) want_cap = cap_limit; }
+  else if (want_cap < pb.cap) want_cap = pb.cap;
+  const dim3 pgrid((unsigned)ctx->num_cu * 4u), pblock(256);
+  unsigned long long t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  int rc;
+  for (uint64_t n_turn = 0;; ++n_turn) {
+    if (n_turn >= max_turns) return fail(ctx, LENTIL_ERR_INVALID, did_not_end);
+    if (pb.cap < want_cap || (host && pb.h_cap < want_cap) || !pb.count) {
+      HIP_TRY(ctx, hipStreamSynchronize(st));       // (the last turn's apply kernel reads the buffers that go)
+      if ((rc = probe_buf_reserve(ctx, pb, want_cap, host))) return rc;
+    }
+    const uint64_t cap = want_cap < 64u ? 64u : want_cap;      // (at most pb.cap: probe_buf_reserve's floor)
+    if (pb.occ_dirty) { HIP_TRY(ctx, hipMemsetAsync(pb.occ, 0, pb.cap, st)); pb.occ_dirty = false; }
+    probe_bind(pb, cap, pr);
+    HIP_TRY(ctx, hipMemsetAsync(pb.count, 0, sizeof(unsigned int), st));
+    if ((rc = turn(pr))) return rc;
+    hipLaunchKernelGGL(ld_probe_clamp_kernel, dim3(1), dim3(64), 0, st, pb.count, pr.cap, b.x);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(t, ctx->d_list_ctr + 4, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (!host) ++ctx->n_dev_waits;
+    const uint64_t raw = t[7], unsettled = t[3];
+    const uint64_t n = raw < cap ? raw : cap;
+    if (n) {
+      if (host) {
+        HIP_TRY(ctx, hipMemcpyAsync(pb.h_seg, pb.seg, (size_t)n * sizeof(lentil_probe_segment), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        memset(pb.h_occ, 0, (size_t)n);
+        ctx->probe_fn(ctx->probe_user, n, pb.h_seg, pb.h_occ);
+        uint64_t occ = 0;
+        for (uint64_t i = 0; i < n; ++i) occ += pb.h_occ[i] ? 1u : 0u;
+        ctx->n_probes += n; ctx->n_probes_occluded += occ; ++ctx->n_probe_calls;
+        if (occ) HIP_TRY(ctx, hipMemcpyAsync(pb.occ, pb.h_occ, (size_t)n, hipMemcpyHostToDevice, st));
+      } else {
+        if ((rc = probe_call_device(ctx, pb, cap, st))) { pb.occ_dirty = true; return rc; }
+        ctx->n_probes += n;
+        if (n > ctx->dev_longest) ctx->dev_longest = n;
+      }
+      hipLaunchKernelGGL(ld_probe_apply_kernel, pgrid, pblock, 0, st, b, (const uint32_t *)pb.idx, pb.occ, (const unsigned int *)pb.count, pr.cap);
+      HIP_TRY(ctx, hipGetLastError());
+    }
+    if (!unsettled) break;
+    if (!n) return fail(ctx, LENTIL_ERR_INVALID, asked_nothing);
+    if (raw > cap) want_cap = raw * 2u > kMost ? (cap > kMost ? cap : kMost) : raw * 2u;
+  }
+  HIP_TRY(ctx, hipStreamSynchronize(st));       // (the last apply, and the host form's upload from the pinned answers)
+  if (!host) {
+    unsigned long long occ = 0;
+    HIP_TRY(ctx, hipMemcpy(&occ, b.x + 2, sizeof occ, hipMemcpyDeviceToHost));
+    ctx->n_probes_occluded += occ;
+  }
+  if (list_ctr) { list_ctr[0] = t[0]; list_ctr[1] = t[1]; list_ctr[2] = t[2]; }
+  return LENTIL_OK;
+}
+
 // One turn's walk of a probed list, on the lens path the unprobed list takes.  lambdas (device memory, polynomial optics):
 // a wavelength per visit of the range; NULL: a.lambda for all of them.
 static int list_probed_launch(lentil_hip_ctx *ctx, dim3 grid, bool po, const ListDrawArgs &a, const ProbeArgs &pr, const ListProbeArgs &b,
@@ -4308,12 +4437,8 @@ static int list_probed_launch(lentil_hip_ctx *ctx, dim3 grid, bool po, const Lis
   return LENTIL_OK;
 }
 
-// LENTIL_DRAWS_PROBED (lentil_list_draws.h): the answer store is sized and allocated, then the turns -- counter reset, the
-// walk, the clamp, the turn's length and the unsettled visits read back (64 bytes, one wait), the callback on this thread
-// (host: segments out, answers in, as probe_ask moves them; device: probe_call_device, nothing else crosses), the apply kernel
-// -- until a turn leaves no visit unsettled.  The turn's buffers are the context's (ld_pb), kept between calls; a turn that
-// wanted more than they hold asks the rest in a later turn, into larger ones.  h: ListDrawArgs::ctr [0..2] at the end.
-// lambdas: as list_probed_launch takes them.
+// LENTIL_DRAWS_PROBED (lentil_list_draws.h): the answer store is sized and allocated, then the turns (probe_turns) until one
+// leaves no visit unsettled.  h: ListDrawArgs::ctr [0..2] at the end.  lambdas: as list_probed_launch takes them.
 static int list_draws_probed(lentil_hip_ctx *ctx, ListDrawArgs &a, dim3 grid, bool po, TmpFree &tf, unsigned long long h[3],
                              const double *lambdas) {
   hipStream_t st = ctx->stream;
@@ -4355,64 +4480,16 @@ static int list_draws_probed(lentil_hip_ctx *ctx, ListDrawArgs &a, dim3 grid, bo
     b.A = store; b.B = store + words;
     HIP_TRY(ctx, hipMemsetAsync(store, 0, (size_t)words * 8u, st));
   }
-  ProbeBuf &pb = ctx->ld_pb;
-  const bool host = ctx->probe_fn != nullptr;
-  constexpr uint64_t kFirstMost = 1ull << 22, kMost = 1ull << 24;
-  uint64_t want_cap = words * 7u < 4096u ? 4096u : (words * 7u > kFirstMost ? kFirstMost : words * 7u);      // about the sum of the samples
-  if (want_cap < pb.cap) want_cap = pb.cap;
+  constexpr uint64_t kFirstMost = 1ull << 22;
+  const uint64_t want_cap = words * 7u < 4096u ? 4096u : (words * 7u > kFirstMost ? kFirstMost : words * 7u);      // about the sum of the samples
   // every walk of an unsettled visit asks about a new seed of it; a turn that did not fit retires a buffer's worth of the store's seeds
   const uint64_t max_turns = most_seeds + 64u + words * 32u / 4096u;
-  const dim3 pgrid((unsigned)ctx->num_cu * 4u), pblock(256);
-  unsigned long long t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (uint64_t turn = 0;; ++turn) {
-    if (turn >= max_turns) return fail(ctx, LENTIL_ERR_INVALID, "list_draws: the probed list's turns did not end (internal)");
-    if (pb.cap < want_cap || (host && pb.h_cap < want_cap) || !pb.count) {
-      HIP_TRY(ctx, hipStreamSynchronize(st));       // (the last turn's apply kernel reads the buffers that go)
-      if ((rc = probe_buf_reserve(ctx, pb, want_cap, host))) return rc;
-    }
-    if (pb.occ_dirty) { HIP_TRY(ctx, hipMemsetAsync(pb.occ, 0, pb.cap, st)); pb.occ_dirty = false; }
-    probe_bind(pb, pb.cap, pr);
-    HIP_TRY(ctx, hipMemsetAsync(pb.count, 0, sizeof(unsigned int), st));
-    HIP_TRY(ctx, hipMemsetAsync(a.ctr + 0, 0, sizeof(unsigned long long), st));
-    HIP_TRY(ctx, hipMemsetAsync(a.ctr + 3, 0, sizeof(unsigned long long), st));
-    if ((rc = list_probed_launch(ctx, grid, po, a, pr, b, lambdas))) return rc;
-    hipLaunchKernelGGL(ld_probe_clamp_kernel, dim3(1), dim3(64), 0, st, pb.count, pr.cap, b.x);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(t, a.ctr, sizeof t, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (!host) ++ctx->n_dev_waits;
-    const uint64_t raw = t[7], unsettled = t[3];
-    const uint64_t n = raw < pb.cap ? raw : pb.cap;
-    if (n) {
-      if (host) {
-        HIP_TRY(ctx, hipMemcpyAsync(pb.h_seg, pb.seg, (size_t)n * sizeof(lentil_probe_segment), hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        memset(pb.h_occ, 0, (size_t)n);
-        ctx->probe_fn(ctx->probe_user, n, pb.h_seg, pb.h_occ);
-        uint64_t occ = 0;
-        for (uint64_t i = 0; i < n; ++i) occ += pb.h_occ[i] ? 1u : 0u;
-        ctx->n_probes += n; ctx->n_probes_occluded += occ; ++ctx->n_probe_calls;
-        if (occ) HIP_TRY(ctx, hipMemcpyAsync(pb.occ, pb.h_occ, (size_t)n, hipMemcpyHostToDevice, st));
-      } else {
-        if ((rc = probe_call_device(ctx, pb, pb.cap, st))) { pb.occ_dirty = true; return rc; }
-        ctx->n_probes += n;
-        if (n > ctx->dev_longest) ctx->dev_longest = n;
-      }
-      hipLaunchKernelGGL(ld_probe_apply_kernel, pgrid, pblock, 0, st, b, (const uint32_t *)pb.idx, pb.occ, (const unsigned int *)pb.count, pr.cap);
-      HIP_TRY(ctx, hipGetLastError());
-    }
-    if (!unsettled) break;
-    if (!n) return fail(ctx, LENTIL_ERR_INVALID, "list_draws: a probed list's turn left visits unsettled and asked nothing (internal)");
-    if (raw > pb.cap) want_cap = raw * 2u > kMost ? (pb.cap > kMost ? pb.cap : kMost) : raw * 2u;
-  }
-  HIP_TRY(ctx, hipStreamSynchronize(st));       // (the last apply, and the host form's upload from the pinned answers)
-  if (!host) {
-    unsigned long long occ = 0;
-    HIP_TRY(ctx, hipMemcpy(&occ, b.x + 2, sizeof occ, hipMemcpyDeviceToHost));
-    ctx->n_probes_occluded += occ;
-  }
-  h[0] = t[0]; h[1] = t[1]; h[2] = t[2];
-  return LENTIL_OK;
+  return probe_turns(ctx, pr, b, want_cap, 0, max_turns, "list_draws: the probed list's turns did not end (internal)",
+                   "list_draws: a probed list's turn left visits unsettled and asked nothing (internal)", h, [&](const ProbeArgs &q) -> int {
+                     HIP_TRY(ctx, hipMemsetAsync(a.ctr + 0, 0, sizeof(unsigned long long), st));
+                     HIP_TRY(ctx, hipMemsetAsync(a.ctr + 3, 0, sizeof(unsigned long long), st));
+                     return list_probed_launch(ctx, grid, po, a, q, b, lambdas);
+                   });
 }
 
 // The scalar and the spectral call: `spectral` takes visit first_visit + i at lambdas[i] (0: params.lambda_bw; polynomial optics
@@ -4529,89 +4606,41 @@ LENTIL_API int lentil_hip_list_draws_spectral(lentil_hip_ctx *ctx, const lentil_
 }
 
 // ---- scene points traced backward under the occlusion probe (lentil_trace_points.h: trace_points_probed_kernel) ---------------
-// The validation of trace_points_call and the probe's own, the inputs on the device, the answer store allocated and zeroed,
-// then the turns, shaped like list_draws_probed's: counter reset, the kernel, the clamp, the turn's length and the unsettled
-// slabs read back in one wait, the callback on this thread (host: segments out, answers in; device: probe_call_device), the
-// apply kernel -- until a turn leaves no slab unsettled.  The buffers are the probed list's (ld_pb), kept between calls; a turn
-// that wanted more than they hold asks the rest in a later turn, into larger ones.  LENTIL_POINTS_PROBE_CAP caps the first
-// turn's capacity (tests: the growth).
+// The point batch's validation with the probe's own, the batch and the probe's arrays on the device, the answer store
+// allocated and zeroed, then the turns (probe_turns).  LENTIL_POINTS_PROBE_CAP caps the first turn's capacity (tests: the
+// growth).
 static int trace_points_probed_call(lentil_hip_ctx *ctx, const lentil_point_batch *batch, const lentil_point_probe *probe) {
-  CHECK_CTX(ctx);
-  if (!batch) return fail(ctx, LENTIL_ERR_INVALID, "batch is null");
-  if (!ctx->have_params) return fail(ctx, LENTIL_ERR_INVALID, "set_params first");
-  const bool po = ctx->P.cameraType == LENTIL_POLYNOMIAL_OPTICS;
-  if (po && !ctx->have_lens) return fail(ctx, LENTIL_ERR_INVALID, "a polynomial-optics camera needs set_lens first");
-  if (ctx->P.bokeh_enable_image && !ctx->have_bokeh) return fail(ctx, LENTIL_ERR_INVALID, "bokeh_enable_image needs set_bokeh first");
-  if (!batch->attempts) return fail(ctx, LENTIL_ERR_INVALID, "attempts is 0");
-  const uint64_t np = batch->n_points, K = batch->attempts;
-  if (np >= (1ull << 32) || np * K >= (1ull << 32)) return fail(ctx, LENTIL_ERR_INVALID, "n_points * attempts must be below 2^32");
-  if (!probing(ctx))
-    return fail(ctx, LENTIL_ERR_INVALID, "trace_points_probed needs an occlusion probe (set_occlusion_probe or set_occlusion_probe_device)");
-  if (po && ctx->P.abb_chromatic != 0.0f)
-    return fail(ctx, LENTIL_ERR_UNSUPPORTED, "trace_points_probed: polynomial optics with abb_chromatic != 0 (every channel's tries under the probe) "
-                                             "is not built; the pass and the probed list refuse the pair too");
-  if (!np) return LENTIL_OK;
-  if (!batch->cs || !batch->pixel || !batch->out_pixel) return fail(ctx, LENTIL_ERR_INVALID, "cs / pixel / out_pixel is null");
-  if (!probe || !probe->origin) return fail(ctx, LENTIL_ERR_INVALID, "trace_points_probed: probe / probe->origin is null");
-  const bool spectral = po && probe->lambdas != nullptr;
-  const bool device = (batch->flags & LENTIL_POINTS_DEVICE_POINTERS) != 0u;
-  // the seeds of a point's tries, first_attempt ... first_attempt + attempts - 1 + retries, must not wrap
-  const uint64_t retries = po && ctx->P.vignetting_retries > 0 ? (uint64_t)ctx->P.vignetting_retries : 0ull;
-  const uint64_t reach = K + (uint64_t)(ctx->P.vignetting_retries > 0 ? ctx->P.vignetting_retries : 0);
-  if (reach >= (1ull << 32)) return fail(ctx, LENTIL_ERR_INVALID, "attempts + vignetting_retries does not fit 32 bits");
-  if (!device && batch->first_attempt)
-    for (uint64_t i = 0; i < np; ++i)
-      if ((uint64_t)batch->first_attempt[i] + reach >= (1ull << 32))
-        return fail(ctx, LENTIL_ERR_INVALID, "first_attempt + attempts + vignetting_retries of point " + std::to_string(i) + " does not fit 32 bits");
+  PointBatch s;
+  int rc;
+  if ((rc = point_batch_check(ctx, batch, nullptr, false, true, probe, s)) || !s.np) return rc;
+  const bool po = s.po;
+  const uint64_t np = s.np;
   // the store: two arrays of `words` 32-bit words; a seed's place in it is a 32-bit bit index
-  const uint64_t seeds = K + retries, wpp = (seeds + 31u) / 32u, words = np * wpp;
+  const uint64_t retries = po && ctx->P.vignetting_retries > 0 ? (uint64_t)ctx->P.vignetting_retries : 0ull;
+  const uint64_t seeds = s.K + retries, wpp = (seeds + 31u) / 32u, words = np * wpp;
   const std::string split = "trace_points_probed: the answer store of this batch (" + std::to_string(words * 8u) + " bytes) does not fit; split the batch";
   if (words >= (1ull << 27)) return fail(ctx, LENTIL_ERR_NOMEM, split);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   if (!ctx->d_list_ctr) HIP_TRY(ctx, hipMalloc(&ctx->d_list_ctr, 16 * sizeof(unsigned long long)));
-  const uint64_t nq = np * K;
-  TracePointArgs a{};
-  a.P = ctx->P; a.lens = po ? ctx->d_lens : nullptr; a.terms = po ? ctx->d_terms : nullptr; a.bokeh = ctx->bokeh;
-  a.attempts = (uint32_t)K;
-  a.slabs_per_point = (uint32_t)((K + kTpSlab - 1) / kTpSlab);
-  a.n_slabs = (uint32_t)(np * a.slabs_per_point);              // <= n_points * attempts < 2^32
-  a.lambda = (!spectral && batch->lambda != 0.0) ? batch->lambda : (double)ctx->P.lambda_bw;
+  ProbeArgs pr{};
+  if ((rc = probe_prepare(ctx, pr, st))) return rc;
+  if ((rc = point_batch_stage(ctx, batch, s))) return rc;
+  const TracePointArgs &a = s.a;
   TracePointProbeArgs b{};
   b.cam = CamMotion{ctx->n_cam_keys >= 2 ? ctx->d_cam_keys : nullptr, ctx->n_cam_keys >= 2 ? ctx->n_cam_keys : 0u, ctx->shutter_t0, ctx->shutter_inv_dt};
   b.words_per_point = (uint32_t)wpp;
   b.unsettled = ctx->d_list_ctr + 7;
   ListProbeArgs lb{};                                          // what ld_probe_apply_kernel and ld_probe_clamp_kernel take
   lb.x = ctx->d_list_ctr + 8;
-  int rc;
-  ProbeArgs pr{};
-  if ((rc = probe_prepare(ctx, pr, st))) return rc;
-  TmpFree tf;
-  float *d_cs = nullptr, *d_origin = nullptr, *d_time = nullptr;
-  uint8_t *d_exempt = nullptr;
-  uint32_t *d_pixel = nullptr, *d_first = nullptr, *d_out = nullptr;
-  double *d_xy = nullptr, *d_sensor = nullptr, *d_lambdas = nullptr;
-  int32_t *d_tries = nullptr;
-  const double *lambdas = spectral ? probe->lambdas : nullptr;
-  if (device) {
-    a.cs = batch->cs; a.pixel = batch->pixel; a.first_attempt = batch->first_attempt;
-    a.out_pixel = batch->out_pixel; a.out_xy = batch->out_xy; a.out_sensor = batch->out_sensor; a.out_tries = batch->out_tries;
+  if (s.device) {
     b.origin = probe->origin; b.time = probe->time; b.exempt = probe->exempt;
   } else {
-    if ((rc = dev_copy_in(ctx, batch->cs, (size_t)np * 3, &d_cs, tf.v))) return rc;
-    if ((rc = dev_copy_in(ctx, batch->pixel, (size_t)np, &d_pixel, tf.v))) return rc;
-    if ((rc = dev_copy_in(ctx, batch->first_attempt, (size_t)np, &d_first, tf.v))) return rc;
-    if ((rc = dev_copy_in(ctx, probe->origin, (size_t)np * 3, &d_origin, tf.v))) return rc;
-    if ((rc = dev_copy_in(ctx, probe->time, (size_t)np, &d_time, tf.v))) return rc;
-    if ((rc = dev_copy_in(ctx, probe->exempt, (size_t)np, &d_exempt, tf.v))) return rc;
-    if (spectral && (rc = dev_copy_in(ctx, lambdas, (size_t)np, &d_lambdas, tf.v))) return rc;
-    lambdas = d_lambdas;
-    if ((rc = dev_alloc(ctx, (size_t)nq, &d_out, tf.v))) return rc;
-    if (batch->out_xy && (rc = dev_alloc(ctx, (size_t)nq * 2, &d_xy, tf.v))) return rc;
-    if (batch->out_sensor && (rc = dev_alloc(ctx, (size_t)nq * 2, &d_sensor, tf.v))) return rc;
-    if (batch->out_tries && (rc = dev_alloc(ctx, (size_t)nq, &d_tries, tf.v))) return rc;
-    a.cs = d_cs; a.pixel = d_pixel; a.first_attempt = d_first;
-    a.out_pixel = d_out; a.out_xy = d_xy; a.out_sensor = d_sensor; a.out_tries = d_tries;
+    float *d_origin = nullptr, *d_time = nullptr;
+    uint8_t *d_exempt = nullptr;
+    if ((rc = dev_copy_in(ctx, probe->origin, (size_t)np * 3, &d_origin, s.tf.v))) return rc;
+    if ((rc = dev_copy_in(ctx, probe->time, (size_t)np, &d_time, s.tf.v))) return rc;
+    if ((rc = dev_copy_in(ctx, probe->exempt, (size_t)np, &d_exempt, s.tf.v))) return rc;
     b.origin = d_origin; b.time = d_time; b.exempt = d_exempt;
   }
   {
@@ -4620,92 +4649,38 @@ static int trace_points_probed_call(lentil_hip_ctx *ctx, const lentil_point_batc
     if (words * 8u + a.n_slabs > free_b / 2u) return fail(ctx, LENTIL_ERR_NOMEM, split);
     uint32_t *store = nullptr;
     if (hipMalloc((void **)&store, (size_t)words * 8u + a.n_slabs) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, LENTIL_ERR_NOMEM, split); }
-    tf.v.push_back(store);
+    s.tf.v.push_back(store);
     b.A = store; b.B = store + words;
     b.settled = reinterpret_cast<uint8_t *>(store + 2u * words);       // a byte per slab behind the two arrays
     lb.A = b.A; lb.B = b.B;
     HIP_TRY(ctx, hipMemsetAsync(store, 0, (size_t)words * 8u + a.n_slabs, st));
   }
   HIP_TRY(ctx, hipMemsetAsync(ctx->d_list_ctr + 7, 0, 5 * sizeof(unsigned long long), st));      // (unsettled and ListProbeArgs::x)
-  ProbeBuf &pb = ctx->ld_pb;
-  const bool host = ctx->probe_fn != nullptr;
-  constexpr uint64_t kFirstMost = 1ull << 22, kMost = 1ull << 24;
+  constexpr uint64_t kFirstMost = 1ull << 22;
   const uint64_t all_seeds = np * seeds;
-  uint64_t want_cap = all_seeds < 4096u ? 4096u : (all_seeds > kFirstMost ? kFirstMost : all_seeds);
-  if (ctx->points_probe_cap) { if (want_cap > ctx->points_probe_cap) want_cap = ctx->points_probe_cap; }
-  else if (want_cap < pb.cap) want_cap = pb.cap;
+  const uint64_t want_cap = all_seeds < 4096u ? 4096u : (all_seeds > kFirstMost ? kFirstMost : all_seeds);
   // a slab that is not settled has an open query; every turn answers what it asks, or hands it to a later turn because the
   // buffers were full -- and then a buffer's worth of the store's seeds has been retired
   const uint64_t max_turns = retries + 2u + 64u + all_seeds / 64u;
-  // a slab per wave, four waves per block; no more blocks than the device holds at once (eight waves per SIMD at the most)
-  const uint64_t want = ((uint64_t)a.n_slabs + kTpBlock / 64 - 1) / (kTpBlock / 64), most = (uint64_t)ctx->num_cu * 8u;
-  const dim3 grid((unsigned)(want < most ? want : most));
-  const dim3 pgrid((unsigned)ctx->num_cu * 4u), pblock(256);
-  unsigned long long t[5] = {0, 0, 0, 0, 0};
-  for (uint64_t turn = 0;; ++turn) {
-    if (turn >= max_turns) return fail(ctx, LENTIL_ERR_INVALID, "trace_points_probed: the turns did not end (internal)");
-    if (pb.cap < want_cap || (host && pb.h_cap < want_cap) || !pb.count) {
-      HIP_TRY(ctx, hipStreamSynchronize(st));       // (the last turn's apply kernel reads the buffers that go)
-      if ((rc = probe_buf_reserve(ctx, pb, want_cap, host))) return rc;
-    }
-    const uint64_t cap = want_cap < 64u ? 64u : want_cap;      // (at most pb.cap: probe_buf_reserve's floor)
-    if (pb.occ_dirty) { HIP_TRY(ctx, hipMemsetAsync(pb.occ, 0, pb.cap, st)); pb.occ_dirty = false; }
-    probe_bind(pb, cap, pr);
-    HIP_TRY(ctx, hipMemsetAsync(pb.count, 0, sizeof(unsigned int), st));
-    HIP_TRY(ctx, hipMemsetAsync(b.unsettled, 0, sizeof(unsigned long long), st));
-    ctx->points_path = lens_dispatch(ctx, po, [&](auto lp) {
-      using T = decltype(lp);
-      if constexpr (T::PO) {
-        if (spectral) {
-          hipLaunchKernelGGL((trace_points_probed_spectral_kernel<typename SpectralLens<typename T::LensT>::Wave, T::kTables>), grid, dim3(kTpBlock), 0, st,
-                             a, pr, b, lambdas);
-          return;
-        }
-      }
-      hipLaunchKernelGGL((trace_points_probed_kernel<typename T::LensT, T::kTables, T::PO>), grid, dim3(kTpBlock), 0, st, a, pr, b);
-    });
-    HIP_TRY(ctx, hipGetLastError());
-    hipLaunchKernelGGL(ld_probe_clamp_kernel, dim3(1), dim3(64), 0, st, pb.count, pr.cap, lb.x);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(t, ctx->d_list_ctr + 7, sizeof t, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (!host) ++ctx->n_dev_waits;
-    const uint64_t raw = t[4], unsettled = t[0];
-    const uint64_t n = raw < cap ? raw : cap;
-    if (n) {
-      if (host) {
-        HIP_TRY(ctx, hipMemcpyAsync(pb.h_seg, pb.seg, (size_t)n * sizeof(lentil_probe_segment), hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        memset(pb.h_occ, 0, (size_t)n);
-        ctx->probe_fn(ctx->probe_user, n, pb.h_seg, pb.h_occ);
-        uint64_t occ = 0;
-        for (uint64_t i = 0; i < n; ++i) occ += pb.h_occ[i] ? 1u : 0u;
-        ctx->n_probes += n; ctx->n_probes_occluded += occ; ++ctx->n_probe_calls;
-        if (occ) HIP_TRY(ctx, hipMemcpyAsync(pb.occ, pb.h_occ, (size_t)n, hipMemcpyHostToDevice, st));
-      } else {
-        if ((rc = probe_call_device(ctx, pb, cap, st))) { pb.occ_dirty = true; return rc; }
-        ctx->n_probes += n;
-        if (n > ctx->dev_longest) ctx->dev_longest = n;
-      }
-      hipLaunchKernelGGL(ld_probe_apply_kernel, pgrid, pblock, 0, st, lb, (const uint32_t *)pb.idx, pb.occ, (const unsigned int *)pb.count, pr.cap);
-      HIP_TRY(ctx, hipGetLastError());
-    }
-    if (!unsettled) break;
-    if (!n) return fail(ctx, LENTIL_ERR_INVALID, "trace_points_probed: a turn left queries open and asked nothing (internal)");
-    if (raw > cap) want_cap = raw * 2u > kMost ? (cap > kMost ? cap : kMost) : raw * 2u;
-  }
-  HIP_TRY(ctx, hipStreamSynchronize(st));       // (the last apply, and the host form's upload from the pinned answers)
-  if (!host) {
-    unsigned long long occ = 0;
-    HIP_TRY(ctx, hipMemcpy(&occ, lb.x + 2, sizeof occ, hipMemcpyDeviceToHost));
-    ctx->n_probes_occluded += occ;
-  }
-  if (device) return LENTIL_OK;
-  HIP_TRY(ctx, hipMemcpy(batch->out_pixel, d_out, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  if (batch->out_xy) HIP_TRY(ctx, hipMemcpy(batch->out_xy, d_xy, (size_t)nq * 2 * sizeof(double), hipMemcpyDeviceToHost));
-  if (batch->out_sensor) HIP_TRY(ctx, hipMemcpy(batch->out_sensor, d_sensor, (size_t)nq * 2 * sizeof(double), hipMemcpyDeviceToHost));
-  if (batch->out_tries) HIP_TRY(ctx, hipMemcpy(batch->out_tries, d_tries, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost));
-  return LENTIL_OK;
+  rc = probe_turns(ctx, pr, lb, want_cap, ctx->points_probe_cap, max_turns, "trace_points_probed: the turns did not end (internal)",
+                   "trace_points_probed: a turn left queries open and asked nothing (internal)", nullptr, [&](const ProbeArgs &q) -> int {
+                     HIP_TRY(ctx, hipMemsetAsync(b.unsettled, 0, sizeof(unsigned long long), st));
+                     ctx->points_path = lens_dispatch(ctx, po, [&](auto lp) {
+                       using T = decltype(lp);
+                       if constexpr (T::PO) {
+                         if (s.spectral) {
+                           hipLaunchKernelGGL((trace_points_probed_spectral_kernel<typename SpectralLens<typename T::LensT>::Wave, T::kTables>), s.grid,
+                                              dim3(kTpBlock), 0, st, a, q, b, s.lambdas);
+                           return;
+                         }
+                       }
+                       hipLaunchKernelGGL((trace_points_probed_kernel<typename T::LensT, T::kTables, T::PO>), s.grid, dim3(kTpBlock), 0, st, a, q, b);
+                     });
+                     HIP_TRY(ctx, hipGetLastError());
+                     return LENTIL_OK;
+                   });
+  if (rc) return rc;
+  return point_batch_finish(ctx, batch, s);
 }
 
 LENTIL_API int lentil_hip_trace_points_probed(lentil_hip_ctx *ctx, const lentil_point_batch *batch, const lentil_point_probe *probe) {

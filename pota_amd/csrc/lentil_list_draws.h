@@ -5,7 +5,8 @@
 // No frame, no accumulators, no counter block, no xor128 state; occlusion probes only in the probed list further down.  Polynomial
 // optics with abb_chromatic != 0 -- three colour channels per attempt, counted by another rule -- have a kernel of their own at
 // the end of this file (list_draws_chroma_kernel, LENTIL_DRAWS_CHANNELS).  A wavelength per visit (lentil_hip_list_draws_spectral)
-// has two kernels of its own behind that one: list_draws_spectral_kernel and list_draws_probed_spectral_kernel.
+// is a policy of the two walks (WaveLambda, lentil_trace_points.h): list_draws_spectral_kernel is ld_walk, as
+// list_draws_kernel is, and list_draws_probed_spectral_kernel is ld_probed_walk, which list_draws_probed_kernel has written out.
 //
 // plan_visits_kernel.  One lane per visit, 64 consecutive visits per wave and step (the five 16-byte columns are read
 // coalesced), grid-stride over such groups; visit_prologue and visit_pixel are the pass's own (load_work_visit), the weight
@@ -126,6 +127,7 @@ LD_DEV float ld_readlane(float x, int src) { return __int_as_float(__builtin_amd
 LD_DEV unsigned long long ld_readlane(unsigned long long x, int src) {
   return (unsigned long long)ld_readlane((uint32_t)x, src) | ((unsigned long long)ld_readlane((uint32_t)(x >> 32), src) << 32);
 }
+LD_DEV double ld_readlane(double x, int src) { return __longlong_as_double((long long)ld_readlane((unsigned long long)__double_as_longlong(x), src)); }
 
 // One wave's wanted lanes take consecutive slots of the list: one atomic per wave (probe_wave_slot, on a 64-bit counter).
 // Called by the whole wave, wmask != 0.
@@ -194,17 +196,18 @@ LD_DEV void ld_store_draw(const ListDrawArgs &a, unsigned long long slot, uint32
   }
 }
 
-template <class LensT, bool kTables, bool PO>
-__global__ __launch_bounds__(kLdBlock) void list_draws_kernel(ListDrawArgs a) {
-  __shared__ DevTerm s_terms[kTables ? kMaxTerms : 1];
-  __shared__ DevLens s_k;
-  if (PO) {
-    stage_lens<kTables>(a.lens, a.terms, a.lambda, kLdBlock, s_terms, &s_k, threadIdx.x == 0);
-    __syncthreads();
-  }
+// The walk of list_draws_kernel and list_draws_spectral_kernel; s_terms / s_k: the block's staged lens.  Lam: the wavelength
+// policy of lentil_trace_points.h.  WaveLambda (lentil_hip_list_draws_spectral) takes visit v at lambdas[v - v_begin]: read in
+// the prologue, lane = visit, one coalesced load per group of 64 visits; the served visit's goes to the whole wave through
+// readlane, like everything else of the visit -- a scalar register, no load inside the walk -- and the wave's row is rewritten
+// before every visit's walk, not between the slabs of one visit.  A wave's trips through every loop here differ from its
+// block's other waves', so nothing waits for the block (see the policy).
+template <class LensT, bool kTables, bool PO, class Lam>
+LD_DEV void ld_walk(const ListDrawArgs &a, const DevTerm *s_terms, const DevLens *s_k, const Lam &lam) {
   LensT L{};
   if constexpr (kTables) L.terms = s_terms;
-  L.k = &s_k;
+  L.k = s_k;
+  lam.bind(L);
   const uint32_t lane = threadIdx.x & 63u;
   const unsigned long long below = (1ull << lane) - 1ull;
   const unsigned long long n_groups = (a.v_end - a.v_begin + 63u) / 64u;
@@ -212,16 +215,21 @@ __global__ __launch_bounds__(kLdBlock) void list_draws_kernel(ListDrawArgs a) {
   for (;;) {
     const unsigned long long g = ld_take_ticket(&a.ctr[0], lane);
     if (g >= n_groups) break;
-    // ---- the prologue, lane = visit
+    // ---- the prologue, lane = visit: its columns and, where the policy stages one, its wavelength
     const uint64_t v = a.v_begin + g * 64u + lane;
     LdVisitLane x{};
-    if (v < a.v_end) x = ld_visit_lane(a.P, a.V, a.lens_length, v);
+    double lam_v = 0.0;
+    if (v < a.v_end) {
+      x = ld_visit_lane(a.P, a.V, a.lens_length, v);
+      lam_v = lam.read(v - a.v_begin);                                   // (indexed by the range, not by the stream)
+    }
     unsigned long long todo = __ballot(x.I.redistribute);
     // ---- the set lanes one after another, lane = attempt
     while (todo) {
       const int src = __builtin_ctzll(todo);
       todo &= todo - 1ull;
       const LdWaveVisit w = ld_broadcast_visit(x, src, (uint32_t)(a.v_begin + g * 64u));
+      if constexpr (Lam::kStaged) lam.stage(ld_readlane(lam_v, src), a.lambda, lane);
       uint32_t accepted = 0, made = 0;
       for (uint32_t k0 = 0; k0 < w.max_total && accepted < w.samples; k0 = ld_next_slab(k0, w.max_total)) {
         const uint32_t attempt = k0 + lane;
@@ -244,6 +252,29 @@ __global__ __launch_bounds__(kLdBlock) void list_draws_kernel(ListDrawArgs a) {
     }
   }
   ld_add_wave_sum(&a.ctr[2], wave_attempts, lane);
+}
+
+template <class LensT, bool kTables, bool PO>
+__global__ __launch_bounds__(kLdBlock) void list_draws_kernel(ListDrawArgs a) {
+  __shared__ DevTerm s_terms[kTables ? kMaxTerms : 1];
+  __shared__ DevLens s_k;
+  if (PO) {
+    stage_lens<kTables>(a.lens, a.terms, a.lambda, kLdBlock, s_terms, &s_k, threadIdx.x == 0);
+    __syncthreads();
+  }
+  ld_walk<LensT, kTables, PO>(a, s_terms, &s_k, FixedLambda{});
+}
+
+// lentil_hip_list_draws_spectral: WaveLambda, polynomial optics with abb_chromatic == 0 (LensT: SpectralLens<...>::Wave of the
+// scalar call's)
+template <class LensT, bool kTables>
+__global__ __launch_bounds__(kLdBlock) void list_draws_spectral_kernel(ListDrawArgs a, const double *lambdas) {
+  __shared__ DevTerm s_terms[kTables ? kMaxTerms : 1];
+  __shared__ DevLens s_k;
+  __shared__ double s_lp[kLdBlock / 64][kMaxExp + 1];
+  stage_lens<kTables>(a.lens, a.terms, a.lambda, kLdBlock, s_terms, &s_k, threadIdx.x == 0);
+  __syncthreads();
+  ld_walk<LensT, kTables, true>(a, s_terms, &s_k, WaveLambda{lambdas, s_lp[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)]});
 }
 
 // ---------------------------------------------------------------------------------------
@@ -384,6 +415,106 @@ struct SeedAnswers {
   }
 };
 
+// One turn's probed walk: list_draws_probed_spectral_kernel calls it, list_draws_probed_kernel behind it has it written out
+// (see there).  Lam: as ld_walk takes it; a visit that a later turn resumes at k_first != 0 stages its row again like any other
+// -- nothing of a wave survives a turn.  A segment asked about does not depend on the wavelength; which seeds get through the
+// lens does.
+template <class LensT, bool kTables, bool PO, class Lam>
+LD_DEV void ld_probed_walk(const ListDrawArgs &a, const ProbeArgs &pr, const ListProbeArgs &b, const DevTerm *s_terms, const DevLens *s_k,
+                           const Lam &lam) {
+  LensT L{};
+  if constexpr (kTables) L.terms = s_terms;
+  L.k = s_k;
+  lam.bind(L);
+  const lentil_params &P = a.P;
+  const uint32_t lane = threadIdx.x & 63u;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  const unsigned long long n_groups = (a.v_end - a.v_begin + 63u) / 64u;
+  unsigned long long wave_attempts = 0, wave_open = 0;
+  for (;;) {
+    const unsigned long long g = ld_take_ticket(&a.ctr[0], lane);
+    if (g >= n_groups) break;
+    // ---- the visits of the group that are not settled, lane = visit
+    const uint64_t v = a.v_begin + g * 64u + lane;
+    LdVisitState S;
+    S.off = 0u; S.k0 = kLdSettled; S.accepted = 0u; S.pad = 0u;
+    if (v < a.v_end) S = b.st[v - a.v_begin];
+    const bool open = S.k0 != kLdSettled;
+    unsigned long long todo = __ballot(open);      // (a group with nothing open falls through the empty loop below)
+    LdVisitLane x{};
+    uint32_t exempt_u = 0u;
+    double lam_v = 0.0;
+    if (open) {
+      x = ld_visit_lane(P, a.V, a.lens_length, v);
+      exempt_u = probe_from_skydome(x.pos_z) ? 1u : 0u;
+      lam_v = lam.read(v - a.v_begin);                                   // (indexed by the range, not by the stream)
+    }
+    // ---- the set lanes one after another, lane = attempt
+    while (todo) {
+      const int src = __builtin_ctzll(todo);
+      todo &= todo - 1ull;
+      const LdWaveVisit w = ld_broadcast_visit(x, src, (uint32_t)(a.v_begin + g * 64u));
+      const uint32_t samples = w.samples, max_total = w.max_total;
+      const uint32_t off = ld_readlane(S.off, src);
+      const uint32_t k_first = ld_readlane(S.k0, src);
+      const float org[3] = {ld_readlane(x.pos_z.x, src), ld_readlane(x.pos_z.y, src), ld_readlane(x.pos_z.z, src)};
+      const float time = ld_readlane(x.raydir_time.w, src);
+      const SeedAnswers seeds{b.A + off, b.B + off, ld_readlane(exempt_u, src) != 0u};
+      // the visit's wavelength, staged in every turn that walks the visit (k_first != 0 too)
+      if constexpr (Lam::kStaged) lam.stage(ld_readlane(lam_v, src), a.lambda, lane);
+      uint32_t accepted = ld_readlane(S.accepted, src);                  // exact while `clean`
+      uint32_t bound = accepted;                                         // what the accepted count can be at most
+      uint32_t made = 0, k_resume = k_first;
+      bool clean = true;                                                 // every slab so far is final
+      for (uint32_t k0 = k_first; k0 < max_total && bound < samples; k0 = ld_next_slab(k0, max_total)) {
+        const uint32_t attempt = k0 + lane;
+        const bool commit = max_total - k0 > lane;
+        // a pass at a seed whose answer is not known leaves the lane dirty: what the attempt comes to is open
+        const AttemptTrace t = trace_attempt<PO>(P, L, a.bokeh, w.cs, w.px, w.py, attempt, commit, seeds);
+        const bool dirty = t.open;
+        const uint32_t pend_m = attempt + (uint32_t)t.tries;
+
+        // ---- who asks: the dirty lanes the reference reaches whatever the open answers are
+        const bool success = commit && !dirty && t.code < LENTIL_POINT_OUTSIDE;
+        const unsigned long long okm = __ballot(success);
+        const unsigned long long dm = __ballot(dirty);
+        const bool ask = dirty && bound + (uint32_t)__builtin_popcountll((okm | dm) & below) < samples;
+        const unsigned long long am = __ballot(ask);
+        if (am) {
+          clean = false;
+          probe_ask_seed(P, pr, ask, b.A + off + (pend_m >> 5), 1u << (pend_m & 31u), off * 32u + pend_m, a.V.cam, time, org, t.lx, t.ly, lane);
+        }
+        if (clean) {
+          // ---- the reference's selection, as ld_walk makes it
+          const bool take = success && accepted + (uint32_t)__builtin_popcountll(okm & below) < samples;
+          const unsigned long long tm = __ballot(take);
+          if (tm) {
+            const unsigned long long slot = list_wave_slot(&a.ctr[1], tm, lane);
+            if (take) ld_store_draw(a, slot, w.visit, attempt, t.code, t.tries, t.xy0, t.xy1);
+          }
+          accepted += (uint32_t)__builtin_popcountll(tm);
+          bound = accepted;
+          made = ld_made(k0, max_total, accepted >= samples, (uint32_t)(63 - __builtin_clzll(tm | 1ull)));
+          k_resume = ld_next_slab(k0, max_total);
+        } else {
+          bound += (uint32_t)__builtin_popcountll(okm | dm);
+        }
+      }
+      if (clean) wave_attempts += made; else ++wave_open;
+      if ((int)lane == src) {
+        LdVisitState s;
+        s.off = off; s.k0 = clean ? kLdSettled : k_resume; s.accepted = accepted; s.pad = 0u;
+        b.st[v - a.v_begin] = s;
+      }
+    }
+  }
+  ld_add_wave_sum(&a.ctr[2], wave_attempts, lane);
+  ld_add_wave_sum(&a.ctr[3], wave_open, lane);
+}
+
+// a.ctr, pr, b: as above the walk, one launch per turn.  What ld_probed_walk is under FixedLambda, written out: as a call of
+// ld_probed_walk the probed list of the compiled-in double gauss measured about 2 % slower than this loop, outside the range
+// of the loop's own runs (profiles/one_loop_kernels.txt), and its SGPR spills rose.  A change to the walk above is made here too.
 template <class LensT, bool kTables, bool PO>
 __global__ __launch_bounds__(kLdBlock) void list_draws_probed_kernel(ListDrawArgs a, ProbeArgs pr, ListProbeArgs b) {
   __shared__ DevTerm s_terms[kTables ? kMaxTerms : 1];
@@ -447,6 +578,7 @@ __global__ __launch_bounds__(kLdBlock) void list_draws_probed_kernel(ListDrawArg
         const unsigned long long am = __ballot(ask);
         if (am) {
           clean = false;
+          // (probe_ask_seed's lines, in place: the call leaves this kernel with other code than the measured one)
           bool win = false;
           const uint32_t bit = 1u << (pend_m & 31u);
           uint32_t *wa = b.A + off + (pend_m >> 5);
@@ -472,7 +604,7 @@ __global__ __launch_bounds__(kLdBlock) void list_draws_probed_kernel(ListDrawArg
           }
         }
         if (clean) {
-          // ---- the reference's selection, as list_draws_kernel makes it
+          // ---- the reference's selection, as ld_walk makes it
           const bool take = success && accepted + (uint32_t)__builtin_popcountll(okm & below) < samples;
           const unsigned long long tm = __ballot(take);
           if (tm) {
@@ -497,6 +629,17 @@ __global__ __launch_bounds__(kLdBlock) void list_draws_probed_kernel(ListDrawArg
   }
   ld_add_wave_sum(&a.ctr[2], wave_attempts, lane);
   ld_add_wave_sum(&a.ctr[3], wave_open, lane);
+}
+
+// the probed list with a wavelength per visit (lentil_hip_list_draws_spectral with LENTIL_DRAWS_PROBED)
+template <class LensT, bool kTables>
+__global__ __launch_bounds__(kLdBlock) void list_draws_probed_spectral_kernel(ListDrawArgs a, ProbeArgs pr, ListProbeArgs b, const double *lambdas) {
+  __shared__ DevTerm s_terms[kTables ? kMaxTerms : 1];
+  __shared__ DevLens s_k;
+  __shared__ double s_lp[kLdBlock / 64][kMaxExp + 1];
+  stage_lens<kTables>(a.lens, a.terms, a.lambda, kLdBlock, s_terms, &s_k, threadIdx.x == 0);
+  __syncthreads();
+  ld_probed_walk<LensT, kTables, true>(a, pr, b, s_terms, &s_k, WaveLambda{lambdas, s_lp[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)]});
 }
 
 // ---------------------------------------------------------------------------------------
@@ -618,215 +761,4 @@ __global__ __launch_bounds__(kLdBlock) void list_draws_chroma_kernel(ListDrawArg
     }
   }
   ld_add_wave_sum(&a.ctr[2], wave_attempts, lane);
-}
-
-// ---------------------------------------------------------------------------------------
-// lentil_hip_list_draws_spectral: visit v at lambdas[v - v_begin] (0: a.lambda, which the host sets to params.lambda_bw),
-// polynomial optics, abb_chromatic == 0.  list_draws_kernel's and list_draws_probed_kernel's walks line for line (kernels of
-// their own, not a parameter of those: the scalar calls' code stays what it is) with the staging of the visit's wavelength in
-// front of the visit's slabs, as trace_points_spectral_kernel stages a point's (lentil_trace_points.h).  A wave serves one
-// visit at a time, so the wavelength is wave-uniform: the block stages the header's constants (and the interpreter's term
-// table) once, every wave keeps the lambda powers of the visit it serves in a row of LDS of its own (LensT =
-// LdsLensAt<LambdaTable> or GenLensAt<Gen>) and rewrites the row before every visit's walk -- not between the slabs of one
-// visit.  The waves of a block take different numbers of trips through every loop here, so nothing waits for the block;
-// nothing has to: the row is the wave's own, written by its lanes 0 ... kMaxExp and read by all of them, and the two
-// wave-scope fences keep the last visit's reads, the writes and this visit's reads in that order.
-// The wavelengths are read in the prologue, lane = visit, one coalesced load per group of 64 visits, and the served visit's
-// goes to the whole wave through readlane, like everything else of the visit (ld_broadcast_visit): a scalar register, no
-// load inside the walk.  In the probed kernel a visit that a later turn resumes at k_first != 0 stages its row again like any
-// other: nothing of a wave survives a turn.  A segment asked about does not depend on the wavelength; which seeds get through
-// the lens does.
-// Every loop is bounded as in the scalar kernels.
-// ---------------------------------------------------------------------------------------
-LD_DEV double ld_readlane(double x, int src) { return __longlong_as_double((long long)ld_readlane((unsigned long long)__double_as_longlong(x), src)); }
-
-// The wave's row of lambda powers for the visit it is about to walk; called by the whole wave, `lambda` wave-uniform.
-LD_DEV void ld_stage_lambda(double *row, double lambda, uint32_t lane) {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  if (lane <= (uint32_t)kMaxExp) row[lane] = lane == 0u ? 1.0 : ipow_u(lambda, lane);      // (ipow_u(x, 1) is x)
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
-template <class LensT, bool kTables>
-__global__ __launch_bounds__(kLdBlock) void list_draws_spectral_kernel(ListDrawArgs a, const double *lambdas) {
-  __shared__ DevTerm s_terms[kTables ? kMaxTerms : 1];
-  __shared__ DevLens s_k;
-  __shared__ double s_lp[kLdBlock / 64][kMaxExp + 1];
-  stage_lens<kTables>(a.lens, a.terms, a.lambda, kLdBlock, s_terms, &s_k, threadIdx.x == 0);
-  __syncthreads();
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  LensT L{};
-  if constexpr (kTables) L.terms = s_terms;
-  L.k = &s_k;
-  L.lam.lp = s_lp[wave];
-  const unsigned long long below = (1ull << lane) - 1ull;
-  const unsigned long long n_groups = (a.v_end - a.v_begin + 63u) / 64u;
-  unsigned long long wave_attempts = 0;
-  for (;;) {
-    const unsigned long long g = ld_take_ticket(&a.ctr[0], lane);
-    if (g >= n_groups) break;
-    // ---- the prologue, lane = visit: its columns and its wavelength
-    const uint64_t v = a.v_begin + g * 64u + lane;
-    LdVisitLane x{};
-    double lam_v = 0.0;
-    if (v < a.v_end) {
-      x = ld_visit_lane(a.P, a.V, a.lens_length, v);
-      lam_v = lambdas[v - a.v_begin];                                    // (indexed by the range, not by the stream)
-    }
-    unsigned long long todo = __ballot(x.I.redistribute);
-    // ---- the set lanes one after another, lane = attempt
-    while (todo) {
-      const int src = __builtin_ctzll(todo);
-      todo &= todo - 1ull;
-      const LdWaveVisit w = ld_broadcast_visit(x, src, (uint32_t)(a.v_begin + g * 64u));
-      double lambda = ld_readlane(lam_v, src);
-      if (lambda == 0.0) lambda = a.lambda;
-      ld_stage_lambda(s_lp[wave], lambda, lane);
-      uint32_t accepted = 0, made = 0;
-      for (uint32_t k0 = 0; k0 < w.max_total && accepted < w.samples; k0 = ld_next_slab(k0, w.max_total)) {
-        const uint32_t attempt = k0 + lane;
-        const bool commit = w.max_total - k0 > lane;
-        const AttemptTrace t = trace_attempt<true>(a.P, L, a.bokeh, w.cs, w.px, w.py, attempt, commit, NoSeedAnswers{});
-
-        // ---- the reference's selection: the successes in attempt order, until `samples` of them are in
-        const bool success = commit && t.code < LENTIL_POINT_OUTSIDE;
-        const unsigned long long okm = __ballot(success);
-        const bool take = success && accepted + (uint32_t)__builtin_popcountll(okm & below) < w.samples;
-        const unsigned long long tm = __ballot(take);
-        if (tm) {
-          const unsigned long long slot = list_wave_slot(&a.ctr[1], tm, lane);
-          if (take) ld_store_draw(a, slot, w.visit, attempt, t.code, t.tries, t.xy0, t.xy1);
-        }
-        accepted += (uint32_t)__builtin_popcountll(tm);
-        made = ld_made(k0, w.max_total, accepted >= w.samples, (uint32_t)(63 - __builtin_clzll(tm | 1ull)));   // (| 1: defined for an empty mask, whose lane nobody asks for)
-      }
-      wave_attempts += made;
-    }
-  }
-  ld_add_wave_sum(&a.ctr[2], wave_attempts, lane);
-}
-
-// a.ctr, pr, b: as list_draws_probed_kernel, one launch per turn
-template <class LensT, bool kTables>
-__global__ __launch_bounds__(kLdBlock) void list_draws_probed_spectral_kernel(ListDrawArgs a, ProbeArgs pr, ListProbeArgs b, const double *lambdas) {
-  __shared__ DevTerm s_terms[kTables ? kMaxTerms : 1];
-  __shared__ DevLens s_k;
-  __shared__ double s_lp[kLdBlock / 64][kMaxExp + 1];
-  stage_lens<kTables>(a.lens, a.terms, a.lambda, kLdBlock, s_terms, &s_k, threadIdx.x == 0);
-  __syncthreads();
-  const lentil_params &P = a.P;
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  LensT L{};
-  if constexpr (kTables) L.terms = s_terms;
-  L.k = &s_k;
-  L.lam.lp = s_lp[wave];
-  const unsigned long long below = (1ull << lane) - 1ull;
-  const unsigned long long n_groups = (a.v_end - a.v_begin + 63u) / 64u;
-  unsigned long long wave_attempts = 0, wave_open = 0;
-  for (;;) {
-    const unsigned long long g = ld_take_ticket(&a.ctr[0], lane);
-    if (g >= n_groups) break;
-    // ---- the visits of the group that are not settled, lane = visit
-    const uint64_t v = a.v_begin + g * 64u + lane;
-    LdVisitState S;
-    S.off = 0u; S.k0 = kLdSettled; S.accepted = 0u; S.pad = 0u;
-    if (v < a.v_end) S = b.st[v - a.v_begin];
-    const bool open = S.k0 != kLdSettled;
-    unsigned long long todo = __ballot(open);      // (a group with nothing open falls through the empty loop below)
-    LdVisitLane x{};
-    uint32_t exempt_u = 0u;
-    double lam_v = 0.0;
-    if (open) {
-      x = ld_visit_lane(P, a.V, a.lens_length, v);
-      exempt_u = probe_from_skydome(x.pos_z) ? 1u : 0u;
-      lam_v = lambdas[v - a.v_begin];                                    // (indexed by the range, not by the stream)
-    }
-    // ---- the set lanes one after another, lane = attempt
-    while (todo) {
-      const int src = __builtin_ctzll(todo);
-      todo &= todo - 1ull;
-      const LdWaveVisit w = ld_broadcast_visit(x, src, (uint32_t)(a.v_begin + g * 64u));
-      const uint32_t samples = w.samples, max_total = w.max_total;
-      const uint32_t off = ld_readlane(S.off, src);
-      const uint32_t k_first = ld_readlane(S.k0, src);
-      const float org[3] = {ld_readlane(x.pos_z.x, src), ld_readlane(x.pos_z.y, src), ld_readlane(x.pos_z.z, src)};
-      const float time = ld_readlane(x.raydir_time.w, src);
-      const SeedAnswers seeds{b.A + off, b.B + off, ld_readlane(exempt_u, src) != 0u};
-      // the visit's wavelength, staged in every turn that walks the visit (k_first != 0 too)
-      double lambda = ld_readlane(lam_v, src);
-      if (lambda == 0.0) lambda = a.lambda;
-      ld_stage_lambda(s_lp[wave], lambda, lane);
-      uint32_t accepted = ld_readlane(S.accepted, src);                  // exact while `clean`
-      uint32_t bound = accepted;                                         // what the accepted count can be at most
-      uint32_t made = 0, k_resume = k_first;
-      bool clean = true;                                                 // every slab so far is final
-      for (uint32_t k0 = k_first; k0 < max_total && bound < samples; k0 = ld_next_slab(k0, max_total)) {
-        const uint32_t attempt = k0 + lane;
-        const bool commit = max_total - k0 > lane;
-        // a pass at a seed whose answer is not known leaves the lane dirty: what the attempt comes to is open
-        const AttemptTrace t = trace_attempt<true>(P, L, a.bokeh, w.cs, w.px, w.py, attempt, commit, seeds);
-        const bool dirty = t.open;
-        const uint32_t pend_m = attempt + (uint32_t)t.tries;
-
-        // ---- who asks: the dirty lanes the reference reaches whatever the open answers are
-        const bool success = commit && !dirty && t.code < LENTIL_POINT_OUTSIDE;
-        const unsigned long long okm = __ballot(success);
-        const unsigned long long dm = __ballot(dirty);
-        const bool ask = dirty && bound + (uint32_t)__builtin_popcountll((okm | dm) & below) < samples;
-        const unsigned long long am = __ballot(ask);
-        if (am) {
-          clean = false;
-          bool win = false;
-          const uint32_t bit = 1u << (pend_m & 31u);
-          uint32_t *wa = b.A + off + (pend_m >> 5);
-          if (ask) win = (atomicOr(wa, bit) & bit) == 0u;
-          const unsigned long long wm = __ballot(win);
-          if (wm) {
-            const uint32_t slot = probe_wave_slot(pr.count, wm, lane);
-            if (win) {
-              if (slot < pr.cap) {
-                float c2w[4][4];
-                probe_cam_to_world(a.V.cam, pr, time, c2w);
-                float tgt[3];
-                probe_target(P, c2w, t.lx, t.ly, 0.0f, tgt);
-                lentil_probe_segment sg;
-                sg.origin[0] = org[0]; sg.origin[1] = org[1]; sg.origin[2] = org[2];
-                sg.target[0] = tgt[0]; sg.target[1] = tgt[1]; sg.target[2] = tgt[2];
-                pr.seg[slot] = sg;
-                pr.idx[slot] = off * 32u + pend_m;
-              } else {
-                atomicAnd(wa, ~bit);
-              }
-            }
-          }
-        }
-        if (clean) {
-          // ---- the reference's selection, as list_draws_kernel makes it
-          const bool take = success && accepted + (uint32_t)__builtin_popcountll(okm & below) < samples;
-          const unsigned long long tm = __ballot(take);
-          if (tm) {
-            const unsigned long long slot = list_wave_slot(&a.ctr[1], tm, lane);
-            if (take) ld_store_draw(a, slot, w.visit, attempt, t.code, t.tries, t.xy0, t.xy1);
-          }
-          accepted += (uint32_t)__builtin_popcountll(tm);
-          bound = accepted;
-          made = ld_made(k0, max_total, accepted >= samples, (uint32_t)(63 - __builtin_clzll(tm | 1ull)));
-          k_resume = ld_next_slab(k0, max_total);
-        } else {
-          bound += (uint32_t)__builtin_popcountll(okm | dm);
-        }
-      }
-      if (clean) wave_attempts += made; else ++wave_open;
-      if ((int)lane == src) {
-        LdVisitState s;
-        s.off = off; s.k0 = clean ? kLdSettled : k_resume; s.accepted = accepted; s.pad = 0u;
-        b.st[v - a.v_begin] = s;
-      }
-    }
-  }
-  ld_add_wave_sum(&a.ctr[2], wave_attempts, lane);
-  ld_add_wave_sum(&a.ctr[3], wave_open, lane);
 }

@@ -18,9 +18,13 @@
 // loops are bounded: at most vignetting_retries + 1 tries, at most 100 Newton iterations (newton_continue).  A compiled-in
 // lens (GenLens<Gen>) runs the same loops over straight-line polynomials.
 //
-// trace_attempt is that trace of one attempt, and the only one: trace_points_kernel calls it once per slab, and so do the
-// list kernels of lentil_list_draws.h (list_draws_kernel, list_draws_probed_kernel; list_draws_chroma_kernel once per colour
-// channel).  What the probed list adds -- answers about the seeds -- comes in as a policy, NoSeedAnswers for everybody else.
+// trace_attempt is that trace of one attempt, and the only one: the slab loop below (tp_slab_loop) calls it once per slab, and
+// so do the walks of lentil_list_draws.h (ld_walk, ld_probed_walk; list_draws_chroma_kernel once per colour channel).  What a
+// probed caller adds -- answers about the seeds -- comes in as a policy, NoSeedAnswers for everybody else.
+//
+// The slab loop is written once, tp_slab_loop, with two compile-time policies: the wavelength (FixedLambda, or WaveLambda's
+// row of LDS per wave) and the answers (TpUnprobed, or TpProbed: a turn of lentil_hip_trace_points_probed).  The kernels at the
+// end of this file declare their LDS, stage the lens and call it; trace_points_spectral_kernel has it written out (see there).
 #pragma once
 #include "lentil_kernels.h"
 
@@ -134,117 +138,57 @@ LD_DEV AttemptTrace trace_attempt(const lentil_params &P, const LensT &L, const 
   return r;
 }
 
-// LensT / kTables: LdsLens with the term table staged into LDS (the interpreter; also the thin lens's, which has no lens: PO
-// false), or GenLens<Gen> of a compiled-in lens -- only the header and the lambda powers in LDS.
-template <class LensT, bool kTables, bool PO>
-__global__ __launch_bounds__(kTpBlock) void trace_points_kernel(TracePointArgs a) {
-  __shared__ DevTerm s_terms[kTables ? kMaxTerms : 1];
-  __shared__ DevLens s_k;
-  if (PO) {
-    stage_lens<kTables>(a.lens, a.terms, a.lambda, kTpBlock, s_terms, &s_k, threadIdx.x == 0);
-    __syncthreads();
-  }
-  LensT L{};
-  if constexpr (kTables) L.terms = s_terms;
-  L.k = &s_k;
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint32_t waves = gridDim.x * (kTpBlock / 64);
-  // (slab < n_slabs - waves before the step: the sum cannot wrap)
-  for (uint32_t slab = blockIdx.x * (kTpBlock / 64) + wave; slab < a.n_slabs; slab = (a.n_slabs - slab > waves) ? slab + waves : a.n_slabs) {
-    const uint32_t point = slab / a.slabs_per_point;
-    const uint32_t k0 = (slab - point * a.slabs_per_point) * kTpSlab;
-    const float cs[3] = {a.cs[(size_t)point * 3], a.cs[(size_t)point * 3 + 1], a.cs[(size_t)point * 3 + 2]};
-    const uint32_t pix = a.pixel[point];
-    const int px = (int)(pix & 0xFFFFu), py = (int)(pix >> 16);
-    const uint32_t attempt = (a.first_attempt ? a.first_attempt[point] : 0u) + k0 + lane;
-    const bool commit = k0 + lane < a.attempts;
-    const uint64_t q = (uint64_t)point * a.attempts + k0 + lane;
-    const AttemptTrace t = trace_attempt<PO>(a.P, L, a.bokeh, cs, px, py, attempt, commit, NoSeedAnswers{});
-    if (commit) {
-      a.out_pixel[q] = t.code;
-      if (a.out_xy) { a.out_xy[q * 2] = t.xy0; a.out_xy[q * 2 + 1] = t.xy1; }            // (the caller's arrays are 8-byte aligned, no more)
-      if (a.out_sensor) { a.out_sensor[q * 2] = t.sen0; a.out_sensor[q * 2 + 1] = t.sen1; }
-      if (a.out_tries) a.out_tries[q] = t.tries;
-    }
-  }
+// ---- the wavelength policy of the trace and list kernels --------------------------------------------------------------------
+// FixedLambda: every point (visit) at a.lambda, whose powers stage_lens put into the block's header; nothing is staged.
+// WaveLambda: point j (visit v_begin + j) at lambdas[j], 0: a.lambda, which the host sets to params.lambda_bw -- polynomial
+// optics.  A wave traces one point (serves one visit) at a time, so the wavelength is wave-uniform: every wave keeps the lambda
+// powers of the one it is at in a row of LDS of its own (LensT = LdsLensAt<LambdaTable> or GenLensAt<Gen>; the block shares the
+// header's constants alone) and rewrites the row when it comes to another.  The waves of a block make different numbers of
+// trips through every loop of these kernels, so nothing in them may wait for the block.  Nothing has to: the row is the wave's
+// own, written by its lanes 0 ... kMaxExp and read by all of them, and LDS serves a wave's accesses in the order it issues
+// them.  What is needed is that the compiler keeps the reads of the last point, the writes, and the reads of this point in that
+// order; the two wave-scope fences say so (DESIGN.md 4.7 has what the loop compiles to).
+LD_DEV void ld_stage_lambda(double *row, double lambda, uint32_t lane) {      // called by the whole wave, `lambda` wave-uniform
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  if (lane <= (uint32_t)kMaxExp) row[lane] = lane == 0u ? 1.0 : ipow_u(lambda, lane);      // (ipow_u(x, 1) is x)
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
 }
 
-// lentil_hip_trace_points_spectral: point j at lambdas[j] (0: a.lambda, which the host sets to params.lambda_bw), polynomial
-// optics.  trace_points_kernel's slab loop line for line (a kernel of its own, not a parameter of that one: the scalar call's
-// code stays what it is) with the staging of the wavelength in front.  A wave traces one point at a time, so the wavelength is
-// wave-uniform: every wave keeps the lambda powers of its point in a row of LDS of its own (LensT = LdsLensAt<LambdaTable> or
-// GenLensAt<Gen>; the block shares the header's constants alone) and rewrites the row when its next slab belongs to another
-// point.  The waves of a block make different numbers of trips through the loop, so nothing in it may wait for the block.
-// Nothing has to: the row is the wave's own, written by its lanes 0 ... kMaxExp and read by all of them, and LDS serves a
-// wave's accesses in the order it issues them.  What is needed is that the compiler keeps the reads of the last slab, the
-// writes, and the reads of this slab in that order; the two wave-scope fences say so (DESIGN.md 4.7 has what the loop compiles
-// to).
-template <class LensT, bool kTables>
-__global__ __launch_bounds__(kTpBlock) void trace_points_spectral_kernel(TracePointArgs a, const double *lambdas) {
-  __shared__ DevTerm s_terms[kTables ? kMaxTerms : 1];
-  __shared__ DevLens s_k;
-  __shared__ double s_lp[kTpBlock / 64][kMaxExp + 1];
-  stage_lens<kTables>(a.lens, a.terms, a.lambda, kTpBlock, s_terms, &s_k, threadIdx.x == 0);
-  __syncthreads();
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint32_t waves = gridDim.x * (kTpBlock / 64);
-  LensT L{};
-  if constexpr (kTables) L.terms = s_terms;
-  L.k = &s_k;
-  L.lam.lp = s_lp[wave];
-  uint32_t staged = 0xFFFFFFFFu;      // (no point: n_points < 2^32)
-  // (slab < n_slabs - waves before the step: the sum cannot wrap)
-  for (uint32_t slab = blockIdx.x * (kTpBlock / 64) + wave; slab < a.n_slabs; slab = (a.n_slabs - slab > waves) ? slab + waves : a.n_slabs) {
-    const uint32_t point = slab / a.slabs_per_point;
-    if (point != staged) {            // wave-uniform
-      double lambda = lambdas[point];
-      if (lambda == 0.0) lambda = a.lambda;
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      if (lane <= (uint32_t)kMaxExp) s_lp[wave][lane] = lane == 0u ? 1.0 : ipow_u(lambda, lane);      // (ipow_u(x, 1) is x)
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      staged = point;
-    }
-    const uint32_t k0 = (slab - point * a.slabs_per_point) * kTpSlab;
-    const float cs[3] = {a.cs[(size_t)point * 3], a.cs[(size_t)point * 3 + 1], a.cs[(size_t)point * 3 + 2]};
-    const uint32_t pix = a.pixel[point];
-    const int px = (int)(pix & 0xFFFFu), py = (int)(pix >> 16);
-    const uint32_t attempt = (a.first_attempt ? a.first_attempt[point] : 0u) + k0 + lane;
-    const bool commit = k0 + lane < a.attempts;
-    const uint64_t q = (uint64_t)point * a.attempts + k0 + lane;
-    const AttemptTrace t = trace_attempt<true>(a.P, L, a.bokeh, cs, px, py, attempt, commit, NoSeedAnswers{});
-    if (commit) {
-      a.out_pixel[q] = t.code;
-      if (a.out_xy) { a.out_xy[q * 2] = t.xy0; a.out_xy[q * 2 + 1] = t.xy1; }            // (the caller's arrays are 8-byte aligned, no more)
-      if (a.out_sensor) { a.out_sensor[q * 2] = t.sen0; a.out_sensor[q * 2 + 1] = t.sen1; }
-      if (a.out_tries) a.out_tries[q] = t.tries;
-    }
-  }
-}
+struct FixedLambda {
+  static constexpr bool kStaged = false;
+  template <class LensT> LD_DEV void bind(LensT &) const {}
+  LD_DEV double read(uint64_t) const { return 0.0; }
+  LD_DEV void stage(double, double, uint32_t) const {}
+};
+
+struct WaveLambda {
+  static constexpr bool kStaged = true;
+  const double *lambdas;
+  double *row;                      // the wave's own: kMaxExp + 1 powers
+  template <class LensT> LD_DEV void bind(LensT &L) const { L.lam.lp = row; }
+  LD_DEV double read(uint64_t j) const { return lambdas[j]; }
+  LD_DEV void stage(double lambda, double fallback, uint32_t lane) const { ld_stage_lambda(row, lambda == 0.0 ? fallback : lambda, lane); }
+};
 
 // ---------------------------------------------------------------------------------------
 // lentil_hip_trace_points_probed: the batch under the context's occlusion probe.  Query (point, m) makes its tries at seeds
 // m + tries, and a try whose segment -- from the point's world position to the try's aperture point -- is occluded fails like
 // one the lens vignettes (thin lens: the attempt is lost).  Which seeds a query reaches depends on the answers, so the batch is
-// traced in turns (lentil_hip.hip: trace_points_probed_call).
+// traced in turns (lentil_hip.hip: probe_turns).
 //
 // The answer store.  Two bits per seed offset 0 ... attempts + max(vignetting_retries, 0) - 1 of every point, in the probed
 // list's encoding (lentil_list_draws.h: (A, B) = (0, 0) never asked about, (1, 0) asked in this turn, (1, 1) clear, (0, 1)
 // occluded), so that ld_probe_apply_kernel serves unchanged.  Every point has the same number of words; point j's begin at
 // j * words_per_point.  A seed's offset is m - first_attempt[point], subtracted on the seed itself.
 //
-// One turn.  trace_points_kernel's slab loop over the slabs that are not settled, trace_attempt with the store's answers.  A
-// lane whose trace comes back `open` -- it got through the lens at a seed whose answer is not known -- asks about that seed:
-// an atomicOr on the A bit elects one lister per (point, seed), across the lanes of a slab, the waves that hold neighbouring
-// slabs of a point, and the blocks; the elected lanes take slots by probe_wave_slot, and one whose slot lies beyond the
-// turn's buffers takes its bit back (the seed is asked about in a later turn; the host grows the buffers from the count).  A
-// lane that is not open has its final outputs -- a known answer never changes -- and writes them (every turn until its slab
+// One turn.  The slab loop over the slabs that are not settled, trace_attempt with the store's answers.  A lane whose trace
+// comes back `open` -- it got through the lens at a seed whose answer is not known -- asks about that seed (probe_ask_seed).
+// A lane that is not open has its final outputs -- a known answer never changes -- and writes them (every turn until its slab
 // settles: the same values).  A slab none of whose lanes is open is settled, a byte per slab; the others are counted for the
 // host.  Every open query asks about, or finds asked, its next seed in every turn, so a query is open for at most
 // max(vignetting_retries, 0) + 1 turns whose lists fit.  A try at a seed known to be occluded fails without a solve
-// (trace_attempt).  Every loop is bounded as in trace_points_kernel.
+// (trace_attempt).  Every loop is bounded as in the unprobed call.
 // ---------------------------------------------------------------------------------------
 struct TracePointProbeArgs {
   const float *origin;            // [n_points][3] world space: the segment's origin
@@ -275,6 +219,36 @@ struct PointSeedAnswers {
   }
 };
 
+// The lanes with `ask` ask about a seed each: `wa` the seed's word of A, `bit` its bit there, `bit_at` its bit index in the
+// whole store.  Neighbouring attempts (the lanes of a slab, the waves that hold neighbouring slabs, the blocks) share seeds: an
+// atomicOr on the A bit elects one lister per seed, the elected lanes take slots by probe_wave_slot, and one whose slot lies
+// beyond the turn's buffers takes its bit back (the seed is asked about in a later turn; the host grows the buffers from the
+// count).  The segment runs from `origin` (world space) to the aperture point (lx, ly) at `time`.  Called by the whole wave.
+LD_DEV void probe_ask_seed(const lentil_params &P, const ProbeArgs &pr, bool ask, uint32_t *wa, uint32_t bit, uint32_t bit_at,
+                           const CamMotion &cam, float time, const float *origin, float lx, float ly, uint32_t lane) {
+  bool win = false;
+  if (ask) win = (atomicOr(wa, bit) & bit) == 0u;
+  const unsigned long long wm = __ballot(win);
+  if (wm) {
+    const uint32_t slot = probe_wave_slot(pr.count, wm, lane);
+    if (win) {
+      if (slot < pr.cap) {
+        float c2w[4][4];
+        probe_cam_to_world(cam, pr, time, c2w);
+        float tgt[3];
+        probe_target(P, c2w, lx, ly, 0.0f, tgt);
+        lentil_probe_segment sg;
+        sg.origin[0] = origin[0]; sg.origin[1] = origin[1]; sg.origin[2] = origin[2];
+        sg.target[0] = tgt[0]; sg.target[1] = tgt[1]; sg.target[2] = tgt[2];
+        pr.seg[slot] = sg;
+        pr.idx[slot] = bit_at;
+      } else {
+        atomicAnd(wa, ~bit);
+      }
+    }
+  }
+}
+
 // What a slab does with its trace: the lanes that are not open commit, the open ones ask.  Called by the whole wave; returns
 // whether some lane is open.
 LD_DEV bool tp_probed_slab(const TracePointArgs &a, const ProbeArgs &pr, const TracePointProbeArgs &b, const AttemptTrace &t, uint32_t point,
@@ -285,56 +259,49 @@ LD_DEV bool tp_probed_slab(const TracePointArgs &a, const ProbeArgs &pr, const T
     if (a.out_sensor) { a.out_sensor[q * 2] = t.sen0; a.out_sensor[q * 2 + 1] = t.sen1; }
     if (a.out_tries) a.out_tries[q] = t.tries;
   }
-  const unsigned long long om = __ballot(t.open);
-  if (!om) return false;
+  if (!__ballot(t.open)) return false;
   const uint32_t off = point * b.words_per_point;                      // (the host refuses a store of 2^27 words or more per array)
   const uint32_t o = attempt + (uint32_t)t.tries - first;              // < attempts + max(vignetting_retries, 0)
-  const uint32_t bit = 1u << (o & 31u);
-  uint32_t *wa = b.A + off + (o >> 5);
-  bool win = false;
-  if (t.open) win = (atomicOr(wa, bit) & bit) == 0u;
-  const unsigned long long wm = __ballot(win);
-  if (wm) {
-    const uint32_t slot = probe_wave_slot(pr.count, wm, lane);
-    if (win) {
-      if (slot < pr.cap) {
-        float c2w[4][4];
-        probe_cam_to_world(b.cam, pr, b.time ? b.time[point] : 0.0f, c2w);
-        float tgt[3];
-        probe_target(a.P, c2w, t.lx, t.ly, 0.0f, tgt);
-        lentil_probe_segment sg;
-        sg.origin[0] = b.origin[(size_t)point * 3]; sg.origin[1] = b.origin[(size_t)point * 3 + 1]; sg.origin[2] = b.origin[(size_t)point * 3 + 2];
-        sg.target[0] = tgt[0]; sg.target[1] = tgt[1]; sg.target[2] = tgt[2];
-        pr.seg[slot] = sg;
-        pr.idx[slot] = off * 32u + o;
-      } else {
-        atomicAnd(wa, ~bit);
-      }
-    }
-  }
+  probe_ask_seed(a.P, pr, t.open, b.A + off + (o >> 5), 1u << (o & 31u), off * 32u + o, b.cam, b.time ? b.time[point] : 0.0f,
+                 b.origin + (size_t)point * 3, t.lx, t.ly, lane);
   return true;
 }
 
-// LensT / kTables / PO: as trace_points_kernel.  One launch per turn.
-template <class LensT, bool kTables, bool PO>
-__global__ __launch_bounds__(kTpBlock) void trace_points_probed_kernel(TracePointArgs a, ProbeArgs pr, TracePointProbeArgs b) {
-  __shared__ DevTerm s_terms[kTables ? kMaxTerms : 1];
-  __shared__ DevLens s_k;
-  if (PO) {
-    stage_lens<kTables>(a.lens, a.terms, a.lambda, kTpBlock, s_terms, &s_k, threadIdx.x == 0);
-    __syncthreads();
-  }
+// the answers policy of the slab loop: nobody probes (NoSeedAnswers, a plain commit), or a turn of the probed call
+struct TpUnprobed {
+  static constexpr bool kProbed = false;
+};
+struct TpProbed {
+  static constexpr bool kProbed = true;
+  const ProbeArgs &pr;
+  const TracePointProbeArgs &b;
+};
+
+// The slab loop of the four kernels below; s_terms / s_k: the block's staged lens.  Lam: the wavelength policy, its row
+// rewritten when the wave's next slab (that is not settled) belongs to another point.
+template <class LensT, bool kTables, bool PO, class Lam, class Probe>
+LD_DEV void tp_slab_loop(const TracePointArgs &a, const DevTerm *s_terms, const DevLens *s_k, const Lam &lam, const Probe &probe) {
   LensT L{};
   if constexpr (kTables) L.terms = s_terms;
-  L.k = &s_k;
+  L.k = s_k;
+  lam.bind(L);
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint32_t waves = gridDim.x * (kTpBlock / 64);
+  uint32_t staged = 0xFFFFFFFFu;      // (no point: n_points < 2^32)
   unsigned long long wave_open = 0;
   // (slab < n_slabs - waves before the step: the sum cannot wrap)
   for (uint32_t slab = blockIdx.x * (kTpBlock / 64) + wave; slab < a.n_slabs; slab = (a.n_slabs - slab > waves) ? slab + waves : a.n_slabs) {
-    if (b.settled[slab]) continue;      // wave-uniform
+    if constexpr (Probe::kProbed) {
+      if (probe.b.settled[slab]) continue;      // wave-uniform
+    }
     const uint32_t point = slab / a.slabs_per_point;
+    if constexpr (Lam::kStaged) {
+      if (point != staged) {                    // wave-uniform
+        lam.stage(lam.read(point), a.lambda, lane);
+        staged = point;
+      }
+    }
     const uint32_t k0 = (slab - point * a.slabs_per_point) * kTpSlab;
     const float cs[3] = {a.cs[(size_t)point * 3], a.cs[(size_t)point * 3 + 1], a.cs[(size_t)point * 3 + 2]};
     const uint32_t pix = a.pixel[point];
@@ -343,21 +310,48 @@ __global__ __launch_bounds__(kTpBlock) void trace_points_probed_kernel(TracePoin
     const uint32_t attempt = first + k0 + lane;
     const bool commit = k0 + lane < a.attempts;
     const uint64_t q = (uint64_t)point * a.attempts + k0 + lane;
-    const size_t off = (size_t)point * b.words_per_point;
-    const PointSeedAnswers seeds{b.A + off, b.B + off, first, b.exempt && b.exempt[point] != 0};
-    const AttemptTrace t = trace_attempt<PO>(a.P, L, a.bokeh, cs, px, py, attempt, commit, seeds);
-    if (tp_probed_slab(a, pr, b, t, point, first, attempt, commit, q, lane)) ++wave_open;
-    else if (lane == 0u) b.settled[slab] = 1;
+    if constexpr (Probe::kProbed) {
+      const TracePointProbeArgs &b = probe.b;
+      const size_t off = (size_t)point * b.words_per_point;
+      const PointSeedAnswers seeds{b.A + off, b.B + off, first, b.exempt && b.exempt[point] != 0};
+      const AttemptTrace t = trace_attempt<PO>(a.P, L, a.bokeh, cs, px, py, attempt, commit, seeds);
+      if (tp_probed_slab(a, probe.pr, b, t, point, first, attempt, commit, q, lane)) ++wave_open;
+      else if (lane == 0u) b.settled[slab] = 1;
+    } else {
+      const AttemptTrace t = trace_attempt<PO>(a.P, L, a.bokeh, cs, px, py, attempt, commit, NoSeedAnswers{});
+      if (commit) {
+        a.out_pixel[q] = t.code;
+        if (a.out_xy) { a.out_xy[q * 2] = t.xy0; a.out_xy[q * 2 + 1] = t.xy1; }            // (the caller's arrays are 8-byte aligned, no more)
+        if (a.out_sensor) { a.out_sensor[q * 2] = t.sen0; a.out_sensor[q * 2 + 1] = t.sen1; }
+        if (a.out_tries) a.out_tries[q] = t.tries;
+      }
+    }
   }
-  if (lane == 0u && wave_open) atomicAdd(b.unsettled, wave_open);
+  if constexpr (Probe::kProbed) {
+    if (lane == 0u && wave_open) atomicAdd(probe.b.unsettled, wave_open);
+  }
 }
 
-// The probed call with a wavelength per point (lentil_point_probe::lambdas), polynomial optics: trace_points_probed_kernel's
-// loop line for line (a kernel of its own: the scalar kernels' code stays what it is) with the wave's own LDS row of lambda
-// powers in front, rewritten when the next slab that is not settled belongs to another point -- what
-// trace_points_spectral_kernel does for trace_points_kernel, fences and all.
+// LensT / kTables: LdsLens with the term table staged into LDS (the interpreter; also the thin lens's, which has no lens: PO
+// false), or GenLens<Gen> of a compiled-in lens -- only the header and the lambda powers in LDS.
+template <class LensT, bool kTables, bool PO>
+__global__ __launch_bounds__(kTpBlock) void trace_points_kernel(TracePointArgs a) {
+  __shared__ DevTerm s_terms[kTables ? kMaxTerms : 1];
+  __shared__ DevLens s_k;
+  if (PO) {
+    stage_lens<kTables>(a.lens, a.terms, a.lambda, kTpBlock, s_terms, &s_k, threadIdx.x == 0);
+    __syncthreads();
+  }
+  tp_slab_loop<LensT, kTables, PO>(a, s_terms, &s_k, FixedLambda{}, TpUnprobed{});
+}
+
+// lentil_hip_trace_points_spectral: a wavelength per point, polynomial optics (LensT: SpectralLens<...>::Wave of the scalar
+// call's).  What tp_slab_loop is under WaveLambda and TpUnprobed, written out: as a call of tp_slab_loop the compiled-in
+// double gauss measured 1.3 % slower than this loop (174.4 against 172.1 ms where two runs of this loop differ by 0.02;
+// profiles/one_loop_kernels.txt), and this is the one of the eight kernels with a rate on record to lose.  A
+// change to the loop above is made here too.
 template <class LensT, bool kTables>
-__global__ __launch_bounds__(kTpBlock) void trace_points_probed_spectral_kernel(TracePointArgs a, ProbeArgs pr, TracePointProbeArgs b, const double *lambdas) {
+__global__ __launch_bounds__(kTpBlock) void trace_points_spectral_kernel(TracePointArgs a, const double *lambdas) {
   __shared__ DevTerm s_terms[kTables ? kMaxTerms : 1];
   __shared__ DevLens s_k;
   __shared__ double s_lp[kTpBlock / 64][kMaxExp + 1];
@@ -371,33 +365,50 @@ __global__ __launch_bounds__(kTpBlock) void trace_points_probed_spectral_kernel(
   L.k = &s_k;
   L.lam.lp = s_lp[wave];
   uint32_t staged = 0xFFFFFFFFu;      // (no point: n_points < 2^32)
-  unsigned long long wave_open = 0;
-  // (slab < n_slabs - waves before the step: the sum cannot wrap)
   for (uint32_t slab = blockIdx.x * (kTpBlock / 64) + wave; slab < a.n_slabs; slab = (a.n_slabs - slab > waves) ? slab + waves : a.n_slabs) {
-    if (b.settled[slab]) continue;      // wave-uniform
     const uint32_t point = slab / a.slabs_per_point;
     if (point != staged) {            // wave-uniform
       double lambda = lambdas[point];
       if (lambda == 0.0) lambda = a.lambda;
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      if (lane <= (uint32_t)kMaxExp) s_lp[wave][lane] = lane == 0u ? 1.0 : ipow_u(lambda, lane);      // (ipow_u(x, 1) is x)
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
+      ld_stage_lambda(s_lp[wave], lambda, lane);
       staged = point;
     }
     const uint32_t k0 = (slab - point * a.slabs_per_point) * kTpSlab;
     const float cs[3] = {a.cs[(size_t)point * 3], a.cs[(size_t)point * 3 + 1], a.cs[(size_t)point * 3 + 2]};
     const uint32_t pix = a.pixel[point];
     const int px = (int)(pix & 0xFFFFu), py = (int)(pix >> 16);
-    const uint32_t first = a.first_attempt ? a.first_attempt[point] : 0u;
-    const uint32_t attempt = first + k0 + lane;
+    const uint32_t attempt = (a.first_attempt ? a.first_attempt[point] : 0u) + k0 + lane;
     const bool commit = k0 + lane < a.attempts;
     const uint64_t q = (uint64_t)point * a.attempts + k0 + lane;
-    const size_t off = (size_t)point * b.words_per_point;
-    const PointSeedAnswers seeds{b.A + off, b.B + off, first, b.exempt && b.exempt[point] != 0};
-    const AttemptTrace t = trace_attempt<true>(a.P, L, a.bokeh, cs, px, py, attempt, commit, seeds);
-    if (tp_probed_slab(a, pr, b, t, point, first, attempt, commit, q, lane)) ++wave_open;
-    else if (lane == 0u) b.settled[slab] = 1;
+    const AttemptTrace t = trace_attempt<true>(a.P, L, a.bokeh, cs, px, py, attempt, commit, NoSeedAnswers{});
+    if (commit) {
+      a.out_pixel[q] = t.code;
+      if (a.out_xy) { a.out_xy[q * 2] = t.xy0; a.out_xy[q * 2 + 1] = t.xy1; }            // (the caller's arrays are 8-byte aligned, no more)
+      if (a.out_sensor) { a.out_sensor[q * 2] = t.sen0; a.out_sensor[q * 2 + 1] = t.sen1; }
+      if (a.out_tries) a.out_tries[q] = t.tries;
+    }
   }
-  if (lane == 0u && wave_open) atomicAdd(b.unsettled, wave_open);
+}
+
+// LensT / kTables / PO: as trace_points_kernel.  One launch per turn.
+template <class LensT, bool kTables, bool PO>
+__global__ __launch_bounds__(kTpBlock) void trace_points_probed_kernel(TracePointArgs a, ProbeArgs pr, TracePointProbeArgs b) {
+  __shared__ DevTerm s_terms[kTables ? kMaxTerms : 1];
+  __shared__ DevLens s_k;
+  if (PO) {
+    stage_lens<kTables>(a.lens, a.terms, a.lambda, kTpBlock, s_terms, &s_k, threadIdx.x == 0);
+    __syncthreads();
+  }
+  tp_slab_loop<LensT, kTables, PO>(a, s_terms, &s_k, FixedLambda{}, TpProbed{pr, b});
+}
+
+// the probed call with a wavelength per point (lentil_point_probe::lambdas), polynomial optics
+template <class LensT, bool kTables>
+__global__ __launch_bounds__(kTpBlock) void trace_points_probed_spectral_kernel(TracePointArgs a, ProbeArgs pr, TracePointProbeArgs b, const double *lambdas) {
+  __shared__ DevTerm s_terms[kTables ? kMaxTerms : 1];
+  __shared__ DevLens s_k;
+  __shared__ double s_lp[kTpBlock / 64][kMaxExp + 1];
+  stage_lens<kTables>(a.lens, a.terms, a.lambda, kTpBlock, s_terms, &s_k, threadIdx.x == 0);
+  __syncthreads();
+  tp_slab_loop<LensT, kTables, true>(a, s_terms, &s_k, WaveLambda{lambdas, s_lp[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)]}, TpProbed{pr, b});
 }
