@@ -1027,6 +1027,31 @@ int lentil_hip_list_draws_path(lentil_hip_ctx *ctx, int *path);   /* 0 thin lens
  * LENTIL_ERR_INVALID: where lentil_hip_list_draws returns it, and for lambdas NULL with polynomial optics and n_visits > 0.
  * n_visits == 0 launches nothing. */
 int lentil_hip_list_draws_spectral(lentil_hip_ctx *ctx, const lentil_draw_list *list, const double *lambdas);
+/* A wavelength per visit in the pass itself, for a spectral renderer that lets the library keep the film: with a column set,
+ * lentil_hip_redistribute over polynomial optics is the reference's pass with lambda_per_sample (src/lentil_filter.cpp:254) =
+ * lambdas[v] for visit v -- the accepted-draw list bit for bit, accumulators, weights and the resolved image at the pass's
+ * usual bar -- with any AOV kinds, cryptomatte, an occlusion probe (host or device callback) and a communicator.
+ *   lambdas [n]  micrometres; lambdas[v] belongs to visit v of the context's stream.  An entry of 0 means params.lambda_bw.
+ *                The values are used as given: there is no range check.  Host memory: copied into device memory of the
+ *                library's before the call returns.  LENTIL_LAMBDAS_DEVICE_POINTER: the column is bound; the caller keeps it
+ *                alive and unchanged while a pass runs.
+ *   lambdas NULL switches the column off: the next pass is the pass without one in every respect.
+ * The column belongs to the stream that was current when it was set.  lentil_hip_upload_visits, lentil_hip_bind_visits and
+ * lentil_hip_visits_end make it stale, and the pass then returns LENTIL_ERR_INVALID until the column is set again or switched
+ * off; so does a column of n wavelengths over a stream of another number of visits (the message names both).
+ * Such a pass runs in the chunked, round-by-round form (lentil_counters::streamed is 0), its solves in solve_po_spectral_kernel:
+ * a wave takes 64 consecutive seeds of one visit at a time, at that visit's wavelength.  A table compiled at run time is served
+ * by the interpreter in it; passes without a column keep their run-time kernel.
+ * Polynomial optics with abb_chromatic != 0: LENTIL_ERR_UNSUPPORTED from the pass, as lentil_hip_list_draws_spectral refuses.
+ * Thin lens: the column's length is checked, the wavelengths are not read; the pass is the pass without a column, and the
+ * statistics below do not count it.  lentil_hip_plan_visits, lentil_hip_list_draws*, lentil_hip_trace_points* and
+ * lentil_hip_camera_rays* do not look at the column.
+ * lentil_hip_spectral_pass_stats: [0] passes run with a column (polynomial optics) since the context was created, [1] the
+ * solve tasks the spectral kernel took in them, [2] the lens path of the last such pass in lentil_hip_list_draws_path's
+ * encoding (1 interpreter, 2 compiled-in lens, 0 none yet), [3] 0. */
+#define LENTIL_LAMBDAS_DEVICE_POINTER 1u
+int lentil_hip_set_visit_lambdas(lentil_hip_ctx *ctx, const double *lambdas, uint64_t n, uint32_t flags);
+int lentil_hip_spectral_pass_stats(lentil_hip_ctx *ctx, uint64_t stats[4]);
 /* The colour channels the draw loop of these parameters traces per attempt (src/lentil_filter.cpp:254-268); needs no context
  * and no GPU.  *n_channels: 3 for polynomial optics with abb_chromatic != 0, else 1 (the thin lens with abb_chromatic > 0
  * picks a channel per attempt from xor128: not described here).  lambda[c]: the channel's wavelength in micrometres, the

@@ -19,6 +19,7 @@ DRAWS_DEVICE_POINTERS = 1
 DRAWS_PROBED = 2                                                                                        # lentil_draw_list::flags
 DRAWS_CHANNELS = 4                                                                                      # ... attempt is n | channel << 30
 DRAWS_PATH_THIN_LENS, DRAWS_PATH_INTERPRETER, DRAWS_PATH_COMPILED_IN = 0, 1, 2                        # lentil_hip_list_draws_path
+LAMBDAS_DEVICE_POINTER = 1                                                                              # lentil_hip_set_visit_lambdas flags
 
 
 class Params(C.Structure):

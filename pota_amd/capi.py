@@ -34,6 +34,7 @@ EXPORTS = [
     "lentil_hip_camera_rays_spectral", "lentil_hip_trace_points_spectral",
     "lentil_hip_plan_visits", "lentil_hip_list_draws", "lentil_hip_list_draws_path", "lentil_hip_draw_channels",
     "lentil_hip_list_draws_spectral", "lentil_hip_trace_points_probed",
+    "lentil_hip_set_visit_lambdas", "lentil_hip_spectral_pass_stats",
     "lentil_hip_set_xor128_state", "lentil_hip_get_xor128_state", "lentil_hip_tl_chroma_stats", "lentil_hip_test_xor128_jump",
     "lentil_hip_host_alloc", "lentil_hip_host_free", "lentil_hip_visits_begin", "lentil_hip_visits_append",
     "lentil_hip_visits_wait", "lentil_hip_visits_end",
@@ -199,6 +200,8 @@ def load_library():
         "lentil_hip_list_draws": (i, [vp, C.POINTER(_abi.DrawList)]),
         "lentil_hip_list_draws_spectral": (i, [vp, C.POINTER(_abi.DrawList), vp]),
         "lentil_hip_list_draws_path": (i, [vp, C.POINTER(C.c_int)]),
+        "lentil_hip_set_visit_lambdas": (i, [vp, vp, u64, u32]),
+        "lentil_hip_spectral_pass_stats": (i, [vp, C.POINTER(u64)]),
         "lentil_hip_draw_channels": (i, [C.POINTER(_abi.Params), C.POINTER(u32), C.POINTER(C.c_double), C.POINTER(C.c_float)]),
         "lentil_hip_set_xor128_state": (i, [vp, C.POINTER(C.c_uint32)]),
         "lentil_hip_get_xor128_state": (i, [vp, C.POINTER(C.c_uint32)]),
@@ -315,7 +318,7 @@ def lens_jit_compile(table, compile=True):
     return int(rc), src.value.decode(), log.value.decode(errors="replace"), float(sec.value), int(nb.value)
 
 
-_LAMBDAS_PER = {"camera_rays": "ray", "trace_points": "point", "list_draws": "visit"}
+_LAMBDAS_PER = {"camera_rays": "ray", "trace_points": "point", "list_draws": "visit", "set_visit_lambdas": "visit"}
 
 
 def _lambdas_arg(call, lambdas, n, device):
@@ -965,6 +968,27 @@ class Context:
         list) since the context was created"""
         n = (C.c_uint64 * 4)()
         self._chk(self.lib.lentil_hip_probe_device_stats(self.h, n))
+        return tuple(int(x) for x in n)
+
+    def set_visit_lambdas(self, lambdas=None, device=False):
+        """a wavelength per visit of the bound stream for the pass (lentil_hip_set_visit_lambdas; micrometres, 0:
+        params.lambda_bw), None: switched off.  device False: a numpy float64 array (or a plain sequence), copied by the
+        library before the call returns; True: a contiguous float64 tensor on this context's GPU, bound -- the context keeps
+        a reference, the caller leaves its content alone while a pass runs.  The column's length is its own: a pass over a
+        stream of another number of visits refuses it."""
+        if lambdas is None:
+            self._lambdas_keep = None
+            self._chk(self.lib.lentil_hip_set_visit_lambdas(self.h, None, 0, 0))
+            return
+        keep, ptr = _lambdas_arg("set_visit_lambdas", lambdas, len(lambdas), self.device if device else None)
+        self._chk(self.lib.lentil_hip_set_visit_lambdas(self.h, ptr, len(lambdas), _abi.LAMBDAS_DEVICE_POINTER if device else 0))
+        self._lambdas_keep = keep if device else None
+
+    def spectral_pass_stats(self):
+        """(passes run with a wavelength column over polynomial optics, solve tasks the spectral kernel took in them, the lens
+        path of the last such pass as list_draws_path reports one, 0) since the context was created"""
+        n = (C.c_uint64 * 4)()
+        self._chk(self.lib.lentil_hip_spectral_pass_stats(self.h, n))
         return tuple(int(x) for x in n)
 
     def set_async(self, on):

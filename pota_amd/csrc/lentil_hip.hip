@@ -151,6 +151,16 @@ struct lentil_hip_ctx {
   bool have_visits = false;
   uint64_t visits_gen = 0;            // counts the visit streams bound so far (cryptomatte columns belong to one of them)
   std::vector<void *> owned_visit_mem;
+  // lentil_hip_set_visit_lambdas: a wavelength per visit for the pass (null: none).  vlam points at the library's copy
+  // (d_vlam, vlam_cap doubles) or at the caller's device memory; vlam_gen: the stream (visits_gen) the column was set for
+  double *d_vlam = nullptr;
+  uint64_t vlam_cap = 0;
+  const double *vlam = nullptr;
+  uint64_t vlam_n = 0, vlam_gen = 0;
+  bool pass_spectral = false;         // redistribute_pass -> stream_pass_applies: the pass being decided has a column and does not stream
+  // lentil_hip_spectral_pass_stats: such passes so far, the solve tasks their kernel took, the last one's lens path
+  uint64_t n_spectral_passes = 0, n_spectral_tasks = 0;
+  int spectral_path = 0;
 
   uint2 *d_work = nullptr;
   uint64_t work_cap = 0;
@@ -796,6 +806,7 @@ LENTIL_API int lentil_hip_destroy(lentil_hip_ctx *ctx) {
   (void)hipFree(ctx->F.zkey_dbg);
   (void)hipFree(ctx->d_resolved);
   (void)hipFree(ctx->d_work);
+  (void)hipFree(ctx->d_vlam);
   for (auto &ch : ctx->chunks) {
     if (ch.stream) (void)hipStreamSynchronize(ch.stream);
     (void)hipFree(ch.hdr); (void)hipFree(ch.prog);
@@ -1826,7 +1837,21 @@ static void launch_slow(lentil_hip_ctx *ctx, const DrawArgs &da, hipStream_t st)
     hipLaunchKernelGGL(solve_slow_kernel, dim3((unsigned)ctx->num_cu * 4), dim3(64), coop_lds_bytes(ctx->hlens.n_terms), st, da);
 }
 
+template <class F>
+static int lens_dispatch(const lentil_hip_ctx *ctx, bool po, F &&f);      // (the lens path of the trace and list kernels, below)
+
+// the one place that launches a round's solves.  A pass with a wavelength column (lentil_hip_set_visit_lambdas) over polynomial
+// optics runs solve_po_spectral_kernel on the lens path the spectral list kernels take -- the compiled-in lens, else the
+// interpreter, which also serves a table compiled at run time -- and parks nothing (da.slow is null: bind_chunk_buffers).
 static void launch_solve(lentil_hip_ctx *ctx, const DrawArgs &da, hipStream_t st, unsigned blocks) {
+  if (da.visit_lambdas && da.P.cameraType == LENTIL_POLYNOMIAL_OPTICS) {
+    ctx->spectral_path = lens_dispatch(ctx, true, [&](auto lp) {
+      using T = decltype(lp);
+      if constexpr (T::PO)
+        hipLaunchKernelGGL((solve_po_spectral_kernel<typename SpectralLens<typename T::LensT>::Wave, T::kTables>), dim3(blocks), dim3(256), 0, st, da);
+    });
+    return;
+  }
   if (da.P.cameraType == LENTIL_POLYNOMIAL_OPTICS) launch_solve_po<false>(ctx, da, st, blocks);
   else hipLaunchKernelGGL(solve_thinlens_kernel, dim3(blocks), dim3(256), 0, st, da);
   launch_slow(ctx, da, st);
@@ -1890,6 +1915,7 @@ static void bind_chunk_buffers(const lentil_hip_ctx::Chunk &ch, DrawArgs &da) {
   const uint64_t usable = ch.slow_cap > (uint64_t)4096 ? ch.slow_cap - 1024 : 0;
   da.slow_cap = (uint32_t)(usable < 0x00FFFFF0ull ? usable : 0x00FFFFF0ull);      // (a pending mark names its slot in 24 bits)
   if (!usable) da.slow = nullptr;
+  if (da.visit_lambdas) da.slow = nullptr;      // (a pass with a wavelength column parks nothing: "no straggler queue")
 }
 
 // rounds with a host check after each (used when the blind rounds did not finish a chunk, and for
@@ -2950,6 +2976,21 @@ static int redistribute_pass(lentil_hip_ctx *ctx) {
                                              "src/lentil_filter.cpp:248-299): not built; the thin lens is probed with any abb_chromatic");
   if (ctx->F.debug_mask && ctx->closest_deferred && !ctx->comm)
     return fail(ctx, LENTIL_ERR_UNSUPPORTED, "the lentil_debug AOV is exchanged between GPUs by lentil_hip_allreduce / _exchange_bands only");
+  // a wavelength per visit (lentil_hip_set_visit_lambdas): the column belongs to one stream and covers all of it -- a frame
+  // that is silently not spectral is worse than an error.  The thin lens reads no wavelength: its pass is the scalar pass.
+  bool spectral = false;
+  if (ctx->vlam) {
+    if (ctx->vlam_gen != ctx->visits_gen)
+      return fail(ctx, LENTIL_ERR_INVALID, "the wavelength column (lentil_hip_set_visit_lambdas) was set for an earlier visit stream: set it again for "
+                                           "this one, or switch it off with lambdas = NULL");
+    if (ctx->vlam_n != ctx->V.n)
+      return fail(ctx, LENTIL_ERR_INVALID, "the wavelength column (lentil_hip_set_visit_lambdas) holds " + std::to_string(ctx->vlam_n) +
+                                               " wavelengths, the visit stream " + std::to_string(ctx->V.n) + " visits");
+    if (P.cameraType == LENTIL_POLYNOMIAL_OPTICS && P.abb_chromatic != 0.0f)
+      return fail(ctx, LENTIL_ERR_UNSUPPORTED, "a wavelength per visit with polynomial optics and abb_chromatic != 0: the mode traces three RGB channels per "
+                                               "attempt, each at a wavelength of its own; the pass has no wavelength per visit for them");
+    spectral = P.cameraType == LENTIL_POLYNOMIAL_OPTICS;
+  }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   { const int rc = crypto_before_pass(ctx); if (rc) return rc; }
   if (ctx->crypto_direct_enqueued) {       // (a pass that failed after it had enqueued them)
@@ -2979,7 +3020,9 @@ static int redistribute_pass(lentil_hip_ctx *ctx) {
     { const int rc = redistribute_tl_chroma(ctx); if (rc) return rc; }      // (with a communicator: on every rank, visits or not)
     streamed = true;          // (nothing of the chunked form below runs)
   } else {
+    ctx->pass_spectral = spectral;       // (stream_pass_applies declines)
     const int rc = redistribute_streamed(ctx, &streamed, &deferred);
+    ctx->pass_spectral = false;
     if (rc) return rc;
     if (ctx->stall_redo) return LENTIL_OK;       // (lentil_hip_redistribute wipes the frame and calls again)
   }
@@ -3032,6 +3075,7 @@ static int redistribute_pass(lentil_hip_ctx *ctx) {
     // ---- draws: per chunk on its own stream
     DrawArgs da{};
     init_draw_args(ctx, da);
+    if (spectral) { da.visit_lambdas = ctx->vlam; ++ctx->n_spectral_passes; }      // (launch_solve, bind_chunk_buffers)
     // solve/accept rounds enqueued without looking (an unused one costs ~30 us, a missing one a host round trip):
     // per chunk what it needed in the previous pass, at least 2 (3 when nothing is known); LENTIL_BLIND_ROUNDS fixes it
     const int forced_rounds = forced_blind_rounds();
@@ -3096,7 +3140,7 @@ static int redistribute_pass(lentil_hip_ctx *ctx) {
           ch.probe_counted = true;
           ch.pb.occ_dirty = true;
           ctx->n_dev_overflows += c.probe_over;       // (the redo's counters start from zero below)
-          HIP_TRY(ctx, hipMemsetAsync((char *)(ctx->d_ctr + ci) + offsetof(DevCounters, probe_n), 0, offsetof(DevCounters, reserved_) - offsetof(DevCounters, probe_n), ch.stream));
+          HIP_TRY(ctx, hipMemsetAsync((char *)(ctx->d_ctr + ci) + offsetof(DevCounters, probe_n), 0, offsetof(DevCounters, spectral_tasks) - offsetof(DevCounters, probe_n), ch.stream));
         }
         ++ctx->last_fallback;
         // the empty rounds left their queue cursors behind: fresh queues, then the chunk again with exact sizes
@@ -3197,7 +3241,7 @@ static int pass_finish(lentil_hip_ctx *ctx) {
       }
     }
     unsigned long long dropped = 0;
-    for (const DevCounters &k : ctx->h_ctr) dropped += k.overflow;
+    for (const DevCounters &k : ctx->h_ctr) { dropped += k.overflow; ctx->n_spectral_tasks += k.spectral_tasks; }      // (0 without a wavelength column)
     if (dropped)
       return fail(ctx, LENTIL_ERR_NOMEM, "the device dropped " + std::to_string(dropped) +
                                              " work items (work list, task queue or result pool too small): the frame is incomplete");
@@ -4691,6 +4735,40 @@ LENTIL_API int lentil_hip_list_draws_path(lentil_hip_ctx *ctx, int *path) {
   CHECK_CTX(ctx);
   if (!path) return fail(ctx, LENTIL_ERR_INVALID, "path is null");
   *path = ctx->draws_path;
+  return LENTIL_OK;
+}
+
+// ---- a wavelength per visit for the pass (redistribute_pass, launch_solve: solve_po_spectral_kernel) ---------------------------
+LENTIL_API int lentil_hip_set_visit_lambdas(lentil_hip_ctx *ctx, const double *lambdas, uint64_t n, uint32_t flags) {
+  CHECK_CTX(ctx);
+  if (flags & ~LENTIL_LAMBDAS_DEVICE_POINTER) return fail(ctx, LENTIL_ERR_INVALID, "set_visit_lambdas: unknown flags");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->vlam = nullptr;
+  ctx->vlam_n = 0;
+  if (!lambdas) return LENTIL_OK;       // switched off
+  if (flags & LENTIL_LAMBDAS_DEVICE_POINTER) {
+    ctx->vlam = lambdas;
+  } else {
+    // (no pass reads the library's copy now: a pass with a column has ended when lentil_hip_redistribute returns)
+    if (n > ctx->vlam_cap) {
+      (void)hipFree(ctx->d_vlam);
+      ctx->d_vlam = nullptr;
+      ctx->vlam_cap = 0;
+      HIP_TRY(ctx, hipMalloc((void **)&ctx->d_vlam, (size_t)n * sizeof(double)));
+      ctx->vlam_cap = n;
+    }
+    if (n) HIP_TRY(ctx, hipMemcpy(ctx->d_vlam, lambdas, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    ctx->vlam = ctx->d_vlam ? ctx->d_vlam : lambdas;      // (n == 0 before any allocation: never read)
+  }
+  ctx->vlam_n = n;
+  ctx->vlam_gen = ctx->visits_gen;
+  return LENTIL_OK;
+}
+
+LENTIL_API int lentil_hip_spectral_pass_stats(lentil_hip_ctx *ctx, uint64_t stats[4]) {
+  CHECK_CTX(ctx);
+  if (!stats) return fail(ctx, LENTIL_ERR_INVALID, "stats is null");
+  stats[0] = ctx->n_spectral_passes; stats[1] = ctx->n_spectral_tasks; stats[2] = (uint64_t)ctx->spectral_path; stats[3] = 0;
   return LENTIL_OK;
 }
 

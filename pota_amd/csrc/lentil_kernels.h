@@ -55,9 +55,10 @@ struct DevCounters {
   // the longest list, lists that did not fit their buffers
   unsigned long long probe_n, probe_occ;
   unsigned int probe_max, probe_over;
-  // (unused: keeps the words below at the offsets they have always had -- which of the atomically updated counters share a
-  // cache line moves with them)
-  unsigned int reserved_[2];
+  // solve tasks taken by solve_po_spectral_kernel in this pass (lentil_hip_spectral_pass_stats), in one of two words that were
+  // unused; the other keeps the words below at the offsets they have always had -- which of the atomically updated counters
+  // share a cache line moves with them
+  unsigned int spectral_tasks, reserved_;
   // diagnostics of a stall (lentil_hip_last_redo_note): accept blocks that have begun, per round parity; what the wave that
   // gave up first saw -- round, parity, the queue's n_tasks, accept_done[0], accept_started[0], its slot's tag word, block
   unsigned int accept_started[2];
@@ -2212,6 +2213,9 @@ struct DrawArgs {
   int32_t item_ready;         // streamed pass, lean tail: parked solves are counted per item (ItemHdr::parked / parked_done) for accept_kernel<3>
   int32_t lean_defer;         // ... and the first accept leaves an item that met parked solves to that accept whole: what it still
                               // needs is decided there, from the stragglers' results
+  // a wavelength per visit of the bound stream (lentil_hip_set_visit_lambdas; 0: P.lambda_bw), read by solve_po_spectral_kernel
+  // alone; null in every other pass
+  const double *visit_lambdas;
 };
 LD_DEV uint32_t slow_queue(const DrawArgs &a) { return a.slow_q >= 0 ? (uint32_t)a.slow_q : (uint32_t)a.parity; }
 LD_DEV uint64_t slow_tag(const DrawArgs &a, uint64_t what) {
@@ -2692,6 +2696,106 @@ __global__ __launch_bounds__(256) LENTIL_SOLVE_ATTR void solve_po_kernel(DrawArg
     if (it64) atomicAdd(&a.ctr->newton_iters, it64);
     if (tr64) atomicAdd(&a.ctr->tries, tr64);
     if (rd64) atomicAdd(&a.ctr->lane_rounds, rd64);
+  }
+}
+
+// ---- solve, polynomial optics, a wavelength per visit (lentil_hip_set_visit_lambdas) --------------------------------
+// The solve kernel of a pass with a wavelength column: a.visit_lambdas[v] is visit v's wavelength, 0: P.lambda_bw.  LensT is
+// SpectralLens<...>::Wave of the scalar pass's lens: the lambda powers come from a row of LDS the wave owns, the block's header
+// keeps the constants.  solve_po_kernel refills single lanes from whatever task comes next, so one of its waves holds solves of
+// several items -- several wavelengths; here a wave takes ONE task at a time, 64 consecutive seeds of one item, stages that
+// item's lambda powers and runs the task's solves to their end: a wave waits for its slowest lane (DevCounters::lane_rounds
+// counts 64 slots per iteration of the slowest, as solve_po_kernel counts 64 per scheduler round).  Nothing is parked
+// (the host passes no straggler queue).  A lane's solve is solve_po_kernel's: po_aperture_sample, newton_init, newton_iter
+// while newton_continue, solve_result -- the same operations in the same order, so at equal wavelengths the codes are equal.
+// Every loop is bounded: the task queue's length, at most 100 Newton iterations (newton_continue).
+template <class LensT, bool kTables>
+__global__ __launch_bounds__(256) void solve_po_spectral_kernel(DrawArgs a) {
+  LENTIL_TL_SPAN(a.round == 0 ? SPAN_SOLVE_R0 : (a.round == 1 ? SPAN_SOLVE_R1 : SPAN_SOLVE_R2));
+  __shared__ DevTerm s_terms[kTables ? kMaxTerms : 1];
+  __shared__ DevLens s_k;
+  __shared__ float s_cdfRow[kMaxBokehRows];
+  __shared__ double s_lp[4][kMaxExp + 1];             // per wave: the lambda powers of the task's item
+  if (kTables) {
+    const uint32_t nt = a.lens->n_terms;
+    for (uint32_t i = threadIdx.x; i < nt; i += blockDim.x) s_terms[i] = a.terms[i];
+  }
+  if (threadIdx.x == 0) s_k = *a.lens;
+  const bool row_in_lds = a.P.bokeh_enable_image && a.bokeh.y <= kMaxBokehRows;
+  if (row_in_lds)
+    for (int i = threadIdx.x; i < a.bokeh.y; i += blockDim.x) s_cdfRow[i] = a.bokeh.cdfRow[i];
+  __syncthreads();
+  const float *cdfRow = row_in_lds ? s_cdfRow : a.bokeh.cdfRow;
+  const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  double *row = s_lp[wv];
+  LensT L;
+  if constexpr (kTables) L.terms = s_terms;
+  L.k = &s_k;
+  L.lam.lp = row;
+  const lentil_params &P = a.P;
+
+  // round r+1's queues are filled by this round's accept kernel: reset them here (nothing else touches them now)
+  if (blockIdx.x == 0 && threadIdx.x == 0 && !a.no_reset) reset_round(a.ctr, (uint32_t)a.parity ^ 1u);
+  const uint32_t par = (uint32_t)a.parity;
+  const Task *tasks = a.tasks[par];
+  uint32_t *res = a.pool[par];
+  const uint32_t n_tasks = a.ctr->n_tasks[par] < a.task_cap ? a.ctr->n_tasks[par] : a.task_cap;
+  const uint32_t lane = lane_id();
+  uint32_t st_iters = 0, st_tries = 0, st_rounds = 0, st_tasks = 0;
+
+  while (true) {
+    uint32_t q = 0;
+    if (lane == 0) q = atomicAdd(&a.ctr->task_head[par], 1u);
+    q = __builtin_amdgcn_readfirstlane(q);
+    if (q >= n_tasks) break;
+    const Task t = tasks[q];
+    const uint32_t item = __builtin_amdgcn_readfirstlane(t.item);
+    const uint32_t m_base = __builtin_amdgcn_readfirstlane(t.m_base);
+    const uint32_t res_off = __builtin_amdgcn_readfirstlane(t.res_off);
+    const uint32_t count = __builtin_amdgcn_readfirstlane(t.count) & 0xFFu;
+    if (count == 0u) continue;         // an item that did not fit left empty tasks
+    ++st_tasks;
+    const ItemHdr *hd = a.hdr + item;
+    const double target[3] = {hd->tx, hd->ty, hd->tz};
+    const uint32_t seed_a = hd->seed_a;
+    // the item's wavelength into the wave's row: written by lanes 0 ... kMaxExp, read by all.  The row is the wave's own and
+    // LDS serves a wave's accesses in the order it issues them; the fences keep the compiler from moving the last task's
+    // reads behind the writes, or this task's reads before them.
+    const uint32_t visit = a.work[item].x;
+    double lambda = a.visit_lambdas[visit];
+    if (lambda == 0.0) lambda = (double)P.lambda_bw;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    if (lane <= (uint32_t)kMaxExp) row[lane] = lane == 0u ? 1.0 : ipow_u(lambda, lane);      // (ipow_u(x, 1) is x: lambda_powers' bits)
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+
+    const bool mine = lane < count;
+    double ap_x = 0.0, ap_y = 0.0;
+    // the reference's try with seed (seed_a, m), src/lentil.h:596-609
+    if (mine) po_aperture_sample(P, a.bokeh, cdfRow, seed_a, m_base + lane, ap_x, ap_y);
+    NewtonState s;
+    newton_init(s);
+    if (mine) ++st_tries;
+    while (true) {
+      const bool go = mine && newton_continue(s);
+      if (__ballot(go) == 0ull) break;
+      if (go) { newton_iter(L, target, ap_x, ap_y, s); ++st_iters; }
+      ++st_rounds;
+    }
+    if (mine) res[res_off + lane] = solve_result(P, L, s);
+  }
+
+  unsigned long long it64 = st_iters, tr64 = st_tries, rd64 = st_rounds;
+  for (int off = 32; off > 0; off >>= 1) {
+    it64 += __shfl_down(it64, off);
+    tr64 += __shfl_down(tr64, off);
+    rd64 += __shfl_down(rd64, off);
+  }
+  if (lane == 0) {
+    if (it64) atomicAdd(&a.ctr->newton_iters, it64);
+    if (tr64) atomicAdd(&a.ctr->tries, tr64);
+    if (rd64) atomicAdd(&a.ctr->lane_rounds, rd64);
+    if (st_tasks) atomicAdd(&a.ctr->spectral_tasks, st_tasks);
   }
 }
 

@@ -228,6 +228,7 @@ static bool stream_pass_applies(lentil_hip_ctx *ctx, DeviceTurn &turn, DrawArgs 
   if (ctx->V.n > 0xFFFFFFF0ull) return false;
   if (no_tries(P)) return false;         // (vignetting_retries < 0: a scan and a count, enqueue_chunk_draws)
   if (probing(ctx)) return false;      // (occlusion probes, host or device callback: answered between a round's solves and its accept -- the round-by-round form)
+  if (ctx->pass_spectral) return false;      // (a wavelength per visit: solve_po_spectral_kernel, launched by the round-by-round form alone)
   // Only into a frame that has been cleared since its last pass (every caller's order: clear, redistribute, resolve): a
   // streamed pass whose waves give up waiting after draws have been accepted is recovered by wiping the frame and running
   // the pass again, which must not cost an earlier pass's sums.  A second pass into the same frame takes the chunked form,
