@@ -1113,6 +1113,19 @@ enum {
  * pixels per tile/group (0 for the two ragged kernels), out[2] dynamic LDS bytes, out[3] blocks launched.  All zero before
  * the first pass.  No effect on the pass. */
 int lentil_hip_debug_last_scan(lentil_hip_ctx *ctx, uint32_t out[4]);
+/* Test hook.  The kernels that replay, after a pass, the cryptomatte adds of the visits that stay in their own pixel; which
+ * one runs follows from the stream's shape and from the LDS a tile needs. */
+enum {
+  LENTIL_CRYPTO_DIRECT_ATOMIC = 1, /* any stream (ragged, or a last pixel short of visits): a lane per visit, atomics */
+  LENTIL_CRYPTO_DIRECT_OWNER = 2,  /* whole pixels: a lane per pixel walks its visits in stream order, no atomics */
+  LENTIL_CRYPTO_DIRECT_TILE = 3    /* ... its tiled form, 128 pixels per block through LDS, where a tile fits 64 KiB */
+};
+/* the own-pixel cryptomatte kernel of the last pass: out[0] kernel (LENTIL_CRYPTO_DIRECT_*; 0 none), out[1] for the tile
+ * kernel its variant (0 the tables are read, added to and written; 1 they hold nothing yet and are only written; 2 the wipe
+ * was put off and every line is written whole), 0 otherwise, out[2] blocks launched, out[3] bit 0: the redistributed-visit
+ * flags came from the pass's work lists, bit 1: a wipe that had been put off was flushed in this call.  All zero before the
+ * first pass with cryptomatte AOVs.  No effect on the pass. */
+int lentil_hip_debug_last_crypto(lentil_hip_ctx *ctx, uint32_t out[4]);
 
 #ifdef __cplusplus
 }

@@ -1148,6 +1148,18 @@ ORC_API void orc_frame_set_crypto(OrcFrame *F, uint32_t n_crypto, uint32_t entri
   }
 }
 
+/* the columns of another stream for a frame that keeps its maps: the next orc_redistribute adds to what the frame holds
+ * (buckets rendered one after the other into one frame) */
+ORC_API int orc_frame_rebind_crypto(OrcFrame *F, uint32_t n_crypto, uint32_t entries, const float *const *hash,
+                                    const float *const *weight) {
+  if (F->crypto.size() != n_crypto || F->crypto_entries != entries) return -1;
+  for (uint32_t c = 0; c < n_crypto; c++) {
+    F->crypto[c].hash = hash[c];
+    F->crypto[c].weight = weight[c];
+  }
+  return 0;
+}
+
 /* Camera::cryptomatte_construct_cache, src/lentil.h:781-811, for one cryptomatte AOV: the depth samples of one AOV
  * sample (opacity RGB and the AOV's float per depth) folded into id -> weight.  AiColorToGrey is the SDK's
  * (r + g + b) / 3 (recalled).  Returns the number of pairs (ids ascending, the map's order); -1 when cap is short. */

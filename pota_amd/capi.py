@@ -27,7 +27,7 @@ EXPORTS = [
     "lentil_hip_set_occlusion_probe_device", "lentil_hip_probe_device_stats", "lentil_hip_test_sphere_occluder_device", "lentil_hip_debug_batch_estimate", "lentil_hip_box_probe",
     "lentil_hip_lens_jit_status", "lentil_hip_lens_jit_wait", "lentil_hip_debug_lens_jit_source", "lentil_hip_debug_lens_jit_compile",
     "lentil_hip_download_draw_log", "lentil_hip_test_lt_sample_aperture",
-    "lentil_hip_test_trace_bw_po", "lentil_hip_test_aperture_sample", "lentil_hip_debug_scan_bands", "lentil_hip_debug_scan_lean_counts", "lentil_hip_debug_last_scan",
+    "lentil_hip_test_trace_bw_po", "lentil_hip_test_aperture_sample", "lentil_hip_debug_scan_bands", "lentil_hip_debug_scan_lean_counts", "lentil_hip_debug_last_scan", "lentil_hip_debug_last_crypto",
     "lentil_hip_lens_is_compiled", "lentil_hip_set_lens_mode",
     "lentil_hip_focus_search", "lentil_hip_test_y0_intersection", "lentil_hip_camera_rays", "lentil_hip_camera_rays_path",
     "lentil_hip_trace_points", "lentil_hip_trace_points_path",
@@ -48,6 +48,9 @@ EXPORTS = [
 SCAN_DMA2, SCAN_DMA, SCAN_DMA_MULTI, SCAN_UNIFORM, SCAN_UNIFORM_MULTI, SCAN_RUNS, SCAN_RAGGED = range(1, 8)
 SCAN_NAMES = {SCAN_DMA2: "dma2", SCAN_DMA: "dma", SCAN_DMA_MULTI: "dma_multi", SCAN_UNIFORM: "uniform",
               SCAN_UNIFORM_MULTI: "uniform_multi", SCAN_RUNS: "runs", SCAN_RAGGED: "ragged"}
+# lentil_hip_debug_last_crypto()[0]: the own-pixel cryptomatte kernels (include/lentil_hip.h, LENTIL_CRYPTO_DIRECT_*)
+CRYPTO_DIRECT_ATOMIC, CRYPTO_DIRECT_OWNER, CRYPTO_DIRECT_TILE = 1, 2, 3
+CRYPTO_FLAGS_FROM_WORK, CRYPTO_WIPE_FLUSHED = 1, 2          # ... [3]'s bits
 
 _lib = None
 
@@ -157,6 +160,7 @@ def load_library():
         "lentil_hip_last_timing": (i, [vp, C.POINTER(C.c_float)]),
         "lentil_hip_last_launches": (i, [vp, C.POINTER(C.c_uint32)]),
         "lentil_hip_debug_last_scan": (i, [vp, C.POINTER(C.c_uint32)]),
+        "lentil_hip_debug_last_crypto": (i, [vp, C.POINTER(C.c_uint32)]),
         "lentil_hip_batch_model_stats": (i, [vp, C.POINTER(C.c_uint64)]),
         "lentil_hip_process_stats": (i, [C.POINTER(C.c_uint64)]),
         "lentil_hip_process_stall_notes": (i, [C.c_char_p, C.c_uint64]),
@@ -1015,6 +1019,13 @@ class Context:
         """(kernel -- SCAN_DMA2 ... SCAN_RAGGED --, pixels per tile/group, dynamic LDS bytes, blocks) of the last pass's scan launch"""
         n = (C.c_uint32 * 4)()
         self._chk(self.lib.lentil_hip_debug_last_scan(self.h, n))
+        return tuple(int(x) for x in n)
+
+    def debug_last_crypto(self):
+        """(kernel -- CRYPTO_DIRECT_ATOMIC / _OWNER / _TILE, 0 none --, the tile kernel's kTables, blocks, bit 0: flags from the
+        work lists | bit 1: a put-off wipe flushed) of the last pass's own-pixel cryptomatte kernel; zeros before the first"""
+        n = (C.c_uint32 * 4)()
+        self._chk(self.lib.lentil_hip_debug_last_crypto(self.h, n))
         return tuple(int(x) for x in n)
 
     def lens_jit_status(self):

@@ -649,6 +649,7 @@ static int crypto_enqueue_direct(lentil_hip_ctx *ctx, hipStream_t st) {
   const unsigned blocks = (unsigned)ctx->num_cu * 8;
   // a wipe that was put off: the tile kernel can stand in for it where its owner lanes write every line of the frame
   bool whole_lines = false;
+  uint32_t hook[4] = {0, 0, 0, 0};          // lentil_hip_debug_last_crypto
   if (k->clear_pending) {
     const VisitsDev &V = ctx->V;
     const bool whole_frame = V.visits_per_pixel && V.n == (uint64_t)k->D.np * V.visits_per_pixel &&
@@ -657,7 +658,7 @@ static int crypto_enqueue_direct(lentil_hip_ctx *ctx, hipStream_t st) {
     const size_t lds_words = (size_t)((128u * V.visits_per_pixel + 3u) & ~3u) + 2u * ((128u * V.visits_per_pixel * k->D.entries + 3u) & ~3u) +
                              2u * 128u * (k->D.slots + 1u) + 2u * 128u;
     whole_lines = whole_frame && k->tables_clear && (k->D.slots & 3u) == 0u && lds_words * 4u <= 64u * 1024u && !(force && force[0] == '0');
-    if (!whole_lines) { const int rc = crypto_flush_clear(ctx, st); if (rc) return rc; }
+    if (!whole_lines) { const int rc = crypto_flush_clear(ctx, st); if (rc) return rc; hook[3] |= 2u; }
   }
   // pixel-major streams whose pixels are all distinct (one pass per clear: the tables hold nothing yet that another
   // lane could be adding to): owner lanes, no atomics
@@ -696,6 +697,7 @@ static int crypto_enqueue_direct(lentil_hip_ctx *ctx, hipStream_t st) {
         }
         HIP_TRY(ctx, hipGetLastError());
         T.flagged = k->d_flag_bits;
+        hook[3] |= 1u;
       }
       const dim3 grid((unsigned)(n_tiles < max_blocks ? n_tiles : max_blocks));
       if (whole_lines)
@@ -705,11 +707,16 @@ static int crypto_enqueue_direct(lentil_hip_ctx *ctx, hipStream_t st) {
       else
         hipLaunchKernelGGL(crypto_direct_tile_kernel<0>, grid, dim3(128), lds, st, k->D, ctx->V, ctx->P, lens_length, T);
       if (whole_lines) k->clear_pending = false;
+      hook[0] = LENTIL_CRYPTO_DIRECT_TILE; hook[1] = whole_lines ? 2u : k->tables_clear ? 1u : 0u; hook[2] = grid.x;
     } else {
       hipLaunchKernelGGL(crypto_direct_owner_kernel, dim3(blocks), dim3(256), 0, st, k->D, ctx->V, ctx->P, lens_length);
+      hook[0] = LENTIL_CRYPTO_DIRECT_OWNER; hook[2] = blocks;
     }
-  } else
+  } else {
     hipLaunchKernelGGL(crypto_direct_kernel, dim3(blocks), dim3(256), 0, st, k->D, ctx->V, ctx->P, lens_length);
+    hook[0] = LENTIL_CRYPTO_DIRECT_ATOMIC; hook[2] = blocks;
+  }
+  for (int i = 0; i < 4; ++i) ctx->last_crypto[i] = hook[i];
   HIP_TRY(ctx, hipGetLastError());
   k->tables_clear = false;
   return LENTIL_OK;

@@ -230,6 +230,7 @@ struct lentil_hip_ctx {
   uint32_t last_scan[4] = {0, 0, 0, 0};      // the last scan launch: kernel (LENTIL_SCAN_*), pixels per tile/group, LDS bytes, blocks (lentil_hip_debug_last_scan)
   unsigned last_scan_skipped = 0;             // blocks of the last scan launch that left at once (scan_dma2_kernel, ScanArgs::skip_blocks)
   int crypto_tile_blocks = 16;               // blocks per CU of crypto_direct_tile_kernel (LENTIL_CRYPTO_TILE_BLOCKS)
+  uint32_t last_crypto[4] = {0, 0, 0, 0};    // the own-pixel cryptomatte kernel of the last pass: kernel (LENTIL_CRYPTO_DIRECT_*), kTables, blocks, bits (lentil_hip_debug_last_crypto)
   bool predict = true;
   uint64_t predict_max_draws = 1536;         // LENTIL_PREDICT_MAX_DRAWS: mean draws per item up to which a pass sizes first batches from the model
   float4 *d_bm_land = nullptr;
@@ -3721,6 +3722,14 @@ LENTIL_API int lentil_hip_debug_last_scan(lentil_hip_ctx *ctx, uint32_t out[4]) 
   CHECK_CTX(ctx);
   if (!out) return fail(ctx, LENTIL_ERR_INVALID, "out is null");
   for (int i = 0; i < 4; ++i) out[i] = ctx->last_scan[i];
+  return LENTIL_OK;
+}
+
+// test hook: which own-pixel cryptomatte kernel the last pass launched, and how (crypto_enqueue_direct)
+LENTIL_API int lentil_hip_debug_last_crypto(lentil_hip_ctx *ctx, uint32_t out[4]) {
+  CHECK_CTX(ctx);
+  if (!out) return fail(ctx, LENTIL_ERR_INVALID, "out is null");
+  for (int i = 0; i < 4; ++i) out[i] = ctx->last_crypto[i];
   return LENTIL_OK;
 }
 

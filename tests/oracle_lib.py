@@ -69,6 +69,7 @@ def load():
         "orc_frame_get_xor128": (None, [vp, C.POINTER(C.c_uint32)]),
         "orc_frame_log": (u64, [vp, vp, u64]),
         "orc_frame_set_crypto": (None, [vp, u32, u32, vp, vp]),
+        "orc_frame_rebind_crypto": (i, [vp, u32, u32, vp, vp]),
         "orc_crypto_construct_cache": (i, [i, vp, vp, vp, vp, i]),
         "orc_crypto_rank": (None, [vp, u32, i, vp, vp]),
         "orc_crypto_pixel": (i, [vp, u32, u64, vp, vp, i, C.POINTER(f)]),
@@ -183,6 +184,16 @@ class Frame:
         hp = (C.c_void_p * n)(*[h.ctypes.data for h in self._crypto_keep[0]])
         wp = (C.c_void_p * n)(*[w.ctypes.data for w in self._crypto_keep[1]])
         self.lib.orc_frame_set_crypto(self.h, n, self._crypto_keep[0][0].shape[1], C.cast(hp, C.c_void_p), C.cast(wp, C.c_void_p))
+
+    def rebind_crypto(self, hashes, weights):
+        """the columns of another stream (as many AOVs and entries); the maps stay: the next run adds to them"""
+        n = len(hashes)
+        keep = ([np.ascontiguousarray(h, np.float32) for h in hashes], [np.ascontiguousarray(w, np.float32) for w in weights])
+        hp = (C.c_void_p * n)(*[h.ctypes.data for h in keep[0]])
+        wp = (C.c_void_p * n)(*[w.ctypes.data for w in keep[1]])
+        rc = self.lib.orc_frame_rebind_crypto(self.h, n, keep[0][0].shape[1], C.cast(hp, C.c_void_p), C.cast(wp, C.c_void_p))
+        assert rc == 0, "rebind_crypto: another number of AOVs or entries than set_crypto's"
+        self._crypto_keep = keep
 
     def set_probe(self, fn, user=None, camera_to_world=None):
         """the occlusion probe (include/lentil_hip.h: lentil_probe_fn) as the address of a C function, e.g. sphere_occluder()"""
